@@ -10,8 +10,13 @@ rasterizer alone with S = 0 (BASELINE.json configs[1]); the default run reports 
 last training stage (C3trace) and BASELINE.json configs[3] (C4trace).  With --gpus N (one rank per GPU) every rank renders its own view
 of the step and the per-gaussian gradients are summed through the factored exchange of materialrefgs_amd/dist.py ("weak" scaling).
 
-Prints ONE JSON line (rank 0).  `roofline` is computed for the dominant kernel from HIP-event durations recorded on the launch stream
-during the timed region; `cpu_baseline` times the CPU checkers (a port: the reference has no CPU path) on one view of the same workload.
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times --steps steps and prints the headline (`value`, `ms_per_step`,
+the host's share of the step) and nothing else.  `--full` adds what takes steps or runs of its own: `roofline` for the dominant kernel
+from HIP-event durations recorded on the launch stream during the timed region (so with --full those sampled events sit in the timed
+region), `stage_ms`, the fenced cold / after-densification / warm figures, the exchange model, `cpu_baseline` (the CPU
+checkers -- a port: the reference has no CPU path -- on one view of the same workload, with the gradient comparison) and, for the
+default workload, the secondary lines.  `--dump-outputs DIR` writes what the last timed step computed (the render outputs and the
+gradients of the parameters, a fixed seeded sample of the larger ones) as DIR/<name>.npy, so that two builds can be compared.
 """
 import argparse
 import json
@@ -139,8 +144,14 @@ def main():
     ap.add_argument("--steps", type=int, default=1000)     # ~1 s timed region at C3full
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--workload", default="C3full", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU oracle leg (also skips grad_max_rel_err)")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary lines of the default run (C2, C2heavy, C3trace, C4trace)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also measure and check everything else: roofline, stage times, fenced cold / warm steps, "
+                         "exchange model, CPU baseline with the oracle comparison, secondary lines of the default workload")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the outputs and parameter gradients of the last timed step as DIR/<name>.npy (float32 / float64; a fixed "
+                         "seeded sample of the larger arrays, 64 MB at most in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle leg (also skips grad_max_rel_err)")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the secondary lines of the default run (C2, C2heavy, C3trace, C4trace)")
     ap.add_argument("--dump-grads", default=None, metavar="PATH",
                     help="after the measurement render step --dump-step once more and let rank 0 save the (reduced) gradient tensors to PATH "
                          "(.npz): tests/test_dist_gpu.py compares a 2-rank run with the sum of two single-rank runs")
@@ -303,6 +314,7 @@ def main():
         if use_loss:
             loss, _tb = losses.calculate_loss(gt_cams[view], pc, out, loss_opt, 5000, gt_cams[view].image_weight, None)
             loss.backward()
+            state["loss"] = loss.detach()
             return
         # the maps calculate_loss consumes (utils/loss_utils.py:147-152,166), with fixed upstream gradients
         outs = [out["render"], out["rend_alpha"], out["rend_normal"], out["rend_dist"], out["surf_depth"], out["surf_normal"]]
@@ -348,6 +360,45 @@ def main():
     forward_fn, backward_fn, exchange_fn = (surfel_forward, surfel_backward, surfel_exchange_and_update) if surfel_mode else \
         (raster_forward, raster_backward, raster_exchange)
 
+    def flat_outputs(res, prefix=""):
+        """name -> detached tensor for every non-empty tensor a caller of the step's render receives (nested dicts as prefix.key)."""
+        items = res.items() if isinstance(res, dict) else zip(("contrib", "color", "feature", "radii", "allmap"), res)
+        flat = {}
+        for k, v in items:
+            if isinstance(v, dict):
+                flat.update(flat_outputs(v, f"{prefix}{k}."))
+            elif torch.is_tensor(v) and v.numel() > 0:
+                flat[prefix + k] = v.detach()
+        return flat
+
+    def step_gradients():
+        """name -> gradient the last step left for each parameter (with several ranks: the reduced sum)."""
+        if surfel_mode:
+            return {n: t_.grad for n, t_ in zip(surfel_names, surfel_params)}
+        if world > 1:
+            return dict(zip(grad_names, state["reduced"]))
+        return {n: t_.grad for n, t_ in zip(grad_names, list(params.values()) + [means2D])}
+
+    def dump_outputs(path, budget=60_000_000):       # bytes of array data: under 64 MB with the .npy headers
+        """--dump-outputs: the last timed step's outputs, its loss and the parameter gradients as path/<name>.npy.  Arrays above an
+        equal share of the budget are reduced to a fixed sample of their flattened elements (seeded by the element count, so the
+        same shape always gives the same positions); floating arrays are written as float32 (float64 stays), integer / bool as float64."""
+        import numpy as np
+        arrays = dict(state["outputs"])
+        if "loss" in state:
+            arrays["loss"] = state["loss"]
+        arrays.update({"grad_" + n: g for n, g in step_gradients().items() if g is not None})
+        cap = max(1, budget // 8 // len(arrays))          # elements per array, 8 bytes each at most
+        os.makedirs(path, exist_ok=True)
+        for name, t_ in arrays.items():
+            flat = t_.detach().reshape(-1)
+            if flat.numel() > cap:
+                idx = np.unique(np.random.default_rng(flat.numel()).integers(0, flat.numel(), cap))
+                flat = flat[torch.from_numpy(idx).to(flat.device)]
+            a = flat.cpu().numpy()
+            a = a.astype(np.float64 if a.dtype == np.float64 or not np.issubdtype(a.dtype, np.floating) else np.float32)
+            np.save(os.path.join(path, name + ".npy"), a.reshape(t_.shape) if a.size == t_.numel() else a)
+
     def step(i):
         """One view, forward and backward, then the exchange and the optimizer step.
         ONE rank: forward AND backward inside ONE rasterizer.deferred_count() box -- the view's pair count, which the GPU produces only
@@ -386,6 +437,12 @@ def main():
                 backward_fn(view, res)
             if _PHASES is not None:
                 _PHASES.append((ta, tb, time.perf_counter()))
+        if i == state.get("dump_step"):
+            # --dump-outputs: the outputs of this step, detached (no graph kept alive, nothing copied inside the timed region)
+            state["outputs"] = flat_outputs(res)
+            vsp = res.get("viewspace_points") if isinstance(res, dict) else None
+            if vsp is not None and vsp.grad is not None:      # render_surfel's screen-space points: what densification reads
+                state["outputs"]["grad_viewspace_points"] = vsp.grad
         exchange_fn(view)
         state["R"] = rasterizer_mod.LAST_NUM_RENDERED
 
@@ -414,14 +471,17 @@ def main():
     if not os.environ.get("MRGS_BENCH_GC_ON"):
         gc.disable()
     # (the warm-up runs with the same sampled event pairs as the timed region: the first timing events on a stream cost the runtime
-    # a one-time set-up that belongs in front of the measurement)
-    L.mrgs_set_profiling(0 if os.environ.get("MRGS_BENCH_NO_KERNEL_EVENTS") else 3)
+    # a one-time set-up that belongs in front of the measurement; only --full records them, for `roofline`)
+    kernel_events = 3 if args.full and not os.environ.get("MRGS_BENCH_NO_KERNEL_EVENTS") else 0
+    L.mrgs_set_profiling(kernel_events)
     for i in range(args.warmup):
         step(i)
     fence()
     # HIP events around the dominant kernel (backward blend, feeds `roofline`) on every fourth launch of the timed region: an event
     # pair costs two ~6 us bubbles on the stream, which every-launch timing would charge to the throughput figure
-    L.mrgs_set_profiling(0 if os.environ.get("MRGS_BENCH_NO_KERNEL_EVENTS") else 3)
+    L.mrgs_set_profiling(kernel_events)
+    if args.dump_outputs:
+        state["dump_step"] = args.warmup + args.steps - 1
     mem0 = (torch.cuda.memory_allocated(dev), torch.cuda.memory_reserved(dev))
     wait0 = rasterizer_mod.COUNT_WAIT_SECONDS
     t0 = time.perf_counter()
@@ -450,6 +510,8 @@ def main():
     fence()
     elapsed = time.perf_counter() - t0
     gc.enable()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs)
     if step_marks is not None and rank == 0:
         mem1 = (torch.cuda.memory_allocated(dev), torch.cuda.memory_reserved(dev))
         print("device memory over the timed region (allocated, reserved) MiB: %.1f, %.1f -> %.1f, %.1f" %
@@ -475,88 +537,83 @@ def main():
             fence()
         with open(os.environ["MRGS_BENCH_TORCH_PROFILE"], "w") as f_:
             f_.write(prof_.key_averages(group_by_stack_n=6).table(sort_by="cuda_time_total", row_limit=60, max_name_column_width=60, max_src_column_width=110))
-    times = MrgsKernelTimes()
-    L.mrgs_get_kernel_times(times)
-    # per-stage breakdown (diagnostic `stage_ms`): a few extra, untimed steps with an event pair around every stage
-    L.mrgs_set_profiling(1)
-    for i in range(min(args.steps, 10)):
-        step(args.warmup + args.steps + i)
-    fence()
-    stage_times = MrgsKernelTimes()
-    L.mrgs_get_kernel_times(stage_times)
-    L.mrgs_set_profiling(0)
-
-    # surfel workloads: torch events around the parts of a view and, with the tracer, around its two native calls (they run on torch's
-    # current stream); a few extra untimed steps
-    trace_ms = {}
-    if surfel_mode:
-        tr_ev = {"surfel_trace_fwd": [], "surfel_trace_bwd": []}
-        if traced:
-            from materialrefgs_amd import surfel_tracing as st_mod
-            orig_f, orig_b = st_mod._Trace.forward, st_mod._Trace.backward
-
-            def timed(name, fn):
-                def wrapper(ctx, *a):
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record()
-                    r = fn(ctx, *a)
-                    e1.record()
-                    tr_ev[name].append((e0, e1))
-                    return r
-                return staticmethod(wrapper)
-            st_mod._Trace.forward, st_mod._Trace.backward = timed("surfel_trace_fwd", orig_f), timed("surfel_trace_bwd", orig_b)
-        state["parts_on"] = True
-        for i in range(min(args.steps, 8)):
-            step(args.warmup + args.steps + 16 + i)
+    if args.full:
+        times = MrgsKernelTimes()
+        L.mrgs_get_kernel_times(times)
+        # per-stage breakdown (diagnostic `stage_ms`): a few extra, untimed steps with an event pair around every stage
+        L.mrgs_set_profiling(1)
+        for i in range(min(args.steps, 10)):
+            step(args.warmup + args.steps + i)
         fence()
-        state["parts_on"] = False
-        if traced:
-            st_mod._Trace.forward, st_mod._Trace.backward = staticmethod(orig_f), staticmethod(orig_b)
-            ls = hw_tracer.tracer.last_state                       # per ray: sum w t^2, final T, hits blended, passes
-            state["trace_hits"] = int(ls[:, 2].sum().item())
-        for name, evs in list(parts.items()) + list(tr_ev.items()):
-            if evs:
-                trace_ms[name] = sum(a.elapsed_time(b) for a, b in evs) / len(evs)
+        stage_times = MrgsKernelTimes()
+        L.mrgs_get_kernel_times(stage_times)
+        L.mrgs_set_profiling(0)
 
-    # First visits: a camera rendered for the first time has no work hint (the forward's queues come from the cull counts) and its
-    # backward orders by itself -- every camera once per training run, and again after each densification.  Timed per step between
-    # fences (so is the warm figure next to it: a fence per step takes the host's launch latency out of hiding, which `ms_per_step` of
-    # the back-to-back timed region does not pay).
-    def fenced_ms(first_index, n):
-        total = 0.0
-        for i in range(n):
+        # surfel workloads: torch events around the parts of a view and, with the tracer, around its two native calls (they run on torch's
+        # current stream); a few extra untimed steps
+        trace_ms = {}
+        if surfel_mode:
+            tr_ev = {"surfel_trace_fwd": [], "surfel_trace_bwd": []}
+            if traced:
+                from materialrefgs_amd import surfel_tracing as st_mod
+                orig_f, orig_b = st_mod._Trace.forward, st_mod._Trace.backward
+
+                def timed(name, fn):
+                    def wrapper(ctx, *a):
+                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        e0.record()
+                        r = fn(ctx, *a)
+                        e1.record()
+                        tr_ev[name].append((e0, e1))
+                        return r
+                    return staticmethod(wrapper)
+                st_mod._Trace.forward, st_mod._Trace.backward = timed("surfel_trace_fwd", orig_f), timed("surfel_trace_bwd", orig_b)
+            state["parts_on"] = True
+            for i in range(min(args.steps, 8)):
+                step(args.warmup + args.steps + 16 + i)
             fence()
-            t_ = time.perf_counter()
-            step(first_index + i)
-            fence()
-            total += time.perf_counter() - t_
-        return 1000.0 * total / n
-    n_cam = len(settings)
-    base_i = ((args.warmup + args.steps + 64) // n_cam + 1) * n_cam
-    warm_fenced = fenced_ms(base_i, n_cam)
-    # ... and the first visit after a densification / pruning step, the normal visit of the reference's first 25 000-30 000 iterations
-    # (every 100 iterations the surfel set changes, and with ~100 training cameras each camera is then seen about once per set): the
-    # camera's measured work is still there (the hint cache is keyed by the camera, not by P), only the deal of its blend waves is redone
-    rasterizer_mod.note_surfel_set_changed()
-    densified_fenced = fenced_ms(base_i, n_cam)
-    rasterizer_mod.reset_work_hints()
-    cold_fenced = fenced_ms(base_i, n_cam)
-    for i in range(2 * n_cam):                                  # leave the hints warm again (second visit: the deal from measured work)
-        step(base_i + i)
-    fence()
+            state["parts_on"] = False
+            if traced:
+                st_mod._Trace.forward, st_mod._Trace.backward = staticmethod(orig_f), staticmethod(orig_b)
+                ls = hw_tracer.tracer.last_state                       # per ray: sum w t^2, final T, hits blended, passes
+                state["trace_hits"] = int(ls[:, 2].sum().item())
+            for name, evs in list(parts.items()) + list(tr_ev.items()):
+                if evs:
+                    trace_ms[name] = sum(a.elapsed_time(b) for a, b in evs) / len(evs)
+
+        # First visits: a camera rendered for the first time has no work hint (the forward's queues come from the cull counts) and its
+        # backward orders by itself -- every camera once per training run, and again after each densification.  Timed per step between
+        # fences (so is the warm figure next to it: a fence per step takes the host's launch latency out of hiding, which `ms_per_step` of
+        # the back-to-back timed region does not pay).
+        def fenced_ms(first_index, n):
+            total = 0.0
+            for i in range(n):
+                fence()
+                t_ = time.perf_counter()
+                step(first_index + i)
+                fence()
+                total += time.perf_counter() - t_
+            return 1000.0 * total / n
+        n_cam = len(settings)
+        base_i = ((args.warmup + args.steps + 64) // n_cam + 1) * n_cam
+        warm_fenced = fenced_ms(base_i, n_cam)
+        # ... and the first visit after a densification / pruning step, the normal visit of the reference's first 25 000-30 000 iterations
+        # (every 100 iterations the surfel set changes, and with ~100 training cameras each camera is then seen about once per set): the
+        # camera's measured work is still there (the hint cache is keyed by the camera, not by P), only the deal of its blend waves is redone
+        rasterizer_mod.note_surfel_set_changed()
+        densified_fenced = fenced_ms(base_i, n_cam)
+        rasterizer_mod.reset_work_hints()
+        cold_fenced = fenced_ms(base_i, n_cam)
+        for i in range(2 * n_cam):                                  # leave the hints warm again (second visit: the deal from measured work)
+            step(base_i + i)
+        fence()
 
     if args.dump_grads:
         step(args.dump_step)
         fence()
         if rank == 0:
             import numpy as np
-            if surfel_mode:
-                dump = {n: t_.grad.detach().cpu().numpy() for n, t_ in zip(surfel_names, surfel_params)}
-            elif world > 1:
-                dump = {n: t_.detach().cpu().numpy() for n, t_ in zip(grad_names, state["reduced"])}
-            else:
-                dump = {n: t_.grad.detach().cpu().numpy() for n, t_ in zip(grad_names, list(params.values()) + [means2D])}
-            np.savez(args.dump_grads, **dump)
+            np.savez(args.dump_grads, **{n: g.detach().cpu().numpy() for n, g in step_gradients().items()})
 
     # What one view-parallel step puts on the links and what every rank computes locally for it (materialrefgs_amd/dist.py), as a model
     # for V = 8 ranks: bytes from the tensor shapes, the time of the local SH expansion measured here by feeding it 8 gathered rows.
@@ -680,7 +737,7 @@ def main():
     if surfel_mode:
         import materialrefgs_amd.renderer as _renderer_mod
         _renderer_mod.set_after_features_hook(None)
-    xmodel = exchange_model() if rank == 0 and torch.cuda.is_available() else None
+    xmodel = exchange_model() if args.full and rank == 0 and torch.cuda.is_available() else None
 
     if world > 1:
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=dev)
@@ -695,8 +752,8 @@ def main():
         "ms_per_step": round(1000.0 * elapsed / args.steps, 4), "timed_region_s": round(elapsed, 4),
         "host_issue_ms_per_step": round(1000.0 * issued / args.steps, 4),
         "host_wait_ms_per_step": round(1000.0 * waited / args.steps, 4), "host_work_ms_per_step": round(1000.0 * host_work / args.steps, 4),
-        "cold_ms_per_step": round(cold_fenced, 4), "after_densify_ms_per_step": round(densified_fenced, 4),
-        "warm_ms_per_step_fenced": round(warm_fenced, 4), "higher_is_better": True, "scaling": "weak",
+        **({"cold_ms_per_step": round(cold_fenced, 4), "after_densify_ms_per_step": round(densified_fenced, 4),
+            "warm_ms_per_step_fenced": round(warm_fenced, 4)} if args.full else {}), "higher_is_better": True, "scaling": "weak",
         "vs_baseline": None, "dtype": "f32", "data": "synthetic",
         "config": {"workload": desc, "P": P, "H": H, "W": W, "S": S, "sh_degree": 3, "num_rendered": int(state["R"]),
                    "views_per_step": world, "cameras_cycled": n_views, "parallelism": f"view-parallel x{world}" if world > 1 else "single GPU"},
@@ -707,65 +764,66 @@ def main():
         import materialrefgs_amd.renderer as _rm
         out["config"]["glue_epilogue"] = bool(_rm._FUSE_GLUE and not indirect and not getattr(pipe, "use_asg", False))
     if rank == 0:
-        R, HW = int(state["R"]), H * W
-        stage_ms = {"preprocess_fwd": stage_times.preprocess_ms, "depth_sort_scan": stage_times.sort_ms,
-                    "duplicate_tilesort_ranges": stage_times.duplicate_ms, "render_fwd": stage_times.render_fwd_ms,
-                    "render_bwd": times.render_bwd_ms, "preprocess_bwd": stage_times.preprocess_bwd_ms}
-        stage_ms.update(trace_ms)
-        # the backward blend is the dominant kernel of the raster / shaded workloads (stage_ms confirms it); its duration comes from
-        # the events of the timed region.  With the tracer the two launches of its forward walk are longer (one "launch" = the mirror
-        # rays of one view); units there: rays, blended hits, surfels.
-        dom = "render_bwd"
-        dom_ms = stage_ms[dom]
-        nbytes = algorithmic_bytes(dom, P, R, HW, S)
-        if traced and trace_ms.get("surfel_trace_fwd", 0.0) > dom_ms:
-            dom, dom_ms = "surfel_trace_fwd", trace_ms["surfel_trace_fwd"]
-            nbytes = algorithmic_bytes(dom, P, state["trace_hits"], HW, S)
-        achieved = nbytes / (dom_ms * 1e-3) / 1e9 if dom_ms > 0 else 0.0
-        # HBM traffic (FETCH_SIZE / WRITE_SIZE passes) and the VALU issue rate (SQ pass) of the dominant kernel come from separate
-        # rocprofv3 --pmc runs of this same command (tools/pmc_traffic.py, tools/pmc_sq.py), which stamp their JSON with the digest of
-        # the kernel sources they measured.  A figure whose digest differs from the sources of THIS run is stale and reported as null.
-        digest = kernel_source_digest()
-        traffic, traffic_src = None, None
-        pmc = _load_json(os.path.join(ROOT, "profiles", "pmc_traffic.json"))
-        if pmc.get("kernel_source_digest") == digest:
-            traffic = pmc.get(args.workload, {}).get(dom)
-            traffic_src = pmc.get("measured_by")
-        out["roofline"] = {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                           "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic,
-                           "algorithmic_bytes_per_launch": int(nbytes), "avg_launch_ms": round(dom_ms, 4),
-                           "kernel_source_digest": digest, "traffic_source": traffic_src}
-        # The dominant kernel is fp32 VALU work (no matrix shape in it) and sits at the VALU issue rate, not at the HBM rate the
-        # required fields above price it against: the SQ counter pass says how close.
-        sqj = _load_json(os.path.join(ROOT, "profiles", "pmc_sq.json"))
-        sq = sqj.get(args.workload, {}).get(dom) if sqj.get("kernel_source_digest") == digest else None
-        out["roofline"]["valu_issue"] = None if not sq else {
-            "cycles_per_inst_per_simd": sq["cycles_per_valu_inst_per_simd"], "peak": 4.0, "frac": round(4.0 / sq["cycles_per_valu_inst_per_simd"], 3),
-            "insts_per_launch": sq["valu_insts_per_launch"], "source": sqj.get("measured_by", "profiles/pmc_sq.json")}
-        out["stage_ms"] = {k: round(v, 4) for k, v in stage_ms.items()}
-        if xmodel is not None:
-            if world == 1:
-                # (render_surfel: the colour factor leaves after the blend backward -- the rasterizer's per-gaussian backward and the glue's
-                #  backward run under its gather --, the indirect factor after the glue's backward; not with the traced term, see above)
-                ov = float(stage_ms.get("preprocess_bwd", 0.0))
-                if surfel_mode:
-                    ov = 0.0 if traced else ov + float(xmodel.get("_feat_bwd_ms", 0.0))
-                xmodel["predicted_scaling"] = predicted_scaling(xmodel, 1000.0 * elapsed / args.steps, ov)
-                # the model's bottom line at top level (the driver's record keeps top-level keys): speed-up of V ranks over one
-                out["predicted_scaling_model"] = {k: v["speedup"] for k, v in xmodel["predicted_scaling"].items() if k.startswith("V")}
-                out["predicted_scaling_model"]["note"] = ("MODEL, not a measurement (no multi-GPU box was available to any round): wire bytes of "
-                                                          "materialrefgs_amd/dist.py over 7 point-to-point xGMI links at 61 GB/s per direction, local "
-                                                          "kernels measured here; inputs under exchange_model")
-            xmodel = {k: v for k, v in xmodel.items() if not k.startswith("_")}
-        out["exchange_model"] = xmodel
+        if args.full:
+            R, HW = int(state["R"]), H * W
+            stage_ms = {"preprocess_fwd": stage_times.preprocess_ms, "depth_sort_scan": stage_times.sort_ms,
+                        "duplicate_tilesort_ranges": stage_times.duplicate_ms, "render_fwd": stage_times.render_fwd_ms,
+                        "render_bwd": times.render_bwd_ms, "preprocess_bwd": stage_times.preprocess_bwd_ms}
+            stage_ms.update(trace_ms)
+            # the backward blend is the dominant kernel of the raster / shaded workloads (stage_ms confirms it); its duration comes from
+            # the events of the timed region.  With the tracer the two launches of its forward walk are longer (one "launch" = the mirror
+            # rays of one view); units there: rays, blended hits, surfels.
+            dom = "render_bwd"
+            dom_ms = stage_ms[dom]
+            nbytes = algorithmic_bytes(dom, P, R, HW, S)
+            if traced and trace_ms.get("surfel_trace_fwd", 0.0) > dom_ms:
+                dom, dom_ms = "surfel_trace_fwd", trace_ms["surfel_trace_fwd"]
+                nbytes = algorithmic_bytes(dom, P, state["trace_hits"], HW, S)
+            achieved = nbytes / (dom_ms * 1e-3) / 1e9 if dom_ms > 0 else 0.0
+            # HBM traffic (FETCH_SIZE / WRITE_SIZE passes) and the VALU issue rate (SQ pass) of the dominant kernel come from separate
+            # rocprofv3 --pmc runs of this same command (tools/pmc_traffic.py, tools/pmc_sq.py), which stamp their JSON with the digest of
+            # the kernel sources they measured.  A figure whose digest differs from the sources of THIS run is stale and reported as null.
+            digest = kernel_source_digest()
+            traffic, traffic_src = None, None
+            pmc = _load_json(os.path.join(ROOT, "profiles", "pmc_traffic.json"))
+            if pmc.get("kernel_source_digest") == digest:
+                traffic = pmc.get(args.workload, {}).get(dom)
+                traffic_src = pmc.get("measured_by")
+            out["roofline"] = {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                               "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic,
+                               "algorithmic_bytes_per_launch": int(nbytes), "avg_launch_ms": round(dom_ms, 4),
+                               "kernel_source_digest": digest, "traffic_source": traffic_src}
+            # The dominant kernel is fp32 VALU work (no matrix shape in it) and sits at the VALU issue rate, not at the HBM rate the
+            # required fields above price it against: the SQ counter pass says how close.
+            sqj = _load_json(os.path.join(ROOT, "profiles", "pmc_sq.json"))
+            sq = sqj.get(args.workload, {}).get(dom) if sqj.get("kernel_source_digest") == digest else None
+            out["roofline"]["valu_issue"] = None if not sq else {
+                "cycles_per_inst_per_simd": sq["cycles_per_valu_inst_per_simd"], "peak": 4.0, "frac": round(4.0 / sq["cycles_per_valu_inst_per_simd"], 3),
+                "insts_per_launch": sq["valu_insts_per_launch"], "source": sqj.get("measured_by", "profiles/pmc_sq.json")}
+            out["stage_ms"] = {k: round(v, 4) for k, v in stage_ms.items()}
+            if xmodel is not None:
+                if world == 1:
+                    # (render_surfel: the colour factor leaves after the blend backward -- the rasterizer's per-gaussian backward and the glue's
+                    #  backward run under its gather --, the indirect factor after the glue's backward; not with the traced term, see above)
+                    ov = float(stage_ms.get("preprocess_bwd", 0.0))
+                    if surfel_mode:
+                        ov = 0.0 if traced else ov + float(xmodel.get("_feat_bwd_ms", 0.0))
+                    xmodel["predicted_scaling"] = predicted_scaling(xmodel, 1000.0 * elapsed / args.steps, ov)
+                    # the model's bottom line at top level (the driver's record keeps top-level keys): speed-up of V ranks over one
+                    out["predicted_scaling_model"] = {k: v["speedup"] for k, v in xmodel["predicted_scaling"].items() if k.startswith("V")}
+                    out["predicted_scaling_model"]["note"] = ("MODEL, not a measurement (no multi-GPU box was available to any round): wire bytes of "
+                                                              "materialrefgs_amd/dist.py over 7 point-to-point xGMI links at 61 GB/s per direction, local "
+                                                              "kernels measured here; inputs under exchange_model")
+                xmodel = {k: v for k, v in xmodel.items() if not k.startswith("_")}
+            out["exchange_model"] = xmodel
         out["host_bound"] = bool(host_work > 0.9 * elapsed)
         if out["host_bound"]:
             # the host's own work (queueing, not waiting for the GPU) filled (nearly) the whole timed region: the figure is then a host figure
             print(f"bench.py: WARNING host_work_ms_per_step {1000.0 * host_work / args.steps:.4f} > 0.9 x ms_per_step {1000.0 * elapsed / args.steps:.4f}: "
                   "the step is paced by the host's launches (Python), not by the GPU", file=sys.stderr)
 
-        if world > 1:
-            pass                         # the CPU baseline and the oracle comparison belong to the N = 1 run only
+        if world > 1 or not args.full:
+            pass                         # the CPU baseline and the oracle comparison belong to the N = 1 run with --full only
         elif not args.no_cpu_baseline and surfel_mode and (traced or use_loss or indirect or flavour != "2dgs"):
             out["cpu_baseline"] = None   # CPU legs exist for the raster workloads and for C3full
         elif not args.no_cpu_baseline and surfel_mode:
@@ -922,7 +980,7 @@ def main():
                                              "unit": "forward views/s at C2/10"}
             except Exception as ex:      # incl. subprocess.TimeoutExpired
                 out["cpu_baseline_torch"] = {"error": type(ex).__name__}
-        if world == 1 and args.workload == "C3full" and not args.no_secondary:
+        if args.full and world == 1 and args.workload == "C3full" and not args.no_secondary:
             # secondary lines, each a fresh child process after everything here is done: the rasterizer alone (C2 = BASELINE.json configs[1],
             # with its own CPU leg, oracle gradient comparison and truth leg), the heavier raster scene (R ~ 6 P, heavy-tailed splat
             # sizes), the last training stage (render_surfel + surfel-traced mirror rays, C3trace) and BASELINE.json configs[3] with the
@@ -931,7 +989,7 @@ def main():
 
             def child(workload, steps, warmup, cpu_leg=False):
                 r = subprocess.run([sys.executable, os.path.abspath(__file__), "--workload", workload, "--steps", str(steps), "--warmup", str(warmup),
-                                    "--no-secondary"] + ([] if cpu_leg else ["--no-cpu-baseline"]), capture_output=True, text=True)
+                                    "--full", "--no-secondary"] + ([] if cpu_leg else ["--no-cpu-baseline"]), capture_output=True, text=True)
                 for line in r.stdout.splitlines():
                     if line.startswith("{"):
                         j = json.loads(line)

@@ -23,7 +23,7 @@ def _bench(tmp_path, name, *args):
     env["MRGS_DIST_BACKEND"] = "gloo"
     env["MRGS_BENCH_VIEWS"] = "8"          # all eight orbit cameras whatever the warm-up: --dump-step k then names camera k in every run
     dump = str(tmp_path / f"{name}.npz")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *args, "--steps", "4", "--warmup", "2", "--no-cpu-baseline", "--no-secondary",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *args, "--steps", "4", "--warmup", "2", "--full", "--no-cpu-baseline", "--no-secondary",
                         "--dump-grads", dump], env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

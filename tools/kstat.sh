@@ -7,7 +7,7 @@ for spec in "$@"; do
   name=${spec%%=*}; lib=${spec#*=}
   if [ -n "$lib" ]; then export MRGS_LIB=$R/$lib; else unset MRGS_LIB; fi
   d=$R/gpurun_out/kstat_$$_$name
-  rocprofv3 --kernel-trace --stats -f csv -d $d -o p -- python3 $R/bench.py --workload $W --steps $K --warmup 6 --no-cpu-baseline --no-secondary > $d.log 2>&1
+  rocprofv3 --kernel-trace --stats -f csv -d $d -o p -- python3 $R/bench.py --full --workload $W --steps $K --warmup 6 --no-cpu-baseline --no-secondary > $d.log 2>&1
   f=$(find $d -name "*kernel_stats.csv" | head -1)
   echo "== $W $name: $(tail -1 $d.log | python3 -c 'import sys,json; print(json.loads(sys.stdin.read())["value"])' 2>/dev/null) views/s"
   python3 - "$f" "$F" <<'PY'

@@ -5,7 +5,7 @@ With the last two arguments the issue-rate extract bench.py reads (profiles/pmc_
 the digest of the kernel sources.
 Pass used for profiles/r1_v7_pmc_sq_C2.json:
   rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAIT_ANY
-            SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY GRBM_GUI_ACTIVE -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline
+            SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY GRBM_GUI_ACTIVE -- python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline
 derived_valu_busy_frac = SQ_ACTIVE_INST_VALU x 4 / (GRBM_GUI_ACTIVE x 1024 SIMDs x ...): see DESIGN.md section 4; the counters are
 summed over the device, GRBM_GUI_ACTIVE counts cycles of one clock domain per XCD (8 instances).
 """

@@ -7,7 +7,7 @@ cd /tmp && export TMPDIR=/tmp
 for spec in "$@"; do
   name=${spec%%=*}; lib=${spec#*=}
   if [ -n "$lib" ]; then export MRGS_LIB=$R/$lib; else unset MRGS_LIB; fi
-  timeout -k 10 240 rocprofv3 --kernel-trace --stats -f csv -d $O/stats_${W}_$name -o p -- python3 $R/bench.py --workload $W --steps $K --warmup 4 --no-cpu-baseline --no-secondary > $O/prof_${W}_$name.log 2>&1
+  timeout -k 10 240 rocprofv3 --kernel-trace --stats -f csv -d $O/stats_${W}_$name -o p -- python3 $R/bench.py --full --workload $W --steps $K --warmup 4 --no-cpu-baseline --no-secondary > $O/prof_${W}_$name.log 2>&1
   f=$(find $O/stats_${W}_$name -name "*kernel_stats.csv" 2>/dev/null | head -1)
   if [ -z "$f" ]; then echo "== $W $name: FAILED (no kernel stats; see prof_${W}_$name.log)"; tail -3 $O/prof_${W}_$name.log; continue; fi
   cp $f $O/${W}_${name}_kernel_stats.csv

@@ -13,12 +13,12 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 cd /tmp && export TMPDIR=/tmp
 O=$R/gpurun_out/round
 rm -rf $O; mkdir -p $O
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -f csv -d $O/stats -o $TAG -- python3 $R/bench.py --workload C2 --steps 30 --warmup 5 --no-cpu-baseline --no-secondary > $O/bench_profiled.log 2>&1
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -f csv -d $O/stats -o $TAG -- python3 $R/bench.py --full --workload C2 --steps 30 --warmup 5 --no-cpu-baseline --no-secondary > $O/bench_profiled.log 2>&1
 for c in FETCH_SIZE WRITE_SIZE; do
-  timeout 300 rocprofv3 --kernel-trace --pmc $c -d $O/pmc_$c -o pmc --output-format csv -- python3 $R/bench.py --workload C2 --steps 5 --warmup 2 --no-cpu-baseline --no-secondary > $O/pmc_$c.log 2>&1
+  timeout 300 rocprofv3 --kernel-trace --pmc $c -d $O/pmc_$c -o pmc --output-format csv -- python3 $R/bench.py --full --workload C2 --steps 5 --warmup 2 --no-cpu-baseline --no-secondary > $O/pmc_$c.log 2>&1
 done
 timeout 300 rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY GRBM_GUI_ACTIVE \
-  -d $O/pmc_sq -o pmc --output-format csv -- python3 $R/bench.py --workload C2 --steps 5 --warmup 2 --no-cpu-baseline --no-secondary > $O/pmc_sq.log 2>&1
+  -d $O/pmc_sq -o pmc --output-format csv -- python3 $R/bench.py --full --workload C2 --steps 5 --warmup 2 --no-cpu-baseline --no-secondary > $O/pmc_sq.log 2>&1
 cd $R
 F=$(find $O/pmc_FETCH_SIZE -name "*counter_collection.csv" | head -1); W=$(find $O/pmc_WRITE_SIZE -name "*counter_collection.csv" | head -1)
 S=$(find $O/pmc_sq -name "*counter_collection.csv" | head -1)
@@ -31,7 +31,7 @@ cp $(find $O/stats -name "*kernel_stats.csv" | head -1) $O/${TAG}_kernel_stats.c
 # the full path (render_surfel with shading) and the traced view: kernel stats and the same counter passes, every kernel of the workload
 for W in C3full C3trace C4trace; do
   cd /tmp
-  timeout 300 rocprofv3 --kernel-trace --stats -f csv -d $O/stats_$W -o ${TAG}_$W -- python3 $R/bench.py --workload $W --steps $([ $W = C4trace ] && echo 8 || echo 20) --warmup 5 --no-cpu-baseline --no-secondary > $O/bench_profiled_$W.log 2>&1
+  timeout 300 rocprofv3 --kernel-trace --stats -f csv -d $O/stats_$W -o ${TAG}_$W -- python3 $R/bench.py --full --workload $W --steps $([ $W = C4trace ] && echo 8 || echo 20) --warmup 5 --no-cpu-baseline --no-secondary > $O/bench_profiled_$W.log 2>&1
   cd $R
   cp $(find $O/stats_$W -name "*kernel_stats.csv" | head -1) $O/${TAG}_${W}_kernel_stats.csv
   tools/pmc_pass.sh round/pmc_$W $W "SQ_WAVES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_WAIT_INST_ANY GRBM_GUI_ACTIVE" \
@@ -39,17 +39,17 @@ for W in C3full C3trace C4trace; do
   cp $O/pmc_$W/pmc_$W.json $O/${TAG}_pmc_$W.json
 done
 cp profiles/pmc_traffic.json $O/pmc_traffic.json; cp profiles/pmc_sq.json $O/pmc_sq.json
-timeout 1500 python bench.py > $O/${TAG}_bench_default.json 2> $O/bench_default.err
-timeout 600 python bench.py --workload C2 --steps 1500 --no-secondary > $O/${TAG}_bench_C2.json 2> $O/bench_C2.err
+timeout 1500 python bench.py --full > $O/${TAG}_bench_default.json 2> $O/bench_default.err
+timeout 600 python bench.py --full --workload C2 --steps 1500 --no-secondary > $O/${TAG}_bench_C2.json 2> $O/bench_C2.err
 if [ "$FULL" = "full" ]; then
-  timeout 600 python bench.py --workload C3 --steps 300 --warmup 20 --no-cpu-baseline > $O/${TAG}_bench_C3.json 2>> $O/bench_C2.err
-  timeout 600 python bench.py --workload C3full --steps 200 --warmup 10 --no-cpu-baseline > $O/${TAG}_bench_C3full.json 2>> $O/bench_C2.err
-  timeout 600 python bench.py --workload C3train --steps 200 --warmup 10 --no-cpu-baseline > $O/${TAG}_bench_C3train.json 2>> $O/bench_C2.err
-  timeout 600 python bench.py --workload C4raster --steps 60 --warmup 5 --no-cpu-baseline > $O/${TAG}_bench_C4raster.json 2>> $O/bench_C2.err
-  timeout 600 python bench.py --workload C4full --steps 60 --warmup 5 --no-cpu-baseline > $O/${TAG}_bench_C4full.json 2>> $O/bench_C2.err
-  timeout 600 python bench.py --workload C3trace --steps 60 --warmup 5 --no-cpu-baseline > $O/${TAG}_bench_C3trace.json 2>> $O/bench_C2.err
-  timeout 600 python bench.py --workload C4trace --steps 30 --warmup 3 --no-cpu-baseline > $O/${TAG}_bench_C4trace.json 2>> $O/bench_C2.err
-  timeout 600 python bench.py --workload C3full-pgsr --steps 200 --warmup 10 --no-cpu-baseline > $O/${TAG}_bench_C3full-pgsr.json 2>> $O/bench_C2.err
+  timeout 600 python bench.py --full --workload C3 --steps 300 --warmup 20 --no-cpu-baseline > $O/${TAG}_bench_C3.json 2>> $O/bench_C2.err
+  timeout 600 python bench.py --full --workload C3full --steps 200 --warmup 10 --no-cpu-baseline > $O/${TAG}_bench_C3full.json 2>> $O/bench_C2.err
+  timeout 600 python bench.py --full --workload C3train --steps 200 --warmup 10 --no-cpu-baseline > $O/${TAG}_bench_C3train.json 2>> $O/bench_C2.err
+  timeout 600 python bench.py --full --workload C4raster --steps 60 --warmup 5 --no-cpu-baseline > $O/${TAG}_bench_C4raster.json 2>> $O/bench_C2.err
+  timeout 600 python bench.py --full --workload C4full --steps 60 --warmup 5 --no-cpu-baseline > $O/${TAG}_bench_C4full.json 2>> $O/bench_C2.err
+  timeout 600 python bench.py --full --workload C3trace --steps 60 --warmup 5 --no-cpu-baseline > $O/${TAG}_bench_C3trace.json 2>> $O/bench_C2.err
+  timeout 600 python bench.py --full --workload C4trace --steps 30 --warmup 3 --no-cpu-baseline > $O/${TAG}_bench_C4trace.json 2>> $O/bench_C2.err
+  timeout 600 python bench.py --full --workload C3full-pgsr --steps 200 --warmup 10 --no-cpu-baseline > $O/${TAG}_bench_C3full-pgsr.json 2>> $O/bench_C2.err
   timeout 300 python tools/trace_time.py 300000 800 mirror > $O/${TAG}_trace_time.json 2>> $O/bench_C2.err
   timeout 300 python tools/trace_time.py 300000 800 primary >> $O/${TAG}_trace_time.json 2>> $O/bench_C2.err
   # the prefilter's batched product per level (matrices warm), with the symmetric tiles and with the full matrices

@@ -10,7 +10,7 @@ for rep in $(seq 1 $REPS); do
     name=${spec%%=*}; rest=${spec#*=}; lib=${rest%%+*}; envs=""
     case "$rest" in *+*) envs=${rest#*+};; esac
     if [ -n "$lib" ]; then export MRGS_LIB=$R/$lib; else unset MRGS_LIB; fi
-    timeout -k 10 400 env $envs python $R/bench.py --workload $W --steps $K --warmup $WU --no-cpu-baseline --no-secondary > $O/${W}_${name}_$rep.json 2> $O/${W}_${name}_$rep.err
+    timeout -k 10 400 env $envs python $R/bench.py --full --workload $W --steps $K --warmup $WU --no-cpu-baseline --no-secondary > $O/${W}_${name}_$rep.json 2> $O/${W}_${name}_$rep.err
     python - "$O/${W}_${name}_$rep.json" "$W $name rep$rep" <<'PY'
 import json, sys
 try:
