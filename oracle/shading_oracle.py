@@ -52,7 +52,7 @@ def _wrap(face, x, y, res):
     v = (y.float() + 0.5) / res * 2 - 1
     u = torch.where(x < 0, torch.full_like(u, -1 - EPS_EDGE), torch.where(x >= res, torch.full_like(u, 1 + EPS_EDGE), u))
     v = torch.where(y < 0, torch.full_like(v, -1 - EPS_EDGE), torch.where(y >= res, torch.full_like(v, 1 + EPS_EDGE), v))
-    d = torch.zeros(u.shape[0], 3)
+    d = torch.zeros(u.shape[0], 3, device=u.device)
     for s in range(6):
         m = face == s
         if m.any():
@@ -65,9 +65,10 @@ def _wrap(face, x, y, res):
     return torch.where(inb, direct, wrapped)
 
 
-def cube_fetch(tex, dirs):
-    """Seamless bilinear fetch of a [6,res,res,C] cubemap at directions [N,3] -> [N,C]."""
-    res = tex.shape[1]
+def bilinear_taps(res, dirs):
+    """The four taps of a seamless bilinear fetch of a res^2 cubemap at directions [N,3]: (idx, w, fx, fy, face) with idx / w lists of
+    four [N] tensors (linear texel index (face res + y) res + x across the edge where a tap leaves the face; weights with the cube corner's
+    tap dropped and the rest renormalised), fx / fy the continuous texel coordinates on the face the direction selects."""
     face, u, v = dir_to_face_uv(dirs)
     fx = (u * 0.5 + 0.5) * res - 0.5
     fy = (v * 0.5 + 0.5) * res - 0.5
@@ -82,12 +83,20 @@ def cube_fetch(tex, dirs):
     w = [torch.where(corner[k], torch.zeros_like(w[k]), w[k]) for k in range(4)]
     any_corner = corner[0] | corner[1] | corner[2] | corner[3]
     norm = torch.where(any_corner, 1.0 / (w[0] + w[1] + w[2] + w[3]).detach(), torch.ones_like(wx))   # renormalisation held constant
+    idx = []
+    for k in range(4):
+        i = _wrap(face, x0 + offs[k][0], y0 + offs[k][1], res)
+        idx.append(torch.where(corner[k], torch.zeros_like(i), i))
+    return idx, [w[k] * norm for k in range(4)], fx, fy, face
+
+
+def cube_fetch(tex, dirs):
+    """Seamless bilinear fetch of a [6,res,res,C] cubemap at directions [N,3] -> [N,C]."""
+    idx, w, _, _, _ = bilinear_taps(tex.shape[1], dirs)
     flat = tex.reshape(-1, tex.shape[-1])
     out = 0
     for k in range(4):
-        idx = _wrap(face, x0 + offs[k][0], y0 + offs[k][1], res)
-        idx = torch.where(corner[k], torch.zeros_like(idx), idx)
-        out = out + (w[k] * norm).unsqueeze(-1) * flat[idx]
+        out = out + w[k].unsqueeze(-1) * flat[idx[k]]
     return out
 
 
@@ -110,7 +119,7 @@ def env_lookup(mips, dirs, roughness=None, min_roughness=0.08, max_roughness=0.5
     l1 = torch.clamp(l0 + 1, max=n - 1)
     f = lc - l0.float()
     samples = torch.stack([cube_fetch(m, dirs) for m in mips], 0)   # [n,N,3]
-    ar = torch.arange(dirs.shape[0])
+    ar = torch.arange(dirs.shape[0], device=dirs.device)
     val = (1 - f).unsqueeze(-1) * samples[l0, ar] + f.unsqueeze(-1) * samples[l1, ar]
     return torch.sigmoid(val)
 
@@ -144,8 +153,8 @@ def specular_color_surfel(mips, lut, albedo, H, W, K, R, T, normal_map, render_a
     """get_specular_color_surfel (utils/refl_utils.py:364-419) with pc.ray_tracer = None.
     albedo/normal_map [H,W,3], render_alpha/refl_strength/roughness [H,W,1] -> specular [3,H,W], direct_light [3,H,W],
     specular_weight [H,W,3]."""
-    rays_cam, _ = sample_camera_rays(H, W, K, R, T)
-    w_o = -rays_cam
+    rays_cam, _ = sample_camera_rays(H, W, K, R.cpu(), T.cpu())
+    w_o = -rays_cam.to(normal_map.device)
     NdotV = torch.sum(w_o * normal_map, dim=-1, keepdim=True)
     rays_refl = 2 * normal_map * NdotV - w_o
     rays_refl = rays_refl / torch.clamp(torch.linalg.norm(rays_refl, dim=-1, keepdim=True), min=1e-20)
@@ -155,3 +164,116 @@ def specular_color_surfel(mips, lut, albedo, H, W, K, R, T, normal_map, render_a
     specular_weight = (0.04 * (1 - refl_strength) + albedo * refl_strength) * fg[..., 0:1] + fg[..., 1:2]
     specular = direct_light * render_alpha * specular_weight
     return specular.permute(2, 0, 1), direct_light.permute(2, 0, 1), specular_weight
+
+
+def mirror_dirs(H, W, K, R, T, normal_map):
+    """The normalised mirror directions [H*W,3] and NdotV [H*W] of specular_color_surfel (same arithmetic)."""
+    rays_cam, _ = sample_camera_rays(H, W, K, R.cpu(), T.cpu())
+    w_o = -rays_cam.to(normal_map.device)
+    NdotV = torch.sum(w_o * normal_map, dim=-1, keepdim=True)
+    rays_refl = 2 * normal_map * NdotV - w_o
+    rays_refl = rays_refl / torch.clamp(torch.linalg.norm(rays_refl, dim=-1, keepdim=True), min=1e-20)
+    return rays_refl.reshape(-1, 3), NdotV.reshape(-1)
+
+
+def shade_taps(mip_res, H, W, K, R, T, normal_map, roughness, min_roughness=0.08, max_roughness=0.5):
+    """Where every pixel of specular_color_surfel fetches (no gradients): the cubemap taps and the quantities at which its per-pixel
+    gradient is discontinuous.  mip_res: resolutions of the levels, finest first.  Returns dict:
+      keys [N,8] int64: level << 24 | texel of the two levels' four taps, -1 where the tap's weight (level share x bilinear) is 0 --
+                        the key layout of the fused backward's hash table (csrc/mrgs_shade.hip, env_scatter_tile);
+      cell_edge [N] float64: distance of the nearest fx / fy (of a level with a share) to an integer, over the level's resolution
+                        (fp32 rounds a texel coordinate in proportion to its size);
+      level_edge [N]:   distance of the un-clamped mip level to an integer (inf where the level is clamped);
+      face_gap [N]:     (|major| - |second|) / |major| of the mirror direction (the face decision);
+      ndv [N], lut_uv [N,2], level [N]."""
+    with torch.no_grad():
+        dirs, ndv = mirror_dirs(H, W, K, R, T, normal_map)
+        rough = roughness.reshape(-1)
+        n = len(mip_res)
+        level = get_mip(rough, n, min_roughness, max_roughness)
+        lc = torch.clamp(level, 0, n - 1)
+        l0 = torch.clamp(torch.floor(lc).long(), max=n - 1)
+        l1 = torch.clamp(l0 + 1, max=n - 1)
+        f = lc - l0.to(lc.dtype)
+        dist = lambda x: (x - torch.round(x)).abs()
+        inf = torch.full_like(f, float("inf"))
+        unclamped = (rough > min_roughness) & (rough < 1.0)
+        level_edge = torch.where(unclamped, dist(lc), inf)
+        edge = inf.clone()
+        keys = torch.full((dirs.shape[0], 8), -1, dtype=torch.int64, device=dirs.device)
+        for li, r_ in enumerate(mip_res):
+            use0, use1 = (l0 == li) & (f < 1), (l1 == li) & (f > 0) & (l1 != l0)
+            use = use0 | use1
+            if not bool(use.any()):
+                continue
+            idx, w, fx, fy, _ = bilinear_taps(r_, dirs)
+            edge = torch.where(use, torch.minimum(edge, torch.minimum(dist(fx), dist(fy)) / r_), edge)
+            for k in range(4):
+                key = (li << 24) | idx[k]
+                keys[:, k] = torch.where(use0 & (w[k] != 0), key, keys[:, k])
+                keys[:, 4 + k] = torch.where(use1 & (w[k] != 0), key, keys[:, 4 + k])
+        a = dirs.abs()
+        top = a.topk(2, dim=1).values
+        face_gap = (top[:, 0] - top[:, 1]) / top[:, 0]
+        fg_uv = torch.stack([ndv, rough], -1).clamp(0, 1)
+    return dict(keys=keys, cell_edge=edge, level_edge=level_edge, face_gap=face_gap, ndv=ndv, lut_uv=fg_uv, level=level)
+
+
+HASH_SIZE, HASH_PROBES, TILE_W, TILE_H, CHECK_EVERY = 4096, 8, 64, 12, 4
+
+
+def _hash_slot(key):
+    return ((key * 2654435761) & 0xFFFFFFFF) >> 20          # (key * 2654435761u) >> (32 - 12)
+
+
+def fused_bwd_schedule(keys, H, W, n_cu, hashed_levels, simulate=(0,)):
+    """Host model of the tile schedule of shade_fused_bwd_kernel (csrc/mrgs_shade.hip): tiles of 64 x 12 pixels, tile t on workgroup
+    t mod min(ntiles, n_cu), the hash table's fill checked after every fourth tile of a workgroup (flushed when more than half of it was
+    taken since the last flush).  keys [H*W, 8] (shade_taps; -1 = no tap); only levels in `hashed_levels` go through the table (the
+    others sit in the dense LDS copy).  For every workgroup the distinct hashed keys of each 4-tile window are counted (a window with
+    more than 4 096 cannot fit the table: some lanes take the global fallback); for the workgroups in `simulate` the table is replayed
+    key by key in pixel order (CAS insert, linear probing, 8 probes) -> inserts, fallbacks and flushes between tiles.
+    Returns dict(ntiles, grid, tiles_per_wg, max_window_keys, windows_over_table, sim: {wg: dict(fallbacks, mid_flushes, inserts)})."""
+    import numpy as np
+    keys = keys.detach().cpu().numpy().reshape(H, W, 8)
+    lev = np.where(keys >= 0, keys >> 24, -1)
+    keys = np.where(np.isin(lev, list(hashed_levels)), keys, -1)
+    tiles_x, tiles_y = (W + TILE_W - 1) // TILE_W, (H + TILE_H - 1) // TILE_H
+    ntiles = tiles_x * tiles_y
+    grid = min(ntiles, n_cu)
+
+    def tile_keys(t):
+        x, y = (t % tiles_x) * TILE_W, (t // tiles_x) * TILE_H
+        k = keys[y:y + TILE_H, x:x + TILE_W].reshape(-1)
+        return k[k >= 0]
+
+    max_win, over = 0, 0
+    for wg in range(grid):
+        ts = list(range(wg, ntiles, grid))
+        for w0 in range(0, len(ts), CHECK_EVERY):
+            d = np.unique(np.concatenate([tile_keys(t) for t in ts[w0:w0 + CHECK_EVERY]])).size
+            max_win = max(max_win, d)
+            over += d > HASH_SIZE
+    sim = {}
+    for wg in simulate:
+        table, taken, flushed_at, fallbacks, mid = {}, 0, 0, 0, 0
+        ts = list(range(wg, ntiles, grid))
+        for i, t in enumerate(ts):
+            for key in tile_keys(t).tolist():
+                h = _hash_slot(key)
+                for _ in range(HASH_PROBES):
+                    old = table.get(h)
+                    if old is None:
+                        table[h] = key
+                        taken += 1
+                        break
+                    if old == key:
+                        break
+                    h = (h + 1) & (HASH_SIZE - 1)
+                else:
+                    fallbacks += 1
+            if (i + 1) % CHECK_EVERY == 0 and taken - flushed_at > HASH_SIZE // 2:
+                table, flushed_at = {}, taken
+                mid += i + 1 < len(ts)          # tiles follow: the flushed slots are taken again in this launch
+        sim[wg] = dict(fallbacks=fallbacks, mid_flushes=mid, inserts=taken)
+    return dict(ntiles=ntiles, grid=grid, tiles_per_wg=(ntiles + grid - 1) // grid, max_window_keys=max_win, windows_over_table=over, sim=sim)

@@ -91,3 +91,53 @@ def brute_force_hits(ray_o, ray_d, means, scales, rotations, opacities, scale_mo
         alpha = torch.clamp(opacities[:, 0][None] * torch.exp(-0.5 * (u * u + v * v)), max=0.99)
         valid = (t > 0) & (u.abs() <= 3.0) & (v.abs() <= 3.0) & (alpha >= 1.0 / 255.0) & torch.isfinite(t)
         return torch.where(valid, t, torch.full_like(t, float("inf")))
+
+
+LEAVES = ("means", "scales", "rotations", "opacities", "colors", "others")
+OUTPUTS = ("rgb", "dpt", "acc", "norm", "dist", "aux")
+
+
+def trace_dense_restricted(ray_o, ray_d, means, scales, rotations, opacities, colors, others, bg, up=None, chunk=256, scale_modifier=1.0):
+    """trace_dense for many rays at large P, `chunk` rays at a time, each chunk against the CANDIDATES of its rays only: the surfels with an
+    accepted hit (brute_force_hits finite) for any ray of the chunk, in increasing index order (the sort's tie order is the same).  A surfel
+    that no ray of the chunk hits enters the chunk's statement only through masked terms, so the restriction changes nothing but the cost.
+    up: None (forward only) or dict output name -> upstream gradient shaped like the output ([R,3] / [R] / [R,2]); the per-surfel
+    gradients of sum(out * up) are index_add-ed back into P-sized tensors.  Runs on the device of its arguments, in their dtype.
+    Returns (out: dict of the OUTPUTS and T, hits over all R rays, detached; grads: dict LEAVES + "o", "d" or None; cand: [P] bool, the union
+    of the candidates of the rays whose upstream is not all zero -- of every ray without `up`)."""
+    P, R = means.shape[0], ray_o.shape[0]
+    dev, dt = means.device, means.dtype
+    surf = [t.detach() for t in (means, scales, rotations, opacities, colors, others)]
+    outs = []
+    cand = torch.zeros(P, dtype=torch.bool, device=dev)
+    grads = None
+    if up is not None:
+        grads = {k: torch.zeros_like(t) for k, t in zip(LEAVES, surf)}
+        grads["o"], grads["d"] = torch.zeros_like(ray_o.detach()), torch.zeros_like(ray_d.detach())
+    for s in range(0, R, chunk):
+        o, d = ray_o[s:s + chunk].detach(), ray_d[s:s + chunk].detach()
+        hit = torch.isfinite(brute_force_hits(o, d, *surf[:4], scale_modifier=scale_modifier))       # [c,P]
+        idx = torch.nonzero(hit.any(dim=0)).reshape(-1)                                              # sorted
+        live = None
+        if up is not None:
+            live = torch.zeros(o.shape[0], dtype=torch.bool, device=dev)
+            for k in OUTPUTS:
+                if k in up:
+                    live |= (up[k][s:s + chunk].reshape(o.shape[0], -1) != 0).any(dim=1)
+        cand |= (hit[live] if live is not None else hit).any(dim=0)
+        sub = [t[idx].clone().requires_grad_(up is not None) for t in surf]
+        oc, dc = o.clone().requires_grad_(up is not None), d.clone().requires_grad_(up is not None)
+        with torch.set_grad_enabled(up is not None):
+            r = trace_dense(oc, dc, *sub, bg.to(dev, dt), scale_modifier=scale_modifier)
+            if up is not None:
+                loss = sum((r[k] * up[k][s:s + chunk].to(dev, dt)).sum() for k in OUTPUTS if k in up)
+                gs = torch.autograd.grad(loss, sub + [oc, dc], allow_unused=True)
+                for k, g in zip(LEAVES, gs[:6]):
+                    if g is not None:
+                        grads[k].index_add_(0, idx, g)
+                for k, g in zip(("o", "d"), gs[6:]):
+                    if g is not None:
+                        grads[k][s:s + chunk] = g
+        outs.append({k: r[k].detach() for k in OUTPUTS + ("T", "hits")})
+    out = {k: torch.cat([x[k] for x in outs]) for k in outs[0]} if outs else {}
+    return out, grads, cand

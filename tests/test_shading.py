@@ -151,6 +151,41 @@ def test_envmap_lookup_parity(gpu_device):
             assert np.abs(r_h.grad.cpu().numpy() - r_o.grad.numpy()).max() <= 1e-4 * float(r_o.grad.abs().max())
 
 
+def test_fused_backward_schedule_model():
+    """CPU: the host model of shade_fused_bwd_kernel's tile schedule (oracle/shading_oracle.fused_bwd_schedule) on hand-made keys, and the
+    keys shade_taps gives for a real frame against the taps of the oracle's own fetch."""
+    H, W = 48, 128                        # 2 x 4 tiles of 64 x 12 on one workgroup: the check after tile 4 flushes, tiles 5-8 follow
+    keys = torch.arange(H * W * 8, dtype=torch.int64).reshape(H * W, 8)        # all distinct, level 0
+    keys[:, 2:] = -1                                                           # two taps a pixel: 1 536 keys a tile, 6 144 a window
+    s = so.fused_bwd_schedule(keys, H, W, n_cu=1, hashed_levels=[0])
+    assert (s["ntiles"], s["grid"], s["tiles_per_wg"]) == (8, 1, 8)
+    assert s["max_window_keys"] == 4 * 64 * 12 * 2 and s["windows_over_table"] == 2
+    sim = s["sim"][0]
+    assert sim["fallbacks"] > 0 and sim["fallbacks"] == H * W * 2 - sim["inserts"] and sim["mid_flushes"] == 1
+    s = so.fused_bwd_schedule(keys, H, W, n_cu=256, hashed_levels=[0])          # a workgroup per tile: every window fits the table
+    assert s["grid"] == 8 and s["windows_over_table"] == 0 and s["sim"][0] == dict(fallbacks=0, mid_flushes=0, inserts=64 * 12 * 2)
+    s = so.fused_bwd_schedule(keys, H, W, n_cu=1, hashed_levels=[1])            # level 0 sits in the dense LDS copy: nothing hashed
+    assert s["max_window_keys"] == 0 and s["sim"][0]["inserts"] == 0
+    # the keys shade_taps gives for a real frame are the oracle fetch's taps of non-zero weight, and those taps reproduce env_lookup
+    cam, albedo, normal, alpha, refl, rough = _frame(24, 40, 6)
+    Hf, Wf, K = cam.HWK
+    mips = make_mips(2, 32, 4)
+    t = so.shade_taps([m.shape[1] for m in mips], Hf, Wf, K, cam.R, cam.T, normal.double(), rough.double())
+    dirs, _ = so.mirror_dirs(Hf, Wf, K, cam.R, cam.T, normal.double())
+    lev = so.get_mip(rough.reshape(-1).double(), len(mips)).clamp(0, len(mips) - 1)
+    vals = torch.zeros(Hf * Wf, 3, dtype=torch.float64)
+    want = torch.full((Hf * Wf, 4 * len(mips)), -1, dtype=torch.int64)
+    for li, m in enumerate(mips):
+        idx, w, _, _, _ = so.bilinear_taps(m.shape[1], dirs)
+        share = torch.clamp(1 - (lev - li).abs(), min=0)
+        for k in range(4):
+            vals += (share * w[k])[:, None] * m.reshape(-1, 3).double()[idx[k]]
+            want[:, 4 * li + k] = torch.where((share * w[k]) != 0, (li << 24) | idx[k], want[:, 4 * li + k])
+    assert torch.equal(want.sort(dim=1, descending=True).values[:, :8], t["keys"].sort(dim=1, descending=True).values)
+    assert float((torch.sigmoid(vals) - so.env_lookup([m.double() for m in mips], dirs, rough.reshape(-1).double())).abs().max()) < 1e-12
+    assert float(t["cell_edge"].min()) >= 0.0 and float(t["level_edge"].min()) >= 0.0 and bool((t["face_gap"] >= 0).all())
+
+
 @pytest.mark.gpu
 def test_shade_specular_parity(gpu_device):
     from materialrefgs_amd.shading import EnvLight, get_specular_color_surfel, load_fg_lut

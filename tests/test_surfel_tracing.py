@@ -121,6 +121,40 @@ def test_host_mirror_shapes_without_a_gpu():
         SurfelTracer().build_acceleration_structure(torch.zeros(8, 3), None)          # no CPU path
 
 
+def test_restricted_dense_oracle_equals_the_unrestricted_one():
+    """trace_dense_restricted (the float64 checker of tests/test_full_size_gradients.py) against trace_dense over ALL surfels with autograd:
+    outputs and every gradient equal to 1e-12, surfels no ray with upstream can hit get exact zeros, everything finite."""
+    P, n = 3000, 256
+    sc, colors, others = _scene(P, 7 + P, 30.0)
+    o, d = _rays(n, 7 + P, inside=False)
+    f = lambda t: t.double()
+    surf = [f(sc.means3D), f(sc.scales), f(sc.rotations), f(sc.opacities), f(colors), f(others)]
+    bg = torch.tensor([0.3, 0.2, 0.6], dtype=torch.float64)
+    g = torch.Generator().manual_seed(2)
+    up = {k: torch.randn(n, c, generator=g, dtype=torch.float64).squeeze(-1) for k, c in (("rgb", 3), ("dpt", 1), ("acc", 1), ("norm", 3),
+                                                                                          ("dist", 1), ("aux", 2))}
+    for k in up:
+        up[k][200:] = 0.0                                  # rays without upstream: their candidates must not enter the union
+    out, grads, cand = sto.trace_dense_restricted(f(o), f(d), *surf, bg, up=up, chunk=96)
+    leaves = [t.clone().requires_grad_(True) for t in surf + [f(o), f(d)]]
+    ref = sto.trace_dense(*leaves[6:], *leaves[:6], bg)
+    sum((ref[k] * up[k]).sum() for k in up).backward()
+    for k in ("rgb", "dpt", "acc", "norm", "dist", "aux", "T", "hits"):
+        assert torch.equal(out[k], ref[k].detach()) or float((out[k] - ref[k].detach()).abs().max()) <= 1e-12, k
+    names = list(sto.LEAVES) + ["o", "d"]
+    for k, leaf in zip(names, leaves):
+        a, b = grads[k], leaf.grad
+        assert bool(torch.isfinite(a).all()) and bool(torch.isfinite(b).all()), k
+        assert float((a - b).abs().max()) <= 1e-12 * float(b.abs().max()), k
+        if k not in ("o", "d"):
+            assert float(a[~cand].abs().max()) == 0.0, k
+    assert float(grads["o"][200:].abs().max()) == 0.0 and float(grads["d"][200:].abs().max()) == 0.0
+    hit = torch.isfinite(sto.brute_force_hits(f(o)[:200], f(d)[:200], *surf[:4])).any(dim=0)
+    assert torch.equal(cand, hit) and 0 < int(cand.sum()) < P
+    out_f, none, cand_f = sto.trace_dense_restricted(f(o), f(d), *surf, bg, chunk=1000)          # forward only, one chunk
+    assert none is None and torch.equal(out_f["hits"], out["hits"]) and int(cand_f.sum()) >= int(cand.sum())
+
+
 # ---- GPU ----------------------------------------------------------------------------------------------------------------------
 
 def _scene(P, seed, radius_px=40.0):
