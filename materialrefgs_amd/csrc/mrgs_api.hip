@@ -681,13 +681,10 @@ static int side_of(SideStream** out)
     SideStream& s = g_side[dev];
     if (s.stream == nullptr) {
         // LOWEST priority: the side work is filler -- the dispatcher hands a free wave slot to the caller's stream first, and what runs
-        // on the side stream takes what is left (the lone-wave tails of the blend kernels); MRGS_SIDE_PRIORITY=default: same priority
+        // on the side stream takes what is left (the lone-wave tails of the blend kernels)
         int least = 0, greatest = 0;
         HIP_TRY(hipDeviceGetStreamPriorityRange(&least, &greatest));
-        const char* pr = getenv("MRGS_SIDE_PRIORITY");
-        const bool dflt = pr != nullptr && pr[0] == 'd';
-        if (dflt) HIP_TRY(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
-        else HIP_TRY(hipStreamCreateWithPriority(&s.stream, hipStreamNonBlocking, least));
+        HIP_TRY(hipStreamCreateWithPriority(&s.stream, hipStreamNonBlocking, least));
         for (int i = 0; i < MRGS_SIDE_EVENTS; i++) HIP_TRY(hipEventCreateWithFlags(&s.ev[i], hipEventDisableTiming));
         HIP_TRY(hipEventCreateWithFlags(&s.pre_blend, hipEventDisableTiming));
     }

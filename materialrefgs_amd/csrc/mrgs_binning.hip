@@ -400,7 +400,7 @@ __global__ void __launch_bounds__(BS_THREADS) __attribute__((amdgpu_waves_per_eu
             reuse_bwd[MRGS_QS_TICKET + w] = 0u;
         }
         if (t == 0 && threadIdx.x < 16) reuse_bwd[threadIdx.x] = reuse_state[MRGS_QS_FWD + threadIdx.x];     // COUNT[8] | PASSES[8]
-        if (t == 0 && threadIdx.x == 16) redo_count[0] = 0u;         // (the list of marked pixels of the MRGS_FWD_REDO_INLINE=0 build)
+        if (t == 0 && threadIdx.x == 16) redo_count[0] = 0u;         // (the forward blend's count of marked pixels)
         if (threadIdx.x < 4) item_work[t * 4 + threadIdx.x] = 0u;
         const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
         const size_t per = (bulk_zero_f4 + T_ - 1) / T_, z0 = per * t, z1 = z0 + per < bulk_zero_f4 ? z0 + per : bulk_zero_f4;

@@ -129,7 +129,7 @@ struct Hit {
 //   * the forward, whose transmittance T is a PRODUCT of (1 - alpha) and therefore carries the accumulated difference of every
 //     earlier pair, marks the PIXEL instead, carries on, and renders marked pixels again at the end of the wave with exact arithmetic
 //     from the first list entry on (mrgs_render_fwd.hip: redo_pixel), which is the oracle's computation of that pixel.  A pixel is
-//     marked for an ambiguous pair it blends and for a transmittance within MRGS_T1_EPS / MRGS_T2_EPS of the 1e-4 / 0.5 tests.
+//     marked for an ambiguous pair it blends and for a transmittance within the band of the 1e-4 test (below) or MRGS_T2_EPS of 0.5.
 // Every decision of an unmarked pixel is then the one exact arithmetic takes; the values stay fast.
 // Bands.  v_rcp_f32 is within 1 ulp, s = p.xy * (1/p.z) then within 1.5 ulp (1.8e-7) of the exact product, rho3d within 4.2e-7
 // relative, the exponent -rho/2 within 2.1e-7 rho <= 2.4e-6 for rho <= 2 ln 255 (beyond that alpha < 1/255 whatever the opacity);
@@ -144,8 +144,8 @@ struct Hit {
 // transmittance: the fast product of (1 - alpha) against the exact one.  T > 0.5: every earlier alpha is below 0.5, the relative
 // difference is at most sum alpha_i / (1 - alpha_i) x 2.7e-6 <= 2 ln 2 x 2.7e-6 = 3.7e-6 (measured over 1.4 M pixels: 5.5e-7) -> 4e-6.
 // T (1 - alpha) < 1e-4: no constant bounds the difference at the END of a list -- a pair with alpha = 0.99 alone moves the relative
-// difference by alpha / (1 - alpha) x 2.5e-7 = 2.5e-5 -- so the forward carries the bound per pixel (MRGS_T1_RUNNING, round 6; rounds
-// 4-5 used MRGS_T1_EPS = 1.5e-5 relative, three times the largest difference MEASURED over 1.4 M pixels: a measurement, not a bound).
+// difference by alpha / (1 - alpha) x 2.5e-7 = 2.5e-5 -- so the forward carries the bound per pixel (a constant band of 1.5e-5 relative,
+// three times the largest difference MEASURED over 1.4 M pixels, was a measurement, not a bound).
 // With F_n >= |T~_n - T_n| (T~: the fast product; T: the oracle's fp32 product of its exactly evaluated factors):
 //     T~_n = fl(T~_{n-1} fl(1 - a~_n)),  T_n = fl(T_{n-1} fl(1 - a_n)),  |a~_n - a_n| <= d_n a_n,  d_n = 2.1e-7 rho_n + 2.5e-7 (above)
 //     |T~_n - T_n| <= |T~_{n-1} - T_{n-1}| (1 - a_n) + T_{n-1} d_n a_n + 4 x 2^-24 T_n          (two roundings on either side)
@@ -158,16 +158,10 @@ struct Hit {
 // within MRGS_T1_SLACK F_n + 1e-11 of 1e-4 marks the pixel.  No division: a multiplication, a multiply-add, a select and a subtraction
 // per blended entry.  Typical pixel (six pairs of alpha ~ 0.8): F / T = 1.2e-5; a pair of alpha 0.99: + 4e-5.  Measured at C3full /
 // C2 (MI355X, 100 views each, twice): 110-124 marked pixels a view against 67-84 with the constant band, forward blend 182-185 us
-// against 178-179 (C2: 156 against 151); carrying rho per pair (MRGS_T1_RUNNING=2: d_n exactly) marks 89-107 and costs the same.
-#ifndef MRGS_T1_RUNNING
-#define MRGS_T1_RUNNING 1
-#endif
+// against 178-179 (C2: 156 against 151); carrying rho per pair (d_n exactly) marks 89-107 and costs the same.
 #define MRGS_T_STEP_ERR 4.1e-7f
 #define MRGS_T1_SLACK 1.25f
 #define MRGS_T1_ABS 1e-11f
-#ifndef MRGS_T1_EPS
-#define MRGS_T1_EPS (MRGS_T_MIN * 1.5e-5f)      // (the constant band of rounds 4-5: MRGS_T1_RUNNING=0 builds)
-#endif
 #ifndef MRGS_T2_EPS
 #define MRGS_T2_EPS (0.5f * 4e-6f)
 #endif

@@ -23,11 +23,8 @@
 
 #include "mrgs_blend_math.h"
 
-// MRGS_FWD_REFINE: the cull against the live pixels' bounding box, for chunks that start with at most MRGS_FWD_REFINE_LIVE live pixels
+// MRGS_FWD_REFINE_LIVE: the cull against the live pixels' bounding box runs for chunks that start with at most this many live pixels
 // (8 ... 40 measure the same, 64 = every chunk is 11 % slower than never).
-#ifndef MRGS_FWD_REFINE
-#define MRGS_FWD_REFINE 1
-#endif
 #ifndef MRGS_FWD_REFINE_LIVE
 #define MRGS_FWD_REFINE_LIVE 24
 #endif
@@ -54,8 +51,9 @@ extern "C" int mrgs_wave_stats_min_total(int n) { return (int)hipMemcpyToSymbol(
 // rounding sequence decides anything -- is multiplied up serially in list order, one rounding per blended entry exactly as
 // forward.cu:400-441 does; the sums (which decide nothing) are formed per lane and folded across the wave at the end.  Lane 0
 // overwrites the pixel's outputs; entries the pixel blends are flagged for the backward like those of the main kernel.
-// Called from the tail of the forward kernel (MRGS_FWD_REDO_INLINE, the default: the forward's occupancy is pinned, so what this code
-// needs beyond the main loop's registers is spilled around it, in code that runs for one wave in a hundred) or from a launch of its own.
+// Called from the tail of the forward kernel: the forward's occupancy is pinned, so what this code needs beyond the main loop's registers
+// is spilled around it, in code that runs for one wave in a hundred.  (A launch of its own was measured: its duration -- the longest
+// marked list, walked by a wave alone on its SIMD -- was fully exposed on the stream, 26 us at C2.)
 // inclusive prefix sum over the 64 lanes in DPP adds: Hillis-Steele inside the 16-lane rows (a lane whose source falls outside its row adds
 // 0), then lane 15 / lane 31 of the rows before into the rows behind.  Every lane of the wave must be active.
 __device__ __forceinline__ float wave_inclusive_sum(float v)
@@ -248,30 +246,6 @@ __device__ __forceinline__ void mrgs_redo_pixel(
     }
 }
 
-// The marked pixels of a launch, one per wave (see mrgs_redo_pixel).  The forward kernel renders its own marked pixels at the end of its
-// wave by default (MRGS_FWD_REDO_INLINE): measured, the separate launch's duration -- the longest marked list, walked by a wave that is
-// alone on its SIMD -- is fully exposed on the stream (26 us at C2), while inside the forward the same work extends a handful of waves
-// of which few are among the last to finish.
-template <int S_MAX>
-__global__ void __launch_bounds__(64) render_fwd_redo_kernel(
-    const uint2* __restrict__ ranges, const uint32_t* __restrict__ point_list, const uint8_t* __restrict__ qmask, uint8_t* cflag, int S, int W, int H,
-    int tiles_x, const float4* __restrict__ rec, const float* __restrict__ features, const float* __restrict__ bg, float* __restrict__ final_T,
-    uint32_t* __restrict__ n_contrib, float* __restrict__ out_color, float* __restrict__ out_feature, float* __restrict__ out_others,
-    const uint32_t* __restrict__ redo_list)
-{
-    __shared__ uint32_t q_id[MRGS_REDO_QCAP], q_pos[MRGS_REDO_QCAP];
-    const int lane = threadIdx.x;
-    const uint32_t count = redo_list[0];
-    for (uint32_t it = blockIdx.x; it < count; it += gridDim.x) {
-        mrgs_redo_pixel<S_MAX>((int)redo_list[2 + it], lane, q_id, q_pos, ranges, point_list, qmask, cflag, S, W, H, tiles_x, rec, features, bg, final_T,
-                               n_contrib, out_color, out_feature, out_others);
-        __builtin_amdgcn_wave_barrier();        // the next pixel's queue starts empty: nothing of this one is read again
-    }
-}
-
-#ifndef MRGS_FWD_REDO_INLINE
-#define MRGS_FWD_REDO_INLINE 1
-#endif
 // S_LIVE: the leading channels that can be non-zero (MrgsRasterInputs::features_live); the rest of the S_MAX are padding of the row
 template <int S_MAX, bool FV, int S_LIVE>
 // Waves per SIMD the register allocator is held to.  Round 4 (after the exact-decision logic joined the loop), forward blend stage in ms at
@@ -339,9 +313,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(S_MAX =
     int cf_end = 0;                  // list entries whose cflag this wave has written
     uint32_t work = 0;
     float T = 1.0f;
-#if MRGS_T1_RUNNING
     float Terr = 0.0f;               // MRGS_T1_SLACK x the bound of |T - the transmittance exact arithmetic has at this point| (mrgs_blend_math.h)
-#endif
     float C0 = 0.f, C1 = 0.f, C2 = 0.f, N0 = 0.f, N1 = 0.f, N2 = 0.f;
     // (the record channel's accumulator is a variable of its own, not F[S_MAX]: as a ninth array element it shifted the pairs the compiler
     //  forms for v_pk_fma_f32 by one -- (x, F0), (F1, F2) ... (F7, F8) -- and every blended entry paid eight register moves to line the
@@ -360,7 +332,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(S_MAX =
     const uint8_t* qm = qmask + range.x;
     uint8_t* cf = cflag + (size_t)range.x * 4 + quad;       // this quadrant's "blended by some pixel" flag of every list entry
     uint32_t id1 = 0, id2 = 0, q1 = 0, q2 = 0;
-    uint32_t idc = 0, idn = 0;       // ids of the chunk being blended / of the one staged behind it (MRGS_FWD_REFINE)
+    uint32_t idc = 0, idn = 0;       // ids of the chunk being blended / of the one staged behind it
 
     uint64_t mask_cur;
     {
@@ -391,7 +363,6 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(S_MAX =
         if (MRGS_FWD_STAGES == 2) stage_next();
 
         uint64_t m = mask_cur;
-#if MRGS_FWD_REFINE
         // Few pixels of the block still alive (a silhouette block late in its list): the cull that tile_ranges_kernel evaluated
         // against the whole 8x8 block is evaluated again against the bounding rectangle of the LIVE pixels, all 64 entries of
         // the chunk at once (lane = entry).  An entry it removes reaches alpha >= 1/255 at no live pixel, i.e. every lane would
@@ -409,7 +380,6 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(S_MAX =
                 m &= __builtin_amdgcn_ballot_w64(touch);
             }
         }
-#endif
         work += (uint32_t)__builtin_popcountll(m);
         const StageBuf<SF>& sb = stage[c % MRGS_FWD_STAGES];
         uint64_t contributed = 0ull;          // bit j: some live pixel of the block is hit by entry base + j
@@ -449,17 +419,9 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(S_MAX =
             // (mrgs_blend_math.h "Exact decisions"; mrgs_redo_pixel).  Three quarters of the marks are transmittance bands.
             // (the two transmittance tests as two comparisons each, against the near and the far edge of the band: between them the
             // pixel is marked, and what the fast path does with a marked pixel does not matter)
-#if MRGS_T1_RUNNING
-            // the band of the 1e-4 test: a running BOUND of |T_fast - T_exact| carried per pixel (mrgs_blend_math.h: MRGS_T1_RUNNING)
-#if MRGS_T1_RUNNING == 2     // (the recurrence with d_n = 2.1e-7 rho_n + 2.5e-7 carried per pair: a tighter band for three more instructions)
-            const float Terr_new = fmaf(Terr, oma, MRGS_T1_SLACK * fmaf(fmaf(2.1e-7f, fminf(h.rho3d, h.rho2d), 2.5e-7f) * h.alpha, T, 2.4e-7f * test_T));
-#else
+            // the band of the 1e-4 test: a running BOUND of |T_fast - T_exact| carried per pixel (mrgs_blend_math.h)
             const float Terr_new = fmaf(Terr, oma, (MRGS_T1_SLACK * MRGS_T_STEP_ERR) * T);
-#endif
             const uint64_t below = MRGS_BALLOT(test_T < (MRGS_T_MIN - MRGS_T1_ABS) - Terr_new);
-#else
-            const uint64_t below = MRGS_BALLOT(test_T < MRGS_T_MIN - MRGS_T1_EPS);
-#endif
             // (a T (1 - alpha) inside the band of the 1e-4 test is not looked for here: it does not end the pixel -- `below` is the near
             // edge of the band --, becomes the pixel's T, and nothing but a terminating entry can follow it: the pixel's FINAL T lies in
             // the band exactly when some entry's did, and is tested once, after the list)
@@ -498,9 +460,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(S_MAX =
                 if constexpr (XREC) Fx = fmaf(a1.w, w, Fx);       // (the record's tail arrives one entry ahead with the rest of it)
             }
             T = upd ? test_T : T;
-#if MRGS_T1_RUNNING
             Terr = upd ? Terr_new : Terr;
-#endif
             last_contributor = upd ? contributor : last_contributor;
         };
 
@@ -580,21 +540,16 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(S_MAX =
         out_others[pix + 6 * HW] = distortion;
     }
 
-    // ---- marked pixels (mrgs_blend_math.h "Exact decisions"): listed for render_fwd_redo_kernel, which renders them again with the
-    // oracle's arithmetic and overwrites what was written above.  ~1e-4 of the pixels.  The backward walks flagged list entries only
+    // ---- marked pixels (mrgs_blend_math.h "Exact decisions"): rendered again with the oracle's arithmetic (mrgs_redo_pixel), which
+    // overwrites what was written above.  ~1e-4 of the pixels.  The backward walks flagged list entries only
     // and the redo may blend entries this wave never reached: the flags it did not write are cleared here, the redo then only sets.
 #ifdef MRGS_FWD_REDO_ALL   // developer build: every pixel goes through the exact path (what the margins are measured against)
     redo = ~0ull;
 #endif
-#if MRGS_T1_RUNNING
     redo |= MRGS_BALLOT(T < (MRGS_T_MIN + MRGS_T1_ABS) + Terr);
-#else
-    redo |= MRGS_BALLOT(T < MRGS_T_MIN + MRGS_T1_EPS);
-#endif
     redo &= __builtin_amdgcn_ballot_w64(inside);
     if (redo != 0ull) {
         for (int e = cf_end + lane; e < total; e += MRGS_CHUNK) cf[(size_t)e * 4] = 0;
-#if MRGS_FWD_REDO_INLINE
         if (lane == 0) atomicAdd(&redo_list[0], (uint32_t)__builtin_popcountll(redo));      // (diagnostics: mrgs_debug_export 12 reports the count)
         // (the list staging buffer is free by now: the candidate queue of the redo lives there)
         uint32_t* q = reinterpret_cast<uint32_t*>(&stage[0]);
@@ -608,18 +563,10 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(S_MAX =
                                    bg, final_T, n_contrib, out_color, out_feature, out_others);
             __builtin_amdgcn_wave_barrier();
         }
-#else
-        if ((redo >> lane) & 1ull) redo_list[2 + atomicAdd(&redo_list[0], 1u)] = (uint32_t)pix;
-#endif
     }
 }
 
 #define MRGS_FWD_KERNEL render_fwd_kernel
-#ifdef MRGS_FWD_REDO_ALL
-#define MRGS_REDO_BLOCKS 8192
-#else
-#define MRGS_REDO_BLOCKS 512
-#endif
 
 void mrgs_launch_render_fwd(const MrgsRasterConfig& cfg, const MrgsRasterInputs& in, const MrgsGeomWs& g, const uint32_t* plist,
                             const uint8_t* qmask, uint8_t* cflag, const MrgsImgWs& img, float* out_color, float* out_feature, float* out_others, hipStream_t stream)
@@ -643,14 +590,4 @@ void mrgs_launch_render_fwd(const MrgsRasterConfig& cfg, const MrgsRasterInputs&
     else if (cfg.S == 24 && fv_ok) LAUNCH(24, true, 24);
     else LAUNCH(24, false, 24);
 #undef LAUNCH
-#if !MRGS_FWD_REDO_INLINE
-    // the marked pixels again, exactly (an empty list most of the time: the launch is there for the count it reads on the device)
-#define REDO(SM) hipLaunchKernelGGL((render_fwd_redo_kernel<SM>), dim3(MRGS_REDO_BLOCKS), block, 0, stream, img.ranges, plist, qmask, cflag, cfg.S, cfg.W, cfg.H, tiles_x, \
-                                    g.rec, in.features, in.bg, img.final_T, img.n_contrib, out_color, out_feature, out_others, img.redo_list)
-    if (cfg.S == 0) REDO(0);
-    else if (cfg.S <= 8) REDO(8);
-    else if (cfg.S <= 12) REDO(12);
-    else REDO(24);
-#undef REDO
-#endif
 }

@@ -358,11 +358,7 @@ __device__ __forceinline__ void acc_add(const EnvMips& m, const ShadeAcc& A, int
 {
     if (loff >= 0) {
         float* a = A.dense + loff + idx * 3;
-#ifdef MRGS_X_INT_ATOMICS   // developer timing build (results are wrong): what the accumulation would cost with integer LDS atomics
-        atomicAdd((int*)a, (int)(v[0] * 65536.f)); atomicAdd((int*)a + 1, (int)(v[1] * 65536.f)); atomicAdd((int*)a + 2, (int)(v[2] * 65536.f));
-#else
         atomicAdd(a, v[0]); atomicAdd(a + 1, v[1]); atomicAdd(a + 2, v[2]);
-#endif
         return;
     }
     const unsigned key = ((unsigned)lk << 24) | (unsigned)idx;
@@ -376,11 +372,7 @@ __device__ __forceinline__ void acc_add(const EnvMips& m, const ShadeAcc& A, int
     }
     if (slot >= 0) {
         float* a = A.vals + slot * 3;
-#ifdef MRGS_X_INT_ATOMICS
-        atomicAdd((int*)a, (int)(v[0] * 65536.f)); atomicAdd((int*)a + 1, (int)(v[1] * 65536.f)); atomicAdd((int*)a + 2, (int)(v[2] * 65536.f));
-#else
         atomicAdd(a, v[0]); atomicAdd(a + 1, v[1]); atomicAdd(a + 2, v[2]);
-#endif
     } else {
         float* g = m.grad[lk] + (size_t)(blockIdx.x % (unsigned)m.copies[lk]) * (size_t)(6 * m.res[lk] * m.res[lk] * 3) + (size_t)idx * 3;
         atomicAdd(g, v[0]); atomicAdd(g + 1, v[1]); atomicAdd(g + 2, v[2]);
@@ -408,16 +400,8 @@ __device__ __forceinline__ void env_scatter_tile(const EnvMips& m, unsigned grad
             const bool live = lev && tp[k].w[q] != 0.f;
             const unsigned key = live ? (((unsigned)lk << 24) | (unsigned)tp[k].idx[q]) : MRGS_SHADE_KEY_NONE;
             if (!live) { v[0] = 0.f; v[1] = 0.f; v[2] = 0.f; }
-#ifdef MRGS_X_NO_MERGE
-            const bool last = true;
-#else
             const bool last = run_merge(key, v);
-#endif
-#ifdef MRGS_X_NO_ACC       // developer timing build: everything but the accumulation (results are wrong)
-            if (last && key == 0x12345678u && v[0] == 1e30f) acc_add(m, A, lk, loff, tp[k].idx[q], v);
-#else
             if (last && key != MRGS_SHADE_KEY_NONE) acc_add(m, A, lk, loff, tp[k].idx[q], v);
-#endif
         }
     }
 }
@@ -918,7 +902,6 @@ __device__ __forceinline__ void csr_spmv3_body(int block, int nrows, const uint3
     const uint32_t a = row_ptr[r], b = gid < nrows ? row_ptr[r + 1] : a;
     float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f;
     uint32_t k = a + sub;
-#ifndef MRGS_SPMV_NO_UNROLL
     // The matrix streams from HBM (it does not survive in the last-level cache between two iterations of a training step) and a wave
     // has only 2 x 128 bytes of it in flight per round: with every wave slot of the chip taken that is 2 MB against the ~8 MB that
     // 8 TB/s x 1 us of latency want.  MRGS_SPMV_ROUNDS rounds of (index, weight) loads are issued before the first gather.
@@ -935,7 +918,6 @@ __device__ __forceinline__ void csr_spmv3_body(int block, int nrows, const uint3
 #pragma unroll
         for (int u = 0; u < MRGS_SPMV_ROUNDS; ++u) { s0 += w[u] * v[u][0]; s1 += w[u] * v[u][1]; s2 += w[u] * v[u][2]; }
     }
-#endif
     for (; k < b; k += G) {
         const float w = (float)val[k];
         const float* xv = x + 3 * (size_t)col[k];

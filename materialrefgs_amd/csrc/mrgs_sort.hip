@@ -221,22 +221,6 @@ __global__ void __launch_bounds__(SORT_THREADS) radix_onesweep_kernel(const uint
     }
     uint32_t all;
     const uint32_t digit_base = block_exclusive_scan<SORT_THREADS>(totals[tid], scan_tmp, all);
-#ifdef MRGS_SORT_DIRECT_SCATTER
-    start[tid] = digit_base + excl;
-    if (__syncthreads_or(!ok)) {
-        if (tid == 0) atomicExch(error_flag, 1u);
-        return;
-    }
-#pragma unroll
-    for (int it = 0; it < ITEMS; it++) {
-        if (wbase + it * 64 < n) {
-            const uint32_t d = (key[it] >> shift) & 255u;
-            const uint32_t pos = start[d] + whist[wave][d] + off[it];
-            kout[pos] = key[it];
-            vout[pos] = val[it];
-        }
-    }
-#else
     // The tile is put in digit order in LDS first and leaves in runs: consecutive threads then store to consecutive addresses
     // of a run (a wave's 64 stores touch a handful of cache lines), where storing straight from the ranking registers sends the
     // 64 keys of a wave instruction to up to 64 different runs.
@@ -270,16 +254,11 @@ __global__ void __launch_bounds__(SORT_THREADS) radix_onesweep_kernel(const uint
             vout[pos] = s_val[e];
         }
     }
-#endif
 }
 
 // tile size of the passes for n keys: enough workgroups to fill 256 CUs for small inputs, longer tiles (shorter look-back
 // chains, fewer status words) for large ones
-#ifdef MRGS_SORT_ITEMS_FORCE
-static int sort_items(int64_t) { return MRGS_SORT_ITEMS_FORCE; }
-#else
 static int sort_items(int64_t n) { return n <= (128 << 10) ? 4 : n <= (768 << 10) ? 8 : 16; }   // look-back chains of <= ~300 tiles
-#endif
 
 size_t mrgs_sort_ws_words(int64_t n)
 {
@@ -494,13 +473,9 @@ __global__ void __launch_bounds__(256) tile_ranges_kernel(const uint32_t* __rest
         const CullConic c = mrgs_cull_load(cull, plist[idx]);
         const int tx = (int)(cur % (uint32_t)tiles_x), ty = (int)(cur / (uint32_t)tiles_x);
         const float x0 = (float)(tx * MRGS_BLOCK_X), y0 = (float)(ty * MRGS_BLOCK_Y);
-#ifdef TR_NO_CULL
-        m = (c.a.x + x0 + y0 > 1e20f) ? 3u : 15u;
-#else
 #pragma unroll
         for (int q = 0; q < 4; q++)
             m |= mrgs_block_may_touch(c, x0 + (float)(8 * (q & 1)), y0 + (float)(8 * (q >> 1)), 7.0f, 7.0f) ? (1u << q) : 0u;
-#endif
         qmask[idx] = (uint8_t)m;
     }
     // per-quadrant counts: summed per wave with ballots, per workgroup in LDS (the 256 sorted entries of a workgroup span one or
@@ -511,11 +486,7 @@ __global__ void __launch_bounds__(256) tile_ranges_kernel(const uint32_t* __rest
     if (threadIdx.x == 0) s_first = cur;          // entry 0 of the workgroup is valid whenever any entry is
     __syncthreads();
     const uint32_t first_tile = s_first;
-#ifdef TR_NO_ATOMICS
-    uint64_t todo = 0;
-#else
     uint64_t todo = __builtin_amdgcn_ballot_w64(valid);
-#endif
     while (todo != 0ull) {
         const uint32_t t = (uint32_t)__builtin_amdgcn_readlane((int)cur, __builtin_ctzll(todo));
         const bool mine = valid && cur == t;

@@ -50,39 +50,6 @@
 
 namespace {
 
-#ifndef ST_GROUP_GATHER
-#define ST_GROUP_GATHER 1                 // packets smaller than the wave test 64 / R candidates per step (st_gather_group); 0: one per step (A/B)
-#endif
-#ifndef ST_REPLAY_MERGE
-#define ST_REPLAY_MERGE 1                 // the replaying backward merges neighbouring lanes that hold the same surfel BEFORE the LDS collection; 0: after (A/B)
-#endif
-#ifndef ST_REC_REFETCH
-#define ST_REC_REFETCH 0                  // st_gather_group: candidate records re-read from memory instead of ds_bpermute from the holding lane (A/B)
-#endif
-#ifndef ST_NO_WET
-#define ST_NO_WET 0                       // developer A/B: 1 = the forward leaves the per-surfel weight sums out (wrong `wet`, timing only)
-#endif
-#ifndef ST_LONE_IN_BLOCK
-#define ST_LONE_IN_BLOCK 1                // backward: a single ray whose record suffices is replayed by its block's wave (LDS gradient table); 0: st_replay_lone_rays4 / a wave of its own (A/B)
-#endif
-#ifndef ST_REPLAY4
-#define ST_REPLAY4 1                      // backward: single rays whose record suffices are replayed four to a wave (st_replay_lone_rays4); 0: one per wave (A/B)
-#endif
-#ifndef ST_NO_STEAL
-#define ST_NO_STEAL 0
-#endif
-#ifndef ST_GLOBAL_ORDER
-#define ST_GLOBAL_ORDER 0
-#endif
-#ifndef ST_REST_SCHED_STATIC_REGION
-#define ST_REST_SCHED_STATIC_REGION 0
-#endif
-#ifndef ST_REST_SCHED
-#define ST_REST_SCHED 0                   // second launch of the forward: 0 = items by ticket, own region first; 1 = every list strided over all waves (A/B)
-#endif
-#ifndef ST_REST_LONE_FIRST
-#define ST_REST_LONE_FIRST 0
-#endif
 #ifndef ST_FWD_WAVES
 #define ST_FWD_WAVES 4                    // waves per SIMD the forward walking kernels are compiled for (register budget 512 / that)
 #endif
@@ -564,16 +531,11 @@ __device__ __forceinline__ int st_gather_wide(const StWide& W, const float* __re
         while (m) {
             const int c = __builtin_ctzll(m);
             m &= m - 1;
-#if ST_REC_REFETCH
-            const float4* gq = leaf + ((size_t)__builtin_amdgcn_readfirstlane(node[0]) * 64 + (size_t)c) * 4;      // (wave-uniform address)
-            const float4 h0 = gq[0], h1 = gq[1], h2 = gq[2], h3 = gq[3];
-#else
             auto bc = [c](float v) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), c)); };
             const float4 h0 = make_float4(bc(rec0.x), bc(rec0.y), bc(rec0.z), bc(rec0.w)), h1 = make_float4(bc(rec1.x), bc(rec1.y), bc(rec1.z), bc(rec1.w));
             const float4 h2 = make_float4(bc(rec2.x), bc(rec2.y), bc(rec2.z), bc(rec2.w));
             float4 h3;
             h3.x = bc(rec3.x); h3.y = bc(rec3.y);
-#endif
 #ifdef ST_PROFILE
             ++prof.tests;
 #endif
@@ -716,20 +678,11 @@ __device__ __forceinline__ int st_gather_group(const StWide& W, const float* __r
                 ++prof.tests;
 #endif
             }
-#if ST_REC_REFETCH
-            // the candidate's record from memory again (the leaf group's 4 KB were fetched a moment ago: L1 / L2) instead of from the lane
-            // that holds it: thirteen ds_bpermute less per step and rec0..3 are dead across the candidate loop
-            const float4* gq = leaf + ((size_t)node[0] * 64 + (size_t)c) * 4;
-            const float4 h0 = gq[0], h1 = gq[1], h2 = gq[2], h3q = gq[3];
-            const float opac = h3q.x;
-            const uint32_t id = __float_as_uint(h3q.y);
-#else
             const float4 h0 = make_float4(from(c, rec0.x), from(c, rec0.y), from(c, rec0.z), from(c, rec0.w));
             const float4 h1 = make_float4(from(c, rec1.x), from(c, rec1.y), from(c, rec1.z), from(c, rec1.w));
             const float4 h2 = make_float4(from(c, rec2.x), from(c, rec2.y), from(c, rec2.z), from(c, rec2.w));
             const float opac = from(c, rec3.x);
             const uint32_t id = __float_as_uint(from(c, rec3.y));
-#endif
             const StHit h = st_hit(h0, h1, h2, opac, rox, roy, roz, rdx, rdy, rdz);
             const bool take = have && ron && h.ok && (first_pass || h.t > rprev_t || (h.t == rprev_t && id > rprev_id));
             const unsigned long long takers = __ballot(take);
@@ -978,11 +931,11 @@ __device__ __forceinline__ void st_trace_tile(const StArgs& A, const float4* __r
     const bool mine = only_packet < 0 ? (no_ray || (packet >= 0 && !deferred)) : (packet == only_packet);
     // The replaying backward also takes its block's single rays along when their recorded hits suffice (round 5): the lane follows the
     // ray's own record (the sorted keys st_trace_lone_rays kept) through the same blend loop and the same LDS gradient table as its
-    // neighbours, who meet the same surfels.  A wave per such ray -- or per four of them, st_replay_lone_rays4 -- sent 18 float atomics
+    // neighbours, who meet the same surfels.  A wave per such ray (or per four of them) sent 18 float atomics
     // per hit straight to memory: 12 300 rays cost 0.15 ms at C3 size, 52 000 cost 0.56 ms at C4 size, the atomic unit's rate.
     bool lone_here = false;
     const unsigned long long* lrec = nullptr;
-    if (MODE == 2 && ST_LONE_IN_BLOCK && only_packet < 0 && lone && A.lone_rec != nullptr) {
+    if (MODE == 2 && only_packet < 0 && lone && A.lone_rec != nullptr) {
         const uint32_t code = A.lone_slot[r], lloc = code & 0x0FFFFFFFu;
         if (lloc < A.lone_cap && A.state[4 * r + 3] <= (float)ST_LONE_REC_PASSES) {
             lone_here = true;
@@ -1026,7 +979,7 @@ __device__ __forceinline__ void st_trace_tile(const StArgs& A, const float4* __r
             for (uint32_t left = packets_present; left; left &= left - 1) {          // wave-uniform: one walk per packet
                 const int pk = __builtin_ctz(left);
                 const bool mine = want && packet == pk;
-                const int got = (pk == 0 || ST_GROUP_GATHER == 0)
+                const int got = pk == 0
                     ? st_gather_wide(A.wide, wide_boxes, wide_vmask, leaf_ro, kb_id, kb_t, tid, ox, oy, oz, dx, dy, dz, ivx, ivy, ivz, prev_t, prev_id, pass == 0, mine, prof)
                     : st_gather_group(A.wide, wide_boxes, wide_vmask, leaf_ro, kb_id, kb_t, kb_n, tid, pk, A.ray_width > 0, ox, oy, oz, dx, dy, dz, prev_t, prev_id,
                                       pass == 0, mine, prof);
@@ -1080,7 +1033,7 @@ __device__ __forceinline__ void st_trace_tile(const StArgs& A, const float4* __r
                     X[0] += w * a0.w; X[1] += w * a1.x;
                     dist += w * (t * t * Aw + M2 - 2.0f * t * M1);
                     D += w * t; Aw += w; M1 += w * t; M2 += w * t * t;
-                    if (!ST_NO_WET) atomicAdd(A.wet + id, w);
+                    atomicAdd(A.wet + id, w);
                 }
             } else {
                 float gv[18];
@@ -1112,29 +1065,10 @@ __device__ __forceinline__ void st_trace_tile(const StArgs& A, const float4* __r
                 }
                 // merge with the horizontal, then the vertical neighbour of the 8x8 block when both hold the same surfel: the lower
                 // lane of a pair carries the sum, the upper one is done (DPP moves: quad_perm [1,0,3,2] = lane ^ 1, [2,3,0,1] = lane ^ 2, row_ror:8 = lane ^ 8).
-                // The replay merges FIRST and collects in LDS what is left (ST_REPLAY_MERGE, round 5): neighbouring rays hold the same surfel
-                // at the same rank more often than not, and up to eight lanes adding to one LDS row are eight serialised ds_add_f32 per term
-                // (688 k / 2.78 M conflict cycles per launch at C3 / C4 size with the LDS pipe the busiest unit of the kernel).
+                // The replay merges BEFORE it collects in LDS what is left: neighbouring rays hold the same surfel at the same rank more
+                // often than not, and up to eight lanes adding to one LDS row are eight serialised ds_add_f32 per term.
                 bool live = act;
                 bool placed = false;
-                auto collect = [&]() {
-                    if (MODE == 2 && live) {
-                        int slot = (int)(((id * 2654435761u) >> 16) % (uint32_t)ST_TAB);
-                        for (int probe = 0; probe < 4 && !placed; ++probe) {
-                            const uint32_t old = atomicCAS(&tab[slot * 19 + 18], ST_REC_NONE, id);
-                            if (old == ST_REC_NONE || old == id) placed = true;
-                            else slot = slot + 1 == ST_TAB ? 0 : slot + 1;
-                        }
-                        if (placed) {
-                            float* row = reinterpret_cast<float*>(tab) + slot * 19;
-#pragma unroll
-                            for (int k = 0; k < 18; ++k) atomicAdd(row + k, gv[k]);
-                        }
-                    }
-                };
-                if (!ST_REPLAY_MERGE) collect();
-                if (MODE != 2 || ST_REPLAY_MERGE || __ballot(act && !placed) != 0) {
-                live = act && !placed;                                      // (what is collected in LDS already takes no part in the merge below)
                 {
                     const uint32_t pid = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)id, 0xB1, 0xf, 0xf, true);
                     const bool plive = __builtin_amdgcn_update_dpp(0, (int)live, 0xB1, 0xf, 0xf, true) != 0;
@@ -1174,7 +1108,23 @@ __device__ __forceinline__ void st_trace_tile(const StArgs& A, const float4* __r
                     }
                     live = live && !(merge && !lower);
                 }
-                if (ST_REPLAY_MERGE) collect();
+                // what is left collects in the LDS table (kept a lambda: as a plain block the kernel compiles to another schedule)
+                auto collect = [&]() {
+                    if (MODE == 2 && live) {
+                        int slot = (int)(((id * 2654435761u) >> 16) % (uint32_t)ST_TAB);
+                        for (int probe = 0; probe < 4 && !placed; ++probe) {
+                            const uint32_t old = atomicCAS(&tab[slot * 19 + 18], ST_REC_NONE, id);
+                            if (old == ST_REC_NONE || old == id) placed = true;
+                            else slot = slot + 1 == ST_TAB ? 0 : slot + 1;
+                        }
+                        if (placed) {
+                            float* row = reinterpret_cast<float*>(tab) + slot * 19;
+#pragma unroll
+                            for (int k = 0; k < 18; ++k) atomicAdd(row + k, gv[k]);
+                        }
+                    }
+                };
+                collect();
                 if (live && !placed) {
                     float* gg = A.g_geom + (size_t)id * 16;
 #pragma unroll
@@ -1182,7 +1132,6 @@ __device__ __forceinline__ void st_trace_tile(const StArgs& A, const float4* __r
                     float* ga_ = A.g_attr + (size_t)id * 8;
 #pragma unroll
                     for (int k = 0; k < 5; ++k) atomicAdd(ga_ + k, gv[13 + k]);
-                }
                 }
             }
             if (act) { T = test_T; ++blended; }
@@ -1317,7 +1266,7 @@ __device__ __forceinline__ void st_trace_lone_rays(const StArgs& A, const float4
                                                    bool skip_replayable = false)
 {
     // item_stride == 0: the one item `first_item` (the forward's second launch hands items out by ticket); otherwise every item_stride-th
-    // skip_replayable (backward): rays whose recorded hits suffice are st_replay_lone_rays4's, four to a wave
+    // skip_replayable (backward): rays whose recorded hits suffice are replayed by their blocks' waves (st_trace_tile)
     const uint32_t listed = ST_CNT(lone_list, region);
     const uint32_t count = listed < A.lone_list_cap ? listed : A.lone_list_cap;
     const StWide& W = A.wide;
@@ -1461,7 +1410,7 @@ __device__ __forceinline__ void st_trace_lone_rays(const StArgs& A, const float4
                 N0 += wave_sum_f(w * nfx); N1 += wave_sum_f(w * nfy); N2 += wave_sum_f(w * nfz);
                 X0 += wave_sum_f(w * a0.w); X1 += wave_sum_f(w * a1.x);
                 dist += wave_sum_f(w * (t * t * Ab + M2b - 2.0f * t * M1b));
-                if (bl && !ST_NO_WET) atomicAdd(A.wet + id, w);
+                if (bl) atomicAdd(A.wet + id, w);
             } else {
                 const float q = gc0 * a0.x + gc1 * a0.y + gc2 * a0.z + gd * t + ga + gn0 * nfx + gn1 * nfy + gn2 * nfz + gx0 * a0.w + gx1 * a1.x
                               + gdist * (t * t * fA - 2.0f * t * fM1 + fM2);
@@ -1524,116 +1473,6 @@ __device__ __forceinline__ void st_trace_lone_rays(const StArgs& A, const float4
     }
 }
 
-// Backward of the single rays whose recorded hits suffice (ST_LONE_REC_PASSES passes of 16 sorted keys), FOUR RAYS PER WAVE: the replay
-// needs no walk, and a ray's 16 hits fill one 16-lane DPP row -- hit j of ray `row` in lane 16 row + j.  Same arithmetic as the replaying
-// branch of st_trace_lone_rays<true> (round 3 gave every such ray a wave of its own, 48 of whose 64 lanes idled through the gathers:
-// 385 us for 12 300 rays at C3 size, 1.0 ms at C4 size), with the wave-wide scans and sums cut down to the row.
-__device__ __forceinline__ float row_sum_f(float v)             // sum over the 16-lane row, in every lane of the row
-{
-    v += ST_DPP(0.0f, v, 0xb1, 0xf); v += ST_DPP(0.0f, v, 0x4e, 0xf); v += ST_DPP(0.0f, v, 0x124, 0xf); v += ST_DPP(0.0f, v, 0x128, 0xf);
-    return v;
-}
-__device__ __forceinline__ void st_replay_lone_rays4(const StArgs& A, const uint32_t* __restrict__ lone_list, int lane, uint32_t region,
-                                                     uint32_t first_quad, uint32_t quad_stride)
-{
-    if (A.lone_rec == nullptr) return;
-    const uint32_t listed = ST_CNT(lone_list, region);
-    uint32_t count = listed < A.lone_list_cap ? listed : A.lone_list_cap;
-    if (count > A.lone_cap) count = A.lone_cap;                  // (items beyond the record's capacity walk again: st_trace_lone_rays)
-    const int row = lane >> 4, j = lane & 15;
-    for (uint32_t quad = first_quad; 4u * quad < count; quad += quad_stride) {
-        const uint32_t item = 4u * quad + (uint32_t)row;
-        bool valid = item < count;
-        const int64_t r = valid ? (int64_t)lone_list[ST_LIST_HDR + (size_t)region * A.lone_list_cap + item] : 0;
-        valid = valid && A.state[4 * r + 3] <= (float)ST_LONE_REC_PASSES;
-        if (__ballot(valid) == 0) continue;
-        const float ox = A.ray_o[3 * r], oy = A.ray_o[3 * r + 1], oz = A.ray_o[3 * r + 2];
-        const float dx = A.ray_d[3 * r], dy = A.ray_d[3 * r + 1], dz = A.ray_d[3 * r + 2];
-        float gc0 = 0, gc1 = 0, gc2 = 0, gd = 0, ga = 0, gn0 = 0, gn1 = 0, gn2 = 0, gx0 = 0, gx1 = 0, gdist = 0;
-        if (A.g_rgb) { gc0 = A.g_rgb[3 * r]; gc1 = A.g_rgb[3 * r + 1]; gc2 = A.g_rgb[3 * r + 2]; }
-        if (A.g_dpt) gd = A.g_dpt[r];
-        if (A.g_acc) ga = A.g_acc[r];
-        if (A.g_dist) gdist = A.g_dist[r];
-        if (A.g_norm) { gn0 = A.g_norm[3 * r]; gn1 = A.g_norm[3 * r + 1]; gn2 = A.g_norm[3 * r + 2]; }
-        if (A.g_aux) { gx0 = A.g_aux[2 * r]; gx1 = A.g_aux[2 * r + 1]; }
-        const float fA = A.acc[r], fM1 = A.dpt[r], fM2 = A.state[4 * r], fT = A.state[4 * r + 1];
-        const float bgdot = gc0 * A.bg[0] + gc1 * A.bg[1] + gc2 * A.bg[2];
-        const float Qtot = gc0 * (A.rgb[3 * r] - fT * A.bg[0]) + gc1 * (A.rgb[3 * r + 1] - fT * A.bg[1]) + gc2 * (A.rgb[3 * r + 2] - fT * A.bg[2])
-                         + gd * fM1 + ga * fA + gn0 * A.norm[3 * r] + gn1 * A.norm[3 * r + 1] + gn2 * A.norm[3 * r + 2]
-                         + gx0 * A.aux[2 * r] + gx1 * A.aux[2 * r + 1] + gdist * 2.0f * (fA * fM2 - fM1 * fM1);
-        float T = 1.0f, Qpre = 0.0f;
-        float go0 = 0, go1 = 0, go2 = 0, gv0 = 0, gv1 = 0, gv2 = 0;
-        bool done = !valid;
-        const unsigned long long* rec = A.lone_rec + ((size_t)region * A.lone_cap + (valid ? item : 0u)) * (ST_LONE_REC_PASSES * ST_K);
-        for (int pass = 0; pass < ST_LONE_REC_PASSES; ++pass) {
-            if (__ballot(!done) == 0) break;
-            const unsigned long long mine = done ? ~0ull : rec[pass * ST_K + j];
-            const uint32_t rowmask = (uint32_t)(__ballot(mine != ~0ull) >> (16 * row)) & 0xFFFFu;
-            const int nb = (int)__popc(rowmask);
-            const bool has = j < nb;
-            const uint32_t id = (uint32_t)mine;
-            const float t = has ? __uint_as_float((uint32_t)(mine >> 32)) : 0.0f;
-            float4 g0 = make_float4(0, 0, 0, 0), g1 = g0, g2 = g0, a0 = g0, a1 = g0;
-            float opacity = 0.f;
-            StHit h;
-            h.alpha = 0.f; h.den = 1.f; h.u = h.v = h.G = 0.f;
-            if (has) {
-                const float4* g = A.geom + (size_t)id * 4;
-                g0 = g[0]; g1 = g[1]; g2 = g[2]; opacity = g[3].x;
-                a0 = A.attr[(size_t)id * 2]; a1 = A.attr[(size_t)id * 2 + 1];
-                h = st_hit(g0, g1, g2, opacity, ox, oy, oz, dx, dy, dz);
-            }
-            const float alpha = has ? h.alpha : 0.0f;
-            const float Tj = T * scan16_mul_excl(1.0f - alpha, lane);          // transmittance in front of hit j
-            const uint32_t stop = (uint32_t)(__ballot(has && Tj * (1.0f - alpha) < 0.0001f) >> (16 * row)) & 0xFFFFu;
-            const int n_bl = stop ? min(nb, (int)__builtin_ctz(stop)) : nb;
-            const bool bl = j < n_bl;
-            const float w = bl ? alpha * Tj : 0.0f;
-            const float sgn = h.den > 0.0f ? -1.0f : 1.0f;
-            const float nfx = sgn * g2.y, nfy = sgn * g2.z, nfz = sgn * g2.w;
-            const float q = gc0 * a0.x + gc1 * a0.y + gc2 * a0.z + gd * t + ga + gn0 * nfx + gn1 * nfy + gn2 * nfz + gx0 * a0.w + gx1 * a1.x
-                          + gdist * (t * t * fA - 2.0f * t * fM1 + fM2);
-            const float wq = w * q;
-            const float Qin = Qpre + scan16_add_excl(wq, lane) + wq;            // inclusive
-            if (bl) {
-                const float inv1ma = 1.0f / (1.0f - alpha);
-                const float dalpha = Tj * q - (Qtot - Qin) * inv1ma - fT * bgdot * inv1ma;
-                const float dG = opacity * dalpha;
-                const float du = -h.u * h.G * dG, dv = -h.v * h.G * dG;
-                const float ax = g0.w, ay = g1.x, az = g1.y, bx = g1.z, by = g1.w, bz = g2.x, nx = g2.y, ny = g2.z, nz = g2.w;
-                const float px = (ox + t * dx) - g0.x, py = (oy + t * dy) - g0.y, pz = (oz + t * dz) - g0.z;
-                const float dpx = du * ax + dv * bx, dpy = du * ay + dv * by, dpz = du * az + dv * bz;
-                const float dt = w * (gd + gdist * 2.0f * (t * fA - fM1)) + (dpx * dx + dpy * dy + dpz * dz);
-                const float dnum = dt / h.den, dden = -dt * t / h.den;
-                float* gg = A.g_geom + (size_t)id * 16;
-                atomicAdd(gg + 0, -dpx + dnum * nx); atomicAdd(gg + 1, -dpy + dnum * ny); atomicAdd(gg + 2, -dpz + dnum * nz);
-                atomicAdd(gg + 3, du * px); atomicAdd(gg + 4, du * py); atomicAdd(gg + 5, du * pz);
-                atomicAdd(gg + 6, dv * px); atomicAdd(gg + 7, dv * py); atomicAdd(gg + 8, dv * pz);
-                atomicAdd(gg + 9, dnum * (g0.x - ox) + dden * dx + sgn * w * gn0);
-                atomicAdd(gg + 10, dnum * (g0.y - oy) + dden * dy + sgn * w * gn1);
-                atomicAdd(gg + 11, dnum * (g0.z - oz) + dden * dz + sgn * w * gn2);
-                atomicAdd(gg + 12, h.G * dalpha);
-                float* ga_ = A.g_attr + (size_t)id * 8;
-                atomicAdd(ga_ + 0, w * gc0); atomicAdd(ga_ + 1, w * gc1); atomicAdd(ga_ + 2, w * gc2);
-                atomicAdd(ga_ + 3, w * gx0); atomicAdd(ga_ + 4, w * gx1);
-                go0 += dpx - dnum * nx; go1 += dpy - dnum * ny; go2 += dpz - dnum * nz;
-                gv0 += t * dpx + dden * nx; gv1 += t * dpy + dden * ny; gv2 += t * dpz + dden * nz;
-            }
-            Qpre += row_sum_f(wq);
-            const float keep = bl ? 1.0f - alpha : 1.0f;
-            float prod = keep;          // product over the row's 16 lanes (the order of st_trace_lone_rays)
-            prod *= ST_DPP(1.0f, prod, 0xb1, 0xf); prod *= ST_DPP(1.0f, prod, 0x4e, 0xf); prod *= ST_DPP(1.0f, prod, 0x124, 0xf); prod *= ST_DPP(1.0f, prod, 0x128, 0xf);
-            T *= prod;
-            if (stop || nb < ST_K) done = true;
-        }
-        const float s0 = row_sum_f(go0), s1 = row_sum_f(go1), s2 = row_sum_f(go2), v0 = row_sum_f(gv0), v1 = row_sum_f(gv1), v2 = row_sum_f(gv2);
-        if (valid && j == 0) {
-            A.g_ray_o[3 * r] = s0; A.g_ray_o[3 * r + 1] = s1; A.g_ray_o[3 * r + 2] = s2;
-            A.g_ray_d[3 * r] = v0; A.g_ray_d[3 * r + 1] = v1; A.g_ray_d[3 * r + 2] = v2;
-        }
-    }
-}
-
 // second launch: every listed packet and every listed single ray gets a wave.  One launch for both: each kind ends in a tail of a few long
 // waves, and the two tails overlap instead of following each other.
 // FORWARD (MODE 0): ST_REST_BLOCKS blocks of persistent waves.  A wave of XCD x (block b, x = b % 8) takes the next packet of region x's
@@ -1645,13 +1484,12 @@ __device__ __forceinline__ void st_replay_lone_rays4(const StArgs& A, const uint
 // A ticket is one L2 atomic per ~150 us walk.  BACKWARD (MODE 1 / 2): no walk to keep local (the replay reads records), and the state
 // is not the backward's to write: every list is strided over all waves of the launch.
 constexpr int ST_REST_BLOCKS = 2048;
-constexpr int ST_REST_PACKET_BLOCKS = 2048;      // ST_REST_SCHED == 2 only (A/B)
 
 // ST_CNT(hdr, r): counts of the eight region lists (final: written by the launch before); ST_TKT(hdr, r): tickets (zeroed by st_init_kernel).  `k`:
 // regions this wave has found exhausted (tickets only grow: they stay exhausted).  Wave-uniform result.
 __device__ __forceinline__ bool st_next_item(uint32_t* hdr, uint32_t cap, uint32_t own, int lane, uint32_t& k, uint32_t& region, uint32_t& local)
 {
-    for (; k < (ST_NO_STEAL ? 1u : 8u); ++k) {
+    for (; k < 8u; ++k) {
         const uint32_t r = (own + k) & 7u;
         const uint32_t listed = ST_CNT(hdr, r);
         const uint32_t n = listed < cap ? listed : cap;
@@ -1674,57 +1512,9 @@ __global__ __launch_bounds__(ST_THREADS) __attribute__((amdgpu_waves_per_eu(MODE
     __shared__ unsigned long long slot[ST_THREADS / 64][ST_K];
     if (MODE != 0 && A.rec_hdr != nullptr && ((A.rec_hdr[1] != 0u) != (MODE == 1))) return;     // the other backward does the work
     const int tid = threadIdx.x, lane = tid & 63;
-    if (MODE == 0 && ST_REST_SCHED == 2) {
-        // tickets, but a wave takes only its share of the items and retires (the hardware's dispatcher starts the next block): blocks below
-        // ST_REST_PACKET_BLOCKS take packets, the others single rays
-        const uint32_t own = ST_GLOBAL_ORDER ? 0u : (blockIdx.x & 7u);
-        uint32_t k = 0, region = 0, local = 0;
-        if (ST_REST_SCHED_STATIC_REGION) {
-            // (A/B) XCD x walks region x's lists, one item per wave and stride
-            const uint32_t r = blockIdx.x & 7u;
-            if (blockIdx.x < ST_REST_PACKET_BLOCKS) {
-                if (A.defer_list == nullptr) return;
-                const uint32_t listed = ST_CNT(A.defer_list, r), count = listed < A.defer_cap ? listed : A.defer_cap;
-                for (uint32_t l = (blockIdx.x >> 3) * (ST_THREADS / 64) + (tid >> 6); l < count; l += (ST_REST_PACKET_BLOCKS / 8) * (ST_THREADS / 64)) {
-                    const uint32_t item = r * A.defer_cap + l;
-                    const uint32_t code = A.defer_list[ST_LIST_HDR + item];
-                    if (code == ST_REC_NONE) continue;
-                    st_trace_tile<MODE>(A, leaf_ro, wide_boxes, wide_vmask, kb_id, kb_t, kb_n, tab[0], tid, (int64_t)(code >> 5), (int)(code & 31u), A.n_tiles + item, r);
-                }
-            } else {
-                st_trace_lone_rays<false>(A, leaf_ro, wide_boxes, wide_vmask, lone_list, slot[tid >> 6], lane, r,
-                                          ((blockIdx.x - ST_REST_PACKET_BLOCKS) >> 3) * (ST_THREADS / 64) + (tid >> 6), ((gridDim.x - ST_REST_PACKET_BLOCKS) / 8) * (ST_THREADS / 64));
-            }
-            return;
-        }
-        if (blockIdx.x < ST_REST_PACKET_BLOCKS) {
-            if (A.defer_list == nullptr) return;
-            uint32_t total = 0;
-            for (int r = 0; r < 8; ++r) total += min(ST_CNT(A.defer_list, r), A.defer_cap);
-            const uint32_t waves = ST_REST_PACKET_BLOCKS * (ST_THREADS / 64);
-            for (uint32_t q = (total + waves - 1) / waves; q > 0 && st_next_item(A.defer_list, A.defer_cap, own, lane, k, region, local); --q) {
-                const uint32_t item = region * A.defer_cap + local;
-                const uint32_t code = A.defer_list[ST_LIST_HDR + item];
-                if (code == ST_REC_NONE) continue;
-                st_trace_tile<MODE>(A, leaf_ro, wide_boxes, wide_vmask, kb_id, kb_t, kb_n, tab[0], tid, (int64_t)(code >> 5), (int)(code & 31u), A.n_tiles + item, region);
-            }
-        } else {
-            uint32_t total = 0;
-            for (int r = 0; r < 8; ++r) total += min(ST_CNT(lone_list, r), A.lone_list_cap);
-            const uint32_t waves = (gridDim.x - ST_REST_PACKET_BLOCKS) * (ST_THREADS / 64);
-            for (uint32_t q = (total + waves - 1) / waves; q > 0 && st_next_item(lone_list, A.lone_list_cap, own, lane, k, region, local); --q)
-                st_trace_lone_rays<false>(A, leaf_ro, wide_boxes, wide_vmask, lone_list, slot[tid >> 6], lane, region, local, 0u);
-        }
-        return;
-    }
-    if (MODE == 0 && ST_REST_SCHED == 0) {
+    if (MODE == 0) {
         const uint32_t own = blockIdx.x & 7u;
         uint32_t k = 0, region = 0, local = 0;
-#if ST_REST_LONE_FIRST
-        while (st_next_item(lone_list, A.lone_list_cap, own, lane, k, region, local))
-            st_trace_lone_rays<false>(A, leaf_ro, wide_boxes, wide_vmask, lone_list, slot[tid >> 6], lane, region, local, 0u);
-        k = 0;
-#endif
         if (A.defer_list != nullptr) {
             while (st_next_item(A.defer_list, A.defer_cap, own, lane, k, region, local)) {
                 const uint32_t item = region * A.defer_cap + local;
@@ -1733,11 +1523,9 @@ __global__ __launch_bounds__(ST_THREADS) __attribute__((amdgpu_waves_per_eu(MODE
                 st_trace_tile<MODE>(A, leaf_ro, wide_boxes, wide_vmask, kb_id, kb_t, kb_n, tab[0], tid, (int64_t)(code >> 5), (int)(code & 31u), A.n_tiles + item, region);
             }
         }
-#if !ST_REST_LONE_FIRST
         k = 0;
         while (st_next_item(lone_list, A.lone_list_cap, own, lane, k, region, local))
             st_trace_lone_rays<false>(A, leaf_ro, wide_boxes, wide_vmask, lone_list, slot[tid >> 6], lane, region, local, 0u);
-#endif
         return;
     }
     // every stride-th item of the eight lists laid end to end: region r's items start at the sum of the counts before it
@@ -1757,20 +1545,11 @@ __global__ __launch_bounds__(ST_THREADS) __attribute__((amdgpu_waves_per_eu(MODE
             before += count;
         }
     }
-    if (MODE == 2 && ST_REPLAY4 && !ST_LONE_IN_BLOCK) {
-        // the rays whose record suffices, four to a wave; the others (more passes than the record keeps) walk again below
-        uint32_t before4 = 0;
-        for (uint32_t region = 0; region < 8u; ++region) {
-            const uint32_t listed = ST_CNT(lone_list, region);
-            st_replay_lone_rays4(A, lone_list, lane, region, (wave + stride - before4 % stride) % stride, stride);
-            before4 += ((listed < A.lone_list_cap ? listed : A.lone_list_cap) + 3u) / 4u;
-        }
-    }
     uint32_t before = 0;
     for (uint32_t region = 0; region < 8u; ++region) {
         const uint32_t listed = ST_CNT(lone_list, region);
         st_trace_lone_rays<MODE != 0>(A, leaf_ro, wide_boxes, wide_vmask, lone_list, slot[tid >> 6], lane, region, (wave + stride - before % stride) % stride, stride,
-                                      MODE == 2 && (ST_REPLAY4 || ST_LONE_IN_BLOCK));
+                                      MODE == 2);
         before += listed < A.lone_list_cap ? listed : A.lone_list_cap;
     }
 }
@@ -1912,6 +1691,11 @@ __global__ __launch_bounds__(256) void st_zero2_kernel(float4* __restrict__ a, s
     if (i < nb) b[i] = make_float4(0.f, 0.f, 0.f, 0.f);
 }
 
+// 1 - cos of the half-angle within which a block / quadrant / 2x2 group of rays must stay to share a walk (st_run_together)
+constexpr float ST_CONE = 0.005f;
+constexpr float ST_CONE_QUAD = ST_CONE;
+constexpr float ST_CONE_GROUP = 0.2f * ST_CONE;     // 2x2 groups must be tighter still: four rays rarely pay for a wide beam
+
 static int st_launch(bool bwd, void* blob, int64_t n_surfels, int64_t n_rays, int32_t ray_width, size_t state_floats, StArgs& a, hipStream_t st)
 {
     a.n_rays = n_rays;
@@ -1926,16 +1710,13 @@ static int st_launch(bool bwd, void* blob, int64_t n_surfels, int64_t n_rays, in
     a.ray_width = (ray_width > 0 && n_rays % ray_width == 0) ? ray_width : 0;
     static const bool no_packets = getenv("MRGS_TRACE_NO_PACKETS") != nullptr;      // developer switch: every ray gets a wave of its own
     a.packets = no_packets ? 0 : 1;
-    static const char* cone_env = getenv("MRGS_TRACE_CONE");
-    a.cone = cone_env ? (float)atof(cone_env) : 0.005f;
-    static const char* cone1_env = getenv("MRGS_TRACE_CONE_QUAD");
-    static const char* cone2_env = getenv("MRGS_TRACE_CONE_GROUP");
-    a.cone_quad = cone1_env ? (float)atof(cone1_env) : a.cone;
-    a.cone_group = cone2_env ? (float)atof(cone2_env) : 0.2f * a.cone;       // 2x2 groups must be tighter still: four rays rarely pay for a wide beam
+    a.cone = ST_CONE;
+    a.cone_quad = ST_CONE_QUAD;
+    a.cone_group = ST_CONE_GROUP;
     const StateLayout SL = st_state(n_rays, a.ray_width);
     if (state_floats < SL.rec_arena) return MRGS_E_WORKSPACE;
     const bool have_arena = state_floats >= SL.total;       // a state without the replay record (forward-only callers): the backward walks again
-    const dim3 grid((unsigned)SL.grid), rgrid(ST_REST_SCHED == 2 ? ST_REST_PACKET_BLOCKS + 4096 : ST_REST_BLOCKS);
+    const dim3 grid((unsigned)SL.grid), rgrid(ST_REST_BLOCKS);
     uint32_t* words = reinterpret_cast<uint32_t*>(a.state);
     a.lone_list = words + SL.lone;
     a.lone_slot = words + SL.lone_slot;

@@ -27,9 +27,6 @@ _PAIR_GUESS_MAX = 64
 # scheduling aid: results do not depend on it.  An entry holds its two matrices, so their storage cannot be handed to another camera's
 # tensors while the entry exists (the address is the key), and a hit must be the same storage at the same version.
 _WORK_HINTS = {}
-_NO_HINT = bool(int(__import__("os").environ.get("MRGS_NO_WORK_HINT", "0")))   # developer switch for A/B timing
-_NO_PREPARE = bool(int(__import__("os").environ.get("MRGS_NO_PREPARE_BWD", "0")))   # developer switch: the backward orders / clears by itself
-_NO_DEFER = bool(int(__import__("os").environ.get("MRGS_NO_DEFER", "0")))   # developer switch: render functions wait for the pair count inside the rasterizer call
 _WORK_HINTS_MAX = 2048                    # cameras ...
 _WORK_HINTS_MAX_BYTES = 256 << 20         # ... and device bytes the cache may pin (a buffer is ~100 KB at 800x800, ~340 KB at 1600x1600), least recently used first out
 _WORK_HINTS_BYTES = [0]
@@ -81,7 +78,6 @@ def _hint_is_warm(raster_settings, device, P=None):
 
 
 _REORDER_EVERY = 16     # visits of a camera between two orderings of its blend waves (MRGS_HINT_REUSE_ORDER in between)
-_NO_REUSE = bool(int(__import__("os").environ.get("MRGS_NO_REUSE_ORDER", "0")))   # developer switch for A/B timing
 
 
 def _hint_flags(raster_settings, device, P, forward=False):
@@ -90,7 +86,7 @@ def _hint_flags(raster_settings, device, P, forward=False):
     0.5 ms view and changes little from one visit to the next.  Every _REORDER_EVERY-th visit orders again, and so does the first visit
     after the surfel set changed (another P, or note_surfel_set_changed()).  forward=True: the call that decides for a forward -- it
     records that the ordering launch of this forward deals the queues for (P, generation); the backward's struct carries no such flag."""
-    if _NO_HINT or _NO_REUSE or not forward:
+    if not forward:
         return 0
     ent = _hint_entry(raster_settings, device)
     if ent is None:
@@ -104,8 +100,6 @@ def _hint_flags(raster_settings, device, P, forward=False):
 
 
 def _work_hint(raster_settings, device, P=None, count_visit=False):
-    if _NO_HINT:
-        return None
     ent = _hint_entry(raster_settings, device)
     if ent is None:
         n = _lib.lib().mrgs_work_hint_bytes(int(raster_settings.image_height), int(raster_settings.image_width)) // 4
@@ -214,7 +208,7 @@ def _stream(device):
 _RESOLVE = object()
 # MrgsRasterInputs::features_live of the render being issued on this thread (GaussianRasterizer.features_live: the settings tuple keeps
 # the reference's fields); the autograd node notes it for its backward
-_LIVE = __import__("threading").local()
+_LIVE = threading.local()
 
 
 def _make_cfg_inputs(raster_settings, means3D, sh, colors_precomp, features, opacities, scales, rotations, cov3Ds_precomp, sh_rest=None,
@@ -330,9 +324,6 @@ class deferred_count:
 def deferred_raster_count(render_fn):
     """Decorator for the render functions: rasterizer counts are collected after the whole view has been queued; a view whose pair
     count outgrew the guess is rendered again (synchronously sized)."""
-    if _NO_DEFER:
-        return render_fn
-
     @functools.wraps(render_fn)
     def wrapper(*args, **kw):
         dc = deferred_count()
@@ -511,7 +502,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         rs = raster_settings._replace(bg=_f32c(raster_settings.bg), viewmatrix=_camera_f32c(raster_settings.viewmatrix),
                                       projmatrix=_camera_f32c(raster_settings.projmatrix), campos=_camera_f32c(raster_settings.campos))
         args = (rs, means3D, sh, colors_precomp, features, opacities, scales, rotations, cov3Ds_precomp, sh_rest,
-                any(ctx.needs_input_grad) and not _NO_PREPARE and means3D.is_cuda and _hint_is_warm(rs, means3D.device))
+                any(ctx.needs_input_grad) and means3D.is_cuda and _hint_is_warm(rs, means3D.device))
         if raster_settings.debug:
             cpu_args = cpu_deep_copy_tuple(args[1:])   # copy them before they can be corrupted
             try:
