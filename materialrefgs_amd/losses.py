@@ -4,7 +4,8 @@ three launches per view for the value and one for all gradient maps, instead of 
 elementwise kernels and their autograd mirror); there is no torch fallback -- CPU tensors raise.
 
 Differences a caller sees: the entries of `tb_dict` are 0-d device tensors instead of python floats (the reference calls
-`.item()` five times per iteration, each a host sync; `float(x)` still works), and the terms the vendored tree cannot run here
+`.item()` five times per iteration, each a host sync; `float(x)` still works), only the first image is differentiated (a second
+image that requires grad raises ValueError while grad mode is on), and the terms the vendored tree cannot run here
 (`first_order_edge_aware_loss` needs kornia, `lpips_loss` needs network weights; both default to off before iteration 18 000,
 arguments/__init__.py:142-143,223-225) raise NotImplementedError when enabled.
 """
@@ -85,6 +86,11 @@ class _FusedLoss(torch.autograd.Function):
 def fused_loss(image, gt, rend_normal=None, surf_normal=None, rend_dist=None, image_weight=None, lambda_dssim=0.2, lambda_normal=0.0,
                lambda_dist=0.0):
     """Returns (loss, terms): terms = [loss, Ll1, ssim, loss0, normal term, lambda_dist*mean(dist), psnr, mse per channel...]."""
+    if torch.is_grad_enabled() and gt.requires_grad:
+        # the backward forms no gradient for gt (its SSIM part would need a second set of derivative maps): refuse instead of
+        # returning a silent None where the reference's l1_loss / ssim differentiate both arguments
+        raise ValueError("materialrefgs_amd.losses: `gt` (the second image) requires grad, but the fused loss differentiates only "
+                         "the first image; pass gt.detach() or evaluate under torch.no_grad()")
     return _FusedLoss.apply(image, gt, rend_normal, surf_normal, rend_dist, image_weight, lambda_dssim, lambda_normal, lambda_dist)
 
 

@@ -56,6 +56,55 @@ def test_oracle_matches_reference_calculate_loss(tag, mode):
     assert _rel(g["rend_dist"], GOLD[key + "_g_dist"]) < 1e-12
 
 
+@pytest.mark.parametrize("tag", CASES)
+@pytest.mark.parametrize("mode", ("w", "cos"))
+def test_torch_checker_matches_the_numpy_oracle_and_reference(tag, mode):
+    """loss_oracle.calculate_loss_torch (the float64 checker of the full-size GPU tests) against the numpy oracle and the reference's
+    float64 vectors, to 1e-12 relative."""
+    d = _inputs(tag)
+    kw = dict(lambda_dssim=0.2, lambda_normal=0.05, lambda_dist=100.0)
+    tn, gn = loss_oracle.calculate_loss(d["img"], d["gt"], d["rn"], d["sn"], d["dist"], d["weight"] if mode == "w" else None, **kw)
+    T = {k: torch.from_numpy(v) for k, v in d.items()}
+    tt, gt = loss_oracle.calculate_loss_torch(T["img"], T["gt"], T["rn"], T["sn"], T["dist"], T["weight"] if mode == "w" else None, **kw)
+    names = ("Ll1", "ssim", "loss0", "normal", "dist", "psnr")
+    got = [float(tt[k]) for k in names]
+    key = f"{tag}_f64_{mode}"
+    assert _rel(got, [tn[k] for k in names]) < 1e-12 and _rel(got, GOLD[key + "_terms"]) < 1e-12
+    assert abs(float(tt["loss"]) - tn["loss"]) < 1e-12 * abs(tn["loss"]) and abs(float(tt["loss"]) - GOLD[key + "_loss"]) < 1e-12 * abs(tn["loss"])
+    np.testing.assert_allclose(tt["mse"].numpy(), tn["mse"], rtol=1e-12, atol=0)
+    for k, g in (("image", "_g_img"), ("rend_normal", "_g_rn"), ("surf_normal", "_g_sn"), ("rend_dist", "_g_dist")):
+        assert _rel(gt[k].numpy(), gn[k]) < 1e-12, k
+        assert _rel(gt[k].numpy(), GOLD[key + g]) < 1e-12, k
+    S, gS = loss_oracle.ssim_map_and_grad_torch(T["img"], T["gt"])
+    assert abs(float(S.mean()) - GOLD[f"{tag}_f64_ssim"]) < 1e-12
+    assert _rel(gS.numpy() / S.numel(), GOLD[f"{tag}_f64_ssim_grad"]) < 1e-12
+
+
+@pytest.mark.parametrize("C,H,W", [(1, 1, 1), (2, 5, 5), (4, 1, 37), (1, 37, 1), (3, 10, 11), (4, 33, 31)])
+def test_torch_checker_matches_the_numpy_oracle_on_ragged_shapes(C, H, W):
+    """Shapes below the window and channel counts other than 3 (the GPU tests' ragged cases): the two checkers agree there too."""
+    rng = np.random.default_rng(C * 1000 + H * 37 + W)
+    img, gt = rng.random((C, H, W), dtype=np.float32), rng.random((C, H, W), dtype=np.float32)
+    for lam in (0.0, 0.2, 1.0):
+        tn, gn = loss_oracle.calculate_loss(img, gt, lambda_dssim=lam)
+        tt, gt_ = loss_oracle.calculate_loss_torch(torch.from_numpy(img), torch.from_numpy(gt), lambda_dssim=lam)
+        for k in ("Ll1", "ssim", "loss", "psnr"):
+            assert abs(float(tt[k]) - tn[k]) <= 1e-12 * abs(tn[k]), (lam, k)
+        assert _rel(gt_["image"].numpy(), gn["image"]) < 1e-12, lam
+
+
+def test_second_image_that_requires_grad_is_refused():
+    """The fused loss differentiates only its first image: a gt that requires grad raises (before any device work) instead of
+    silently getting no gradient; without a graph there is nothing to refuse."""
+    from materialrefgs_amd import losses
+    img, gt = torch.rand(3, 8, 8, requires_grad=True), torch.rand(3, 8, 8, requires_grad=True)
+    for f in (losses.fused_loss, losses.l1_loss, losses.ssim):
+        with pytest.raises(ValueError, match="requires grad"):
+            f(img, gt)
+        with torch.no_grad(), pytest.raises(RuntimeError, match="device tensors"):
+            f(img, gt)
+
+
 def test_reference_fp32_is_close_to_its_fp64():
     """Sizes the tolerance of the GPU tests: the reference's own fp32 run differs from its fp64 run by this much."""
     worst = 0.0
