@@ -504,6 +504,59 @@ int mrgs_loss_backward(const MrgsLossConfig* cfg, const float* image, const floa
                        const float* image_weight, const void* ws, const float* g_loss, float* g_image, float* g_rend_normal,
                        float* g_surf_normal, float* g_rend_dist, void* stream);
 
+/* ---- multi-view material consistency loss (calc_warp_loss, train_refnerf.py:414-739, train_refreal.py:405-729) ------------------
+ * View v and neighbour n, both H x W.  Geometry: every pixel p of v is back-projected through depth_v, projected into n, looked up in
+ * depth_n (bilinear, border, align_corners), back-projected and re-projected into v; e = |p' - p|.  valid = inside n (strict bounds,
+ * view depth > 0.1) and e < pixel_noise_th; weight_map = exp(-e) on valid pixels, 0 elsewhere.  geo = geo_weight * mean over valid of
+ * weight * e (MRGS_WARP_GEO; otherwise 0).  Sampling: min(n_valid, sample_num) distinct valid pixels, uniform, deterministic for
+ * (seed, valid set), in ascending pixel order -- or the n_given pixel indices in `samples` (n_given >= 0).  Per sample, a
+ * (2 patch_half + 1)^2 patch: the view's maps at integer texels (zeros outside), the neighbour's through the sample's plane homography
+ * (bilinear, zeros, align_corners).  out_terms[4] (device): geo, base_weight * base colour term, metallic_weight * L-mean over the
+ * kept samples, roughness_weight * the same (NaN for an empty keep set; terms switched off and every term with n_valid = 0 are 0).
+ * out_counts[4] (device int32): n_valid, samples, kept samples, 0.  keep = min fg over the patch > 0.99 and keep_v[p] != 0 (NULL: all).
+ * cam_v / cam_n: device records of 28 floats, world_view_transform (row-vector form, 16), R (9), T (3) of scene/cameras.py.
+ * samples (forward, n_given = -1): if not NULL, receives the drawn pixel indices (sample_num slots; the first out_counts[1] are used).
+ * Given samples (n_given >= 0) are the caller's contract, not checked on the device: they must be distinct valid pixels inside the
+ * image (a duplicate leaves the slot map to one of its copies and the view-map gradients lose the other; an index outside is read as
+ * pixel 0), and n_given = 0 with valid pixels gives a NaN base-colour term (the mean over no sample).
+ * The view's material maps take no gradient in the reference (it samples them under torch.no_grad()); g_base_v / g_metal_v /
+ * g_rough_v are an optional extra (NULL: not computed).
+ * ws (mrgs_warp_loss_ws_bytes) carries the draw and per-sample records from forward to backward.  Backward: g_terms[4] (device) are the
+ * upstream gradients of out_terms; every non-NULL gradient map is written in full (depth [H,W], base [3,H,W], metal / rough [H,W]).
+ * Nothing reaches normal_v, distance_v, fg_v or the weights.  No host synchronisation in either call. */
+#define MRGS_WARP_GEO 1u            /* the geometric term (train_refreal.py returns it) */
+#define MRGS_WARP_MATERIAL 2u       /* sampling and the base-colour term (iteration > 10000) */
+#define MRGS_WARP_METALLIC 4u       /* directional metallic term (needs MATERIAL) */
+#define MRGS_WARP_ROUGHNESS 8u      /* directional roughness term (needs MATERIAL) */
+typedef struct MrgsWarpConfig {
+    uint32_t struct_size;           /* = sizeof(MrgsWarpConfig); checked like MrgsRasterConfig::struct_size */
+    int32_t H, W;
+    int32_t sample_num;             /* multi_view_sample_num */
+    int32_t patch_half;             /* multi_view_patch_size: 1, 2 or 3 (one 64-lane wave per patch) */
+    int32_t n_given;                /* -1: draw on the device; 0 .. sample_num: use `samples` as given */
+    uint32_t flags;                 /* MRGS_WARP_* */
+    uint32_t seed_lo, seed_hi;
+    float fx_v, fy_v, cx_v, cy_v, fx_n, fy_n, cx_n, cy_n;   /* Fx, Fy, Cx, Cy of scene/cameras.py:65-68 */
+    float pixel_noise_th, geo_weight, base_weight, metallic_weight, roughness_weight;
+} MrgsWarpConfig;
+typedef struct MrgsWarpMaps {
+    const float* depth_v;           /* surf_depth [H,W] */
+    const float* depth_n;
+    const float* normal_v;          /* rend_normal [3,H,W] */
+    const float* distance_v;        /* rend_distance [H,W] */
+    const float *base_v, *metal_v, *rough_v;   /* diffuse_map [3,H,W], refl_strength_map [H,W], roughness_map [H,W] of v */
+    const float *base_n, *metal_n, *rough_n;   /* the same of n */
+    const float* fg_v;              /* foreground mask of v [H,W] */
+    const uint8_t* keep_v;          /* [H,W] not on an edge, or NULL */
+    const float *cam_v, *cam_n;     /* device camera records (28 floats) */
+} MrgsWarpMaps;
+size_t mrgs_warp_loss_ws_bytes(int32_t H, int32_t W, int32_t sample_num, int32_t patch_half);
+int mrgs_warp_loss_forward(const MrgsWarpConfig* cfg, const MrgsWarpMaps* maps, int32_t* samples, void* ws, size_t ws_bytes,
+                           float* weight_map, float* out_terms, int32_t* out_counts, void* stream);
+int mrgs_warp_loss_backward(const MrgsWarpConfig* cfg, const MrgsWarpMaps* maps, const void* ws, const float* weight_map,
+                            const float* g_terms, float* g_depth_v, float* g_depth_n, float* g_base_v, float* g_metal_v, float* g_rough_v,
+                            float* g_base_n, float* g_metal_n, float* g_rough_n, void* stream);
+
 /* ---- closest-hit ray queries against a triangle mesh (visibility rays) --------------------
  * Replaces RayTracer(vertices, triangles).trace (submodules/raytracing/raytracing/raytracer.py:8-56,
  * raytracing_brdf/raytracer.py:18-123) = create_raytracer + TriangleBvh4::build / ray_trace_gpu

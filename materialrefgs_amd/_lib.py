@@ -95,6 +95,21 @@ class MrgsLossConfig(ctypes.Structure):
                 ("lambda_dist", c_float)]
 
 
+MRGS_WARP_GEO, MRGS_WARP_MATERIAL, MRGS_WARP_METALLIC, MRGS_WARP_ROUGHNESS = 1, 2, 4, 8
+
+
+class MrgsWarpConfig(_Sized):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("H", c_int32), ("W", c_int32), ("sample_num", c_int32), ("patch_half", c_int32),
+                ("n_given", c_int32), ("flags", ctypes.c_uint32), ("seed_lo", ctypes.c_uint32), ("seed_hi", ctypes.c_uint32)] + \
+               [(n, c_float) for n in ("fx_v", "fy_v", "cx_v", "cy_v", "fx_n", "fy_n", "cx_n", "cy_n", "pixel_noise_th", "geo_weight",
+                                       "base_weight", "metallic_weight", "roughness_weight")]
+
+
+class MrgsWarpMaps(ctypes.Structure):
+    _fields_ = [(n, c_void_p) for n in ("depth_v", "depth_n", "normal_v", "distance_v", "base_v", "metal_v", "rough_v", "base_n", "metal_n",
+                                        "rough_n", "fg_v", "keep_v", "cam_v", "cam_n")]
+
+
 class MrgsAdamTensor(ctypes.Structure):
     _fields_ = [("param", c_void_p), ("grad", c_void_p), ("exp_avg", c_void_p), ("exp_avg_sq", c_void_p), ("numel", c_int64),
                 ("lr", c_float), ("step", c_int32)]
@@ -160,6 +175,10 @@ SYMBOLS = {
                                          c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
     "mrgs_loss_backward": (ctypes.c_int, [ctypes.POINTER(MrgsLossConfig), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mrgs_warp_loss_ws_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32]),
+    "mrgs_warp_loss_forward": (ctypes.c_int, [ctypes.POINTER(MrgsWarpConfig), ctypes.POINTER(MrgsWarpMaps), c_void_p, c_void_p, c_size_t,
+                                              c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mrgs_warp_loss_backward": (ctypes.c_int, [ctypes.POINTER(MrgsWarpConfig), ctypes.POINTER(MrgsWarpMaps)] + [c_void_p] * 12),
     "mrgs_bvh_bytes": (c_size_t, [c_int64]),
     "mrgs_bvh_build": (ctypes.c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_size_t]),
     "mrgs_bvh_trace": (ctypes.c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
