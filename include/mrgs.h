@@ -557,6 +557,31 @@ int mrgs_warp_loss_backward(const MrgsWarpConfig* cfg, const MrgsWarpMaps* maps,
                             const float* g_terms, float* g_depth_v, float* g_depth_n, float* g_base_v, float* g_metal_v, float* g_rough_v,
                             float* g_base_n, float* g_metal_n, float* g_rough_n, void* stream);
 
+/* ---- grey-image patch NCC of the same view pair (get_consistency_loss2 over lncc, train_refreal.py:358-395, :707-710) -------------
+ * The term train_refreal.py adds to its loss next to the ones above; the only one whose gradient goes through the plane homography,
+ * so the only one that reaches rend_normal / rend_distance of the view.  It follows a completed mrgs_warp_loss_forward of the same
+ * (cfg, maps) on the same stream and takes that call's workspace and weight map: with MRGS_WARP_MATERIAL it reuses the draw and the
+ * stored homographies; without, it runs the same sampler (equal seed and valid set: the draw the material terms would have got; given
+ * samples are honoured the same way, and `samples` has the meaning it has there).  maps needs cam_v, cam_n, normal_v, distance_v,
+ * metal_v and metal_n whatever the flags.  grey_v / grey_n: [H,W] grey photographs.  Per sample, P = (2 patch_half + 1)^2 taps:
+ * r = grey_v at the integer texels (zeros outside), q = grey_n through the homography (bilinear, zeros, align_corners; a non-finite
+ * position samples zero); cc = cross^2 / (var_r var_q + 1e-8) from the centred patch sums (the reference's literal sums are the same
+ * numbers and cancel on flat patches), ncc = clamp(1 - cc, 0, 2); m = patch mean of metal_v + patch mean of metal_n; a sample is used
+ * when ncc < 0.9 and m < 0.4.  out_term[0] = ncc_weight * mean over the used samples of ncc * weight_map (0 where none is used: no
+ * host read decides it).  out_counts[2]: samples, used samples.  ref_weight_map [H,W]: 1 - m / 2 at the sample pixels (0 where that
+ * is below 0.9), 0 elsewhere.  out_ncc [sample_num] / out_use [sample_num] (either may be NULL): per-sample ncc and the use flag.
+ * Backward: g_term[1] (device); g_normal_v [3,H,W] and g_distance_v [H,W] (either may be NULL) are written in full.  Every sample
+ * owns its centre pixel, so there are no atomics and both calls are bitwise repeatable.  Nothing reaches the grey images, the metal
+ * maps, the weights or the depths.  The forward keeps d ncc / d (normal, distance) per sample (4 floats) in ws, so the backward is
+ * one pass over the pixels.  No host synchronisation in either call. */
+size_t mrgs_warp_ncc_ws_bytes(int32_t H, int32_t W, int32_t sample_num, int32_t patch_half);
+int mrgs_warp_ncc_forward(const MrgsWarpConfig* cfg, const MrgsWarpMaps* maps, const float* grey_v, const float* grey_n,
+                          const float* weight_map, const void* warp_ws, size_t warp_ws_bytes, int32_t* samples, void* ws, size_t ws_bytes,
+                          float ncc_weight, float* out_term, int32_t* out_counts, float* ref_weight_map, float* out_ncc, uint8_t* out_use,
+                          void* stream);
+int mrgs_warp_ncc_backward(const MrgsWarpConfig* cfg, const void* warp_ws, const void* ws, float ncc_weight, const float* g_term,
+                           float* g_normal_v, float* g_distance_v, void* stream);
+
 /* ---- closest-hit ray queries against a triangle mesh (visibility rays) --------------------
  * Replaces RayTracer(vertices, triangles).trace (submodules/raytracing/raytracing/raytracer.py:8-56,
  * raytracing_brdf/raytracer.py:18-123) = create_raytracer + TriangleBvh4::build / ray_trace_gpu

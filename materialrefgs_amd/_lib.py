@@ -179,6 +179,11 @@ SYMBOLS = {
     "mrgs_warp_loss_forward": (ctypes.c_int, [ctypes.POINTER(MrgsWarpConfig), ctypes.POINTER(MrgsWarpMaps), c_void_p, c_void_p, c_size_t,
                                               c_void_p, c_void_p, c_void_p, c_void_p]),
     "mrgs_warp_loss_backward": (ctypes.c_int, [ctypes.POINTER(MrgsWarpConfig), ctypes.POINTER(MrgsWarpMaps)] + [c_void_p] * 12),
+    "mrgs_warp_ncc_ws_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32]),
+    "mrgs_warp_ncc_forward": (ctypes.c_int, [ctypes.POINTER(MrgsWarpConfig), ctypes.POINTER(MrgsWarpMaps), c_void_p, c_void_p, c_void_p,
+                                             c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_float] + [c_void_p] * 6),
+    "mrgs_warp_ncc_backward": (ctypes.c_int, [ctypes.POINTER(MrgsWarpConfig), c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p,
+                                              c_void_p]),
     "mrgs_bvh_bytes": (c_size_t, [c_int64]),
     "mrgs_bvh_build": (ctypes.c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_size_t]),
     "mrgs_bvh_trace": (ctypes.c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -18,6 +18,8 @@
 //                       (atomics).
 //   warp_view_gather    per view pixel: the <= (2h+1)^2 samples whose patch covers it, found through the slot map; no atomics.
 //   warp_nbr_scatter    per sample wave: the bilinear corners of every neighbour tap (atomics).
+// Grey-image NCC (train_refreal.py's get_consistency_loss2), a second pair of calls on the same draw: warp_ncc_fwd / warp_ncc_finalize /
+// warp_ncc_bwd, described where they stand at the end of the file.
 // The file is compiled with -ffp-contract=off: the tap positions of the backward kernels repeat the forward's arithmetic bit for bit.
 #include "mrgs_internal.h"
 
@@ -730,6 +732,27 @@ int check_maps(const WarpArgs& a, const MrgsWarpMaps* mp)
     return MRGS_OK;
 }
 
+// the sample list and the slot map of w: the caller's samples (n_given >= 0) or the draw over w.valid; w.st holds warp_geo_finalize's words
+int draw_samples(const WarpArgs& a, const WarpWs& w, int32_t* samples, hipStream_t st)
+{
+    const int HW = a.H * a.W, nbg = (HW + WB - 1) / WB;
+    if (a.n_given >= 0) {
+        if (hipMemsetAsync(w.slot, 0xFF, (size_t)HW * 4, st) != hipSuccess) return MRGS_E_HIP;
+        if (a.n_given > 0) warp_given_samples<<<(a.n_given + WB - 1) / WB, WB, 0, st>>>(a, w, samples);
+    } else {
+        if (hipMemsetAsync(w.hist, 0, 2 * (size_t)NBINS * 4, st) != hipSuccess) return MRGS_E_HIP;
+        warp_sel_hist<<<nbg, WB, 0, st>>>(a, w, 0);
+        warp_sel_scan<<<1, FIN, 0, st>>>(w, 0);
+        warp_sel_hist<<<nbg, WB, 0, st>>>(a, w, 1);
+        warp_sel_scan<<<1, FIN, 0, st>>>(w, 1);
+        warp_compact_count<<<nbg, WB, 0, st>>>(a, w);
+        warp_compact_scan<<<1, FIN, 0, st>>>(w, nbg);
+        warp_compact_write<<<nbg, WB, 0, st>>>(a, w);
+        if (samples && hipMemcpyAsync(samples, w.samples, (size_t)a.k * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return MRGS_E_HIP;
+    }
+    return MRGS_OK;
+}
+
 }   // namespace
 
 extern "C" size_t mrgs_warp_loss_ws_bytes(int32_t H, int32_t W, int32_t sample_num, int32_t patch_half)
@@ -755,20 +778,7 @@ extern "C" int mrgs_warp_loss_forward(const MrgsWarpConfig* cfg, const MrgsWarpM
     warp_geo_fwd<<<nbg, WB, 0, st>>>(a, maps->depth_v, maps->depth_n, maps->cam_v, maps->cam_n, w, weight_map);
     warp_geo_finalize<<<1, FIN, 0, st>>>(a, w, nbg, out_terms, out_counts);
     if (!(a.flags & MRGS_WARP_MATERIAL)) return hipGetLastError() == hipSuccess ? MRGS_OK : MRGS_E_HIP;
-    if (a.n_given >= 0) {
-        if (hipMemsetAsync(w.slot, 0xFF, (size_t)HW * 4, st) != hipSuccess) return MRGS_E_HIP;
-        if (a.n_given > 0) warp_given_samples<<<(a.n_given + WB - 1) / WB, WB, 0, st>>>(a, w, samples);
-    } else {
-        if (hipMemsetAsync(w.hist, 0, 2 * (size_t)NBINS * 4, st) != hipSuccess) return MRGS_E_HIP;
-        warp_sel_hist<<<nbg, WB, 0, st>>>(a, w, 0);
-        warp_sel_scan<<<1, FIN, 0, st>>>(w, 0);
-        warp_sel_hist<<<nbg, WB, 0, st>>>(a, w, 1);
-        warp_sel_scan<<<1, FIN, 0, st>>>(w, 1);
-        warp_compact_count<<<nbg, WB, 0, st>>>(a, w);
-        warp_compact_scan<<<1, FIN, 0, st>>>(w, nbg);
-        warp_compact_write<<<nbg, WB, 0, st>>>(a, w);
-        if (samples && hipMemcpyAsync(samples, w.samples, (size_t)a.k * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return MRGS_E_HIP;
-    }
+    if ((rc = draw_samples(a, w, samples, st))) return rc;
     const Maps m = make_maps(maps);
     const int ns_max = a.n_given >= 0 ? a.n_given : a.k;
     if (ns_max > 0) warp_patch_fwd<<<(ns_max + WB / 64 - 1) / (WB / 64), WB, 0, st>>>(a, w, m, maps->cam_v, maps->cam_n, weight_map);
@@ -812,5 +822,273 @@ extern "C" int mrgs_warp_loss_backward(const MrgsWarpConfig* cfg, const MrgsWarp
         if ((g.base_n || g.metal_n || g.rough_n) && ns_max > 0)
             warp_nbr_scatter<<<(ns_max + WB / 64 - 1) / (WB / 64), WB, 0, st>>>(a, w, m, g_terms, g);
     }
+    return hipGetLastError() == hipSuccess ? MRGS_OK : MRGS_E_HIP;
+}
+
+// ---- grey-image patch NCC (get_consistency_loss2 over lncc; train_refreal.py:358-395, utils/loss_utils.py:230-265) -----------------
+// The term of the multi-view loss whose gradient goes through the plane homography: it trains rend_normal and rend_distance of the view.
+//   warp_ncc_fwd        one 64-lane wave per sample, one lane per tap: the view's grey tap r at its integer texel, the neighbour's q through
+//                       the homography.  A tap position depends on (n, d) through the one scalar s = (n . K_v^-1 X) / d: H X = A - B s with
+//                       B = K_n t_rel the same for every tap, so each lane carries dq/ds and the wave reduces the forward-mode derivative
+//                       d ncc / d (rend_normal, rend_distance) next to the value.  Double throughout: the literal lncc sums cancel on
+//                       low-contrast patches (var_r var_q next to the 1e-8 of the denominator), so the centred sums are taken instead.
+//   warp_ncc_finalize   one workgroup: the used samples in a fixed order -> the scalar and the counts.
+//   warp_ncc_bwd        per pixel of the view: the sample that owns it (slot map) scaled by the upstream gradient; no atomics.
+namespace {
+
+constexpr int ST_NUSED = 7;              // the NCC workspace's own state word (the other words are a copy of WarpWs::st)
+
+struct NccWs {
+    int32_t* st;                         // copy of the material call's state, + ST_NUSED
+    uint32_t* hist;                      // the sampler's scratch when the material call drew nothing
+    int32_t* blk;
+    int32_t* slot;
+    int32_t* samples;
+    double* val;                         // [k] ncc_s w_s on used samples, 0 elsewhere
+    float4* dval;                        // [k] w_s d ncc_s / d (N_x, N_y, N_z, d) on used samples, 0 elsewhere
+    uint8_t* use;                        // [k]
+};
+
+size_t ncc_layout(int H, int W, int k, NccWs* n, char* base)
+{
+    const size_t HW = (size_t)H * W, nbg = (HW + WB - 1) / WB;
+    size_t o = 0;
+    auto take = [&](size_t bytes) { const size_t at = o; o += al(bytes); return base ? base + at : nullptr; };
+    char* st = take(ST_WORDS * 4);
+    char* hist = take(2 * (size_t)NBINS * 4);
+    char* bk = take(nbg * 4);
+    char* sl = take(HW * 4);
+    char* sa = take((size_t)k * 4);
+    char* va = take((size_t)k * 8);
+    char* dv = take((size_t)k * 16);
+    char* us = take((size_t)k);
+    if (n) {
+        n->st = (int32_t*)st; n->hist = (uint32_t*)hist; n->blk = (int32_t*)bk; n->slot = (int32_t*)sl; n->samples = (int32_t*)sa;
+        n->val = (double*)va; n->dval = (float4*)dv; n->use = (uint8_t*)us;
+    }
+    return o;
+}
+
+__device__ __forceinline__ double wsumd(double v)
+{
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+struct NccIn {
+    const float *normal_v, *dist_v, *metal_v, *metal_n, *grey_v, *grey_n, *camv, *camn, *weight;
+    const int32_t* samples;
+    const double* homog;                 // the material call's H_s, or nullptr (computed here)
+};
+
+__global__ __launch_bounds__(WB) void warp_ncc_fwd(WarpArgs a, NccIn in, NccWs n, float* __restrict__ ref_weight,
+                                                   float* __restrict__ out_ncc, uint8_t* __restrict__ out_use)
+{
+    const int s = blockIdx.x * (WB / 64) + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (s >= n.st[ST_NSEL]) return;
+    Cam cv, cn;
+    load_cam(in.camv, cv);
+    load_cam(in.camn, cn);
+    const size_t HW = (size_t)a.H * a.W;
+    const int p = in.samples[s];
+    const int x = p % a.W, y = p / a.W;
+    double Hs[9];
+    if (in.homog) {
+        for (int i = 0; i < 9; ++i) Hs[i] = in.homog[(size_t)s * 9 + i];
+    } else {
+        Maps m{};
+        m.normal_v = in.normal_v; m.dist_v = in.dist_v;
+        homography(a, cv, cn, m, p, Hs);
+    }
+    // s_tap = (nc . r) / d with r = K_v^-1 X; H X = A - B s_tap, B = K_n t_rel
+    const double N[3] = {(double)in.normal_v[p], (double)in.normal_v[HW + p], (double)in.normal_v[2 * HW + p]};
+    const double d = (double)in.dist_v[p];
+    double nc[3], t[3];
+    for (int j = 0; j < 3; ++j) nc[j] = N[0] * cv.Wm[0][j] + N[1] * cv.Wm[1][j] + N[2] * cv.Wm[2][j];
+    for (int i = 0; i < 3; ++i) {
+        double ti = cn.Wm[3][i];
+        for (int j = 0; j < 3; ++j) {
+            const double Rij = cn.Wm[0][i] * cv.Wm[0][j] + cn.Wm[1][i] * cv.Wm[1][j] + cn.Wm[2][i] * cv.Wm[2][j];
+            ti -= Rij * cv.Wm[3][j];
+        }
+        t[i] = ti;
+    }
+    const double Bx = a.fxn * t[0] + a.cxn * t[2], By = a.fyn * t[1] + a.cyn * t[2], Bz = t[2];
+    const bool tap = lane < a.P;
+    const int side = 2 * a.h + 1;
+    const int tx = x + (lane % side) - a.h, ty = y + (lane / side) - a.h;
+    double r = 0.0, q = 0.0, mv = 0.0, mn = 0.0, dq = 0.0;       // dq = dq / ds_tap
+    double e[4] = {0.0, 0.0, 0.0, 0.0};                         // ds_tap / d (N_x, N_y, N_z, d)
+    bool ok = false;
+    if (tap) {
+        if (inb(a, tx, ty)) {
+            r = (double)in.grey_v[(size_t)ty * a.W + tx];
+            mv = (double)in.metal_v[(size_t)ty * a.W + tx];
+        }
+        const double X = (double)tx, Y = (double)ty;
+        const double gz = Hs[6] * X + Hs[7] * Y + Hs[8];
+        const double den = gz + 1e-10;
+        const double Gx = Hs[0] * X + Hs[1] * Y + Hs[2], Gy = Hs[3] * X + Hs[4] * Y + Hs[5];
+        const double gx = Gx / den, gy = Gy / den;
+        ok = gx > -2.0 && gx < (double)a.W + 1.0 && gy > -2.0 && gy < (double)a.H + 1.0;
+        if (ok) {
+            const double fx0 = floor(gx), fy0 = floor(gy);
+            const double fx = gx - fx0, fy = gy - fy0;
+            const int x0 = (int)fx0, y0 = (int)fy0;
+            const bool b00 = inb(a, x0, y0), b01 = inb(a, x0 + 1, y0), b10 = inb(a, x0, y0 + 1), b11 = inb(a, x0 + 1, y0 + 1);
+            const size_t i00 = (size_t)y0 * a.W + x0;            // (only dereferenced where the corner is inside)
+            auto corner = [&](const float* __restrict__ img, double& v00, double& v01, double& v10, double& v11) {
+                v00 = b00 ? (double)img[i00] : 0.0;
+                v01 = b01 ? (double)img[i00 + 1] : 0.0;
+                v10 = b10 ? (double)img[i00 + a.W] : 0.0;
+                v11 = b11 ? (double)img[i00 + a.W + 1] : 0.0;
+            };
+            double v00, v01, v10, v11;
+            corner(in.grey_n, v00, v01, v10, v11);
+            q = v00 * ((1.0 - fx) * (1.0 - fy)) + v01 * (fx * (1.0 - fy)) + v10 * ((1.0 - fx) * fy) + v11 * (fx * fy);
+            const double qx = (v01 - v00) * (1.0 - fy) + (v11 - v10) * fy;
+            const double qy = (v10 - v00) * (1.0 - fx) + (v11 - v01) * fx;
+            const double dgx = (Gx * Bz - Bx * den) / (den * den), dgy = (Gy * Bz - By * den) / (den * den);
+            dq = qx * dgx + qy * dgy;
+            corner(in.metal_n, v00, v01, v10, v11);
+            mn = v00 * ((1.0 - fx) * (1.0 - fy)) + v01 * (fx * (1.0 - fy)) + v10 * ((1.0 - fx) * fy) + v11 * (fx * fy);
+            const double rr[3] = {(X - a.cxv) / a.fxv, (Y - a.cyv) / a.fyv, 1.0};
+            for (int i = 0; i < 3; ++i) e[i] = (cv.Wm[i][0] * rr[0] + cv.Wm[i][1] * rr[1] + cv.Wm[i][2] * rr[2]) / d;
+            e[3] = -(nc[0] * rr[0] + nc[1] * rr[1] + nc[2] * rr[2]) / (d * d);
+        }
+    }
+    const double P = (double)a.P;
+    const double rbar = wsumd(r) / P, qbar = wsumd(q) / P, m_s = wsumd(mv) / P + wsumd(mn) / P;
+    const double rc = tap ? r - rbar : 0.0, qc = tap ? q - qbar : 0.0;
+    const double cross = wsumd(rc * qc), var_r = wsumd(rc * rc), var_q = wsumd(qc * qc);
+    const double D = var_r * var_q + 1e-8;
+    const double raw = 1.0 - cross * cross / D;
+    const double ncc = raw < 0.0 ? 0.0 : (raw > 2.0 ? 2.0 : raw);
+    const bool use = ncc < 0.9 && m_s < 0.4;
+    const float wt = in.weight[p];
+    // d ncc / dq_p = -(2 cross rc_p / D - 2 cross^2 var_r qc_p / D^2); nothing passes the clamp outside [0, 2]
+    const double al_ = 2.0 * cross / D, be_ = 2.0 * cross * cross * var_r / (D * D);
+    const double c = (ok && use && raw >= 0.0 && raw <= 2.0) ? -(al_ * rc - be_ * qc) * dq : 0.0;
+    double g[4];
+    for (int i = 0; i < 4; ++i) g[i] = wsumd(c != 0.0 ? c * e[i] : 0.0);
+    if (lane == 0) {
+        n.val[s] = use ? ncc * (double)wt : 0.0;
+        n.use[s] = (uint8_t)use;
+        n.dval[s] = use ? make_float4((float)((double)wt * g[0]), (float)((double)wt * g[1]), (float)((double)wt * g[2]), (float)((double)wt * g[3]))
+                        : make_float4(0.f, 0.f, 0.f, 0.f);
+        const double rw = 1.0 - m_s / 2.0;
+        ref_weight[p] = rw < 0.9 ? 0.f : (float)rw;
+        if (out_ncc) out_ncc[s] = (float)ncc;
+        if (out_use) out_use[s] = (uint8_t)use;
+    }
+}
+
+__global__ __launch_bounds__(FIN) void warp_ncc_finalize(NccWs n, float ncc_w, float* __restrict__ out_term, int32_t* __restrict__ out_counts)
+{
+    __shared__ double sd[FIN];
+    __shared__ long long si[FIN];
+    const int ns = n.st[ST_NSEL];
+    double v = 0.0;
+    long long c = 0;
+    for (int i = threadIdx.x; i < ns; i += FIN) { v += n.val[i]; c += n.use[i]; }
+    v = block_sum(v, sd);
+    c = block_sum(c, si);
+    if (threadIdx.x == 0) {
+        const int nu = n.st[ST_NVALID] > 0 ? (int)c : 0;
+        n.st[ST_NUSED] = nu;
+        out_term[0] = nu > 0 ? (float)((double)ncc_w * v / (double)nu) : 0.f;
+        out_counts[0] = ns;
+        out_counts[1] = nu;
+    }
+}
+
+__global__ __launch_bounds__(WB) void warp_ncc_bwd(int HW, const int32_t* __restrict__ slot, NccWs n, float ncc_w, const float* __restrict__ g_term,
+                                                   float* __restrict__ g_normal, float* __restrict__ g_dist)
+{
+    const int p = blockIdx.x * WB + threadIdx.x;
+    if (p >= HW) return;
+    const int s = slot[p], nu = n.st[ST_NUSED];
+    float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (s >= 0 && nu > 0 && n.use[s]) {
+        const double c = (double)g_term[0] * (double)ncc_w / (double)nu;
+        const float4 dv = n.dval[s];
+        o = make_float4((float)(c * dv.x), (float)(c * dv.y), (float)(c * dv.z), (float)(c * dv.w));
+    }
+    if (g_normal) { g_normal[p] = o.x; g_normal[(size_t)HW + p] = o.y; g_normal[2 * (size_t)HW + p] = o.z; }
+    if (g_dist) g_dist[p] = o.w;
+}
+
+// the NCC calls accept the configuration of the material call they follow
+int ncc_args(const MrgsWarpConfig* cfg, const MrgsWarpMaps* mp, float ncc_w, WarpArgs& a)
+{
+    const int rc = make_args(cfg, a);
+    if (rc) return rc;
+    if (!(ncc_w == ncc_w)) return MRGS_E_BAD_ARG;
+    if (mp && (!mp->cam_v || !mp->cam_n || !mp->normal_v || !mp->distance_v || !mp->metal_v || !mp->metal_n)) return MRGS_E_BAD_ARG;
+    return MRGS_OK;
+}
+
+}   // namespace
+
+extern "C" size_t mrgs_warp_ncc_ws_bytes(int32_t H, int32_t W, int32_t sample_num, int32_t patch_half)
+{
+    if (H <= 0 || W <= 0 || (int64_t)H * W >= ((int64_t)1 << 30) || sample_num <= 0 || patch_half < 1 || patch_half > 3) return 0;
+    return ncc_layout(H, W, sample_num, nullptr, nullptr);
+}
+
+extern "C" int mrgs_warp_ncc_forward(const MrgsWarpConfig* cfg, const MrgsWarpMaps* maps, const float* grey_v, const float* grey_n,
+                                     const float* weight_map, const void* warp_ws, size_t warp_ws_bytes, int32_t* samples, void* ws,
+                                     size_t ws_bytes, float ncc_weight, float* out_term, int32_t* out_counts, float* ref_weight_map,
+                                     float* out_ncc, uint8_t* out_use, void* stream)
+{
+    WarpArgs a;
+    if (!maps) return MRGS_E_BAD_ARG;
+    const int rc = ncc_args(cfg, maps, ncc_weight, a);
+    if (rc) return rc;
+    if (!grey_v || !grey_n || !weight_map || !warp_ws || !ws || !out_term || !out_counts || !ref_weight_map) return MRGS_E_BAD_ARG;
+    if (a.n_given > 0 && !(a.flags & MRGS_WARP_MATERIAL) && !samples) return MRGS_E_BAD_ARG;
+    if (warp_ws_bytes < ws_layout(a.H, a.W, a.k, nullptr, nullptr) || ws_bytes < ncc_layout(a.H, a.W, a.k, nullptr, nullptr))
+        return MRGS_E_WORKSPACE;
+    WarpWs w;
+    NccWs n;
+    ws_layout(a.H, a.W, a.k, &w, (char*)warp_ws);
+    ncc_layout(a.H, a.W, a.k, &n, (char*)ws);
+    hipStream_t st = (hipStream_t)stream;
+    const int HW = a.H * a.W;
+    if (hipMemcpyAsync(n.st, w.st, ST_WORDS * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return MRGS_E_HIP;
+    if (hipMemsetAsync(ref_weight_map, 0, (size_t)HW * 4, st) != hipSuccess) return MRGS_E_HIP;
+    NccIn in{maps->normal_v, maps->distance_v, maps->metal_v, maps->metal_n, grey_v, grey_n, maps->cam_v, maps->cam_n, weight_map,
+             w.samples, w.homog};
+    if (!(a.flags & MRGS_WARP_MATERIAL)) {
+        // the material call drew nothing: the same sampler on its valid map, into this workspace (equal seed and valid set: equal draw)
+        WarpWs d = w;
+        d.st = n.st; d.hist = n.hist; d.blk = n.blk; d.slot = n.slot; d.samples = n.samples;
+        const int rcd = draw_samples(a, d, samples, st);
+        if (rcd) return rcd;
+        in.samples = n.samples;
+        in.homog = nullptr;
+    }
+    const int ns_max = a.n_given >= 0 ? a.n_given : a.k;
+    if (ns_max > 0) warp_ncc_fwd<<<(ns_max + WB / 64 - 1) / (WB / 64), WB, 0, st>>>(a, in, n, ref_weight_map, out_ncc, out_use);
+    warp_ncc_finalize<<<1, FIN, 0, st>>>(n, ncc_weight, out_term, out_counts);
+    return hipGetLastError() == hipSuccess ? MRGS_OK : MRGS_E_HIP;
+}
+
+extern "C" int mrgs_warp_ncc_backward(const MrgsWarpConfig* cfg, const void* warp_ws, const void* ws, float ncc_weight, const float* g_term,
+                                      float* g_normal_v, float* g_distance_v, void* stream)
+{
+    WarpArgs a;
+    const int rc = ncc_args(cfg, nullptr, ncc_weight, a);
+    if (rc) return rc;
+    if (!warp_ws || !ws || !g_term) return MRGS_E_BAD_ARG;
+    if (!g_normal_v && !g_distance_v) return MRGS_OK;
+    WarpWs w;
+    NccWs n;
+    ws_layout(a.H, a.W, a.k, &w, (char*)warp_ws);
+    ncc_layout(a.H, a.W, a.k, &n, (char*)ws);
+    const int HW = a.H * a.W;
+    const int32_t* slot = (a.flags & MRGS_WARP_MATERIAL) ? w.slot : n.slot;
+    warp_ncc_bwd<<<(HW + WB - 1) / WB, WB, 0, (hipStream_t)stream>>>(HW, slot, n, ncc_weight, g_term, g_normal_v, g_distance_v);
     return hipGetLastError() == hipSuccess ? MRGS_OK : MRGS_E_HIP;
 }

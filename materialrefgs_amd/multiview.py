@@ -10,9 +10,10 @@ Differences a caller sees:
   * the edge mask comes from the caller's `edges_fn` (the reference's `dilated_edges_imgs`, cv2 Canny + dilation).
   * use_virtul_cam, ncc_scale != 1, wo_use_geo_occ_aware and (train_refreal.py) directional_rghmtl_warp_alignment = False raise
     NotImplementedError; all four are off by default.
-  * the grey-image NCC is not built.  train_refnerf.py / train_glossy.py compute it and never return it; train_refreal.py RETURNS it and
-    adds it to its loss from iteration 7000 (it trains rend_normal / rend_distance through the homography), so calc_warp_loss_refreal
-    refuses unless the caller passes without_ncc=True.
+  * the grey-image NCC (get_consistency_loss2) is a second autograd node, `_WarpNcc`, that follows the first on the same draw and
+    differentiates rend_normal / rend_distance of the view.  train_refnerf.py / train_glossy.py compute the term and never return it, so
+    calc_warp_loss leaves it out; calc_warp_loss_refreal returns it.  Where no sample is used the reference returns None, here the term is
+    0 with zero gradient; visual_refweight is a device map (the reference builds it on the CPU).
 """
 import ctypes
 import math
@@ -106,11 +107,11 @@ class _WarpLoss(torch.autograd.Function):
         ctx.cfg, ctx.maps = cfg, maps
         ctx.shapes = [None if t is None else t.shape for t in (depth_v, depth_n, base_v, metal_v, rough_v, base_n, metal_n, rough_n)]
         ctx.save_for_backward(ws, weight, samples, *keepers)
-        ctx.mark_non_differentiable(weight, counts)
-        return terms, weight, counts
+        ctx.mark_non_differentiable(weight, counts, ws)
+        return terms, weight, counts, ws              # ws: the draw and the homographies, for _WarpNcc
 
     @staticmethod
-    def backward(ctx, g_terms, _gw, _gc):
+    def backward(ctx, g_terms, _gw, _gc, _gws):
         nil = (None,) * 17
         if g_terms is None:
             return nil
@@ -135,22 +136,94 @@ class _WarpLoss(torch.autograd.Function):
         return tuple(grads) + (None,) * 9
 
 
+class _WarpNcc(torch.autograd.Function):
+    """The grey-image patch NCC of the view pair of a completed _WarpLoss (its weight map and workspace): term[1], the ref_weight map
+    [H,W], counts[2] (samples, used samples), per-sample ncc [sample_num] and use flag [sample_num] (empty unless `detail`).  Differentiable in rend_normal and
+    rend_distance of the view only."""
+
+    @staticmethod
+    def forward(ctx, normal_v, dist_v, grey_v, grey_n, metal_v, metal_n, weight, warp_ws, cam_v, cam_n, samples, out_samples, cfg, ncc_weight,
+                detail):
+        ctx.set_materialize_grads(False)
+        H, W = cfg.H, cfg.W
+        dev = weight.device
+        keepers = [_c(normal_v), _c(dist_v), _c(grey_v), _c(grey_n), _c(metal_v), _c(metal_n)]
+        maps = _lib.MrgsWarpMaps(normal_v=_p(keepers[0]), distance_v=_p(keepers[1]), metal_v=_p(keepers[4]), metal_n=_p(keepers[5]),
+                                 cam_v=_p(cam_v), cam_n=_p(cam_n))
+        lib = _lib.lib()
+        with _lib.guard(dev):
+            ws = torch.empty(lib.mrgs_warp_ncc_ws_bytes(H, W, cfg.sample_num, cfg.patch_half), dtype=torch.uint8, device=dev)
+            term = torch.empty(1, dtype=torch.float32, device=dev)
+            counts = torch.empty(2, dtype=torch.int32, device=dev)
+            refw = torch.empty((H, W), dtype=torch.float32, device=dev)
+            # per-sample outputs only where the caller asked for them (slots past the sample count stay 0)
+            ncc_s = torch.zeros(cfg.sample_num if detail else 0, dtype=torch.float32, device=dev)
+            use_s = torch.zeros(cfg.sample_num if detail else 0, dtype=torch.uint8, device=dev)
+            smp = samples if samples is not None else out_samples
+            _lib.check(lib.mrgs_warp_ncc_forward(ctypes.byref(cfg), ctypes.byref(maps), _p(keepers[2]), _p(keepers[3]), _p(weight), _p(warp_ws),
+                                                 warp_ws.numel(), _p(smp), _p(ws), ws.numel(), ncc_weight, _p(term), _p(counts), _p(refw),
+                                                 _p(ncc_s) if detail else None, _p(use_s) if detail else None, _lib.stream_ptr(dev)))
+        ctx.cfg, ctx.ncc_weight = cfg, ncc_weight
+        ctx.shapes = (normal_v.shape, dist_v.shape)
+        ctx.save_for_backward(warp_ws, ws)
+        ctx.mark_non_differentiable(refw, counts, ncc_s, use_s)
+        return term, refw, counts, ncc_s, use_s
+
+    @staticmethod
+    def backward(ctx, g_term, *_):
+        nil = (None,) * 15
+        if g_term is None:
+            return nil
+        warp_ws, ws = ctx.saved_tensors
+        cfg = ctx.cfg
+        dev = ws.device
+        H, W = cfg.H, cfg.W
+        need = ctx.needs_input_grad
+        gn = torch.empty((3, H, W), dtype=torch.float32, device=dev) if need[0] else None
+        gd = torch.empty((H, W), dtype=torch.float32, device=dev) if need[1] else None
+        gt = _c(g_term)
+        with _lib.guard(dev):
+            _lib.check(_lib.lib().mrgs_warp_ncc_backward(ctypes.byref(cfg), _p(warp_ws), _p(ws), ctx.ncc_weight, _p(gt), _p(gn), _p(gd),
+                                                         _lib.stream_ptr(dev)))
+        return (None if gn is None else gn.view(ctx.shapes[0]), None if gd is None else gd.view(ctx.shapes[1])) + (None,) * 13
+
+
+def _grey_image(cam):
+    """The camera's grey photograph as train_refreal.py reads it (get_image()[1], scene/cameras.py), or None if it carries none."""
+    if hasattr(cam, "get_image"):
+        return cam.get_image()[1]
+    g = getattr(cam, "original_image_gray", None)
+    if g is not None:
+        return g
+    img = getattr(cam, "original_image", None)
+    if img is None:
+        return None
+    return (0.299 * img[0] + 0.587 * img[1] + 0.114 * img[2])[None]          # scene/cameras.py:63
+
+
 def warp_consistency_loss(view_cam, view_pkg, nearest_cam, nearest_pkg, fg_mask, keep_mask=None, *, iteration, seed, samples=None,
                           out_samples=None, patch_size=3, sample_num=102400, pixel_noise_th=1.0, geo_weight=0.03, ncc_weight=0.15,
                           metallic_weight=0.05, roughness_weight=0.05, use_metallic_warp=True, use_roughness_warp=True, use_geo=True,
-                          schedule="refnerf"):
+                          schedule="refnerf", grey_v=None, grey_n=None, ncc_detail=None):
     """The multi-view consistency terms of view `view_cam` (render dictionary `view_pkg`, with "rend_distance") against
     `nearest_cam` / `nearest_pkg`.  Returns (geo, base_colour, metallic, roughness, weight_map, n_valid): 0-d device tensors for the
     terms (weights a(it) * multi_view_ncc_weight and b(it) * metallic / roughness weight applied; 0 where a term is switched off),
     the detached [H,W] weight map and n_valid as a 0-d int32 device tensor.  The material terms run when iteration > 10000.
     fg_mask: [H,W] foreground of the view; keep_mask: [H,W] bool, False on an edge (None: keep all).  `samples`: int32 pixel indices
     (y * W + x) to use instead of the device draw (tests replay a recorded draw); `out_samples`: int32 [sample_num] device tensor that
-    receives the draw.  No host read."""
+    receives the draw.  No host read.
+    grey_v / grey_n ([H,W] or [1,H,W] device tensors, both or neither): the grey photographs of the two cameras.  With them the call
+    returns two more values, (..., ncc, ref_weight_map): train_refreal.py's grey-image NCC term (get_consistency_loss2; weight
+    ncc_weight, no schedule, live at every iteration and differentiable in view_pkg["rend_normal"] / ["rend_distance"]) on the draw of
+    the material terms, and the detached [H,W] device map of visual_refweight.  `ncc_detail`: a dict that receives "ncc_s", "use_s"
+    (per sample, [sample_num]) and "counts" (samples, used samples) as device tensors."""
     depth_v, depth_n = view_pkg["surf_depth"], nearest_pkg["surf_depth"]
     if not depth_v.is_cuda:
         raise RuntimeError("materialrefgs_amd.multiview needs device tensors (libmrgs.so has no CPU path)")
     if "rend_distance" not in view_pkg:
         raise ValueError("warp_consistency_loss: view_pkg has no 'rend_distance' (render with the \"pgsr\" flavour; train_refnerf.py:568)")
+    if (grey_v is None) != (grey_n is None):
+        raise ValueError("warp_consistency_loss: pass both grey_v and grey_n, or neither")
     if patch_size not in (1, 2, 3):
         raise ValueError(f"warp_consistency_loss: patch_size {patch_size} is not 1, 2 or 3 (one 64-lane wave covers a patch)")
     if schedule not in ("refnerf", "refreal"):
@@ -189,11 +262,24 @@ def warp_consistency_loss(view_cam, view_pkg, nearest_cam, nearest_pkg, fg_mask,
     if fg is not None and fg.device != dev:
         fg = fg.to(dev, non_blocking=True)
     vp, npk = view_pkg, nearest_pkg
-    terms, weight, counts = _WarpLoss.apply(
+    cam_v, cam_n = _cam_record(view_cam, dev), _cam_record(nearest_cam, dev)
+    terms, weight, counts, ws = _WarpLoss.apply(
         depth_v.reshape(H, W), depth_n.reshape(H, W), vp["diffuse_map"], vp["refl_strength_map"], vp["roughness_map"], npk["diffuse_map"],
         npk["refl_strength_map"], npk["roughness_map"], vp["rend_normal"], vp["rend_distance"], fg, keep,
-        _cam_record(view_cam, dev), _cam_record(nearest_cam, dev), samples, out_samples, cfg)
-    return terms[0], terms[1], terms[2], terms[3], weight, counts[0]
+        cam_v, cam_n, samples, out_samples, cfg)
+    if grey_v is None:
+        return terms[0], terms[1], terms[2], terms[3], weight, counts[0]
+    greys = []
+    for g in (grey_v, grey_n):
+        if not g.is_cuda or g.numel() != H * W:
+            raise ValueError("warp_consistency_loss: grey_v / grey_n must be [H,W] or [1,H,W] device tensors")
+        greys.append(g.reshape(H, W))
+    ncc, refw, ncc_counts, ncc_s, use_s = _WarpNcc.apply(vp["rend_normal"], vp["rend_distance"], greys[0], greys[1], vp["refl_strength_map"],
+                                                         npk["refl_strength_map"], weight, ws, cam_v, cam_n, samples, out_samples, cfg,
+                                                         float(ncc_weight), ncc_detail is not None)
+    if ncc_detail is not None:
+        ncc_detail.update(ncc_s=ncc_s, use_s=use_s, counts=ncc_counts)
+    return terms[0], terms[1], terms[2], terms[3], weight, counts[0], ncc[0], refw
 
 
 def _check_opt(viewpoint_cam, opt, refreal):
@@ -208,7 +294,7 @@ def _check_opt(viewpoint_cam, opt, refreal):
 
 
 def _drop_in(viewpoint_cam, scene, opt, gaussians, pipe, render, render_pkg, mask_images, iteration, bg, use_metallic_warp,
-             use_roughness_warp, edges_fn, refreal, samples):
+             use_roughness_warp, edges_fn, refreal, samples, grey_v=None):
     _check_opt(viewpoint_cam, opt, refreal)
     if not render_pkg["surf_depth"].is_cuda:
         raise RuntimeError("materialrefgs_amd.multiview needs device tensors (libmrgs.so has no CPU path)")
@@ -223,19 +309,27 @@ def _drop_in(viewpoint_cam, scene, opt, gaussians, pipe, render, render_pkg, mas
         return None
     nearest_cam = scene.getTrainCameras()[random.sample(viewpoint_cam.nearest_id, 1)[0]]
     nearest_pkg = render(nearest_cam, gaussians, pipe, bg, srgb=opt.srgb, opt=opt, wo_render_img=False)
+    grey = {}
+    if grey_v is not None:
+        grey_n = _grey_image(nearest_cam)
+        if grey_n is None:
+            raise NotImplementedError("calc_warp_loss_refreal: the neighbour camera carries no image for the grey-image NCC term; pass "
+                                      "without_ncc=True to train without it (INTEGRATION.md section 4h)")
+        dev = render_pkg["surf_depth"].device
+        grey = dict(grey_v=torch.as_tensor(grey_v).to(dev, non_blocking=True), grey_n=torch.as_tensor(grey_n).to(dev, non_blocking=True))
     seed = int(np.random.randint(0, 2 ** 62, dtype=np.int64))
     if iteration > 10000:
         opt.directional_rghmtl_warp_alignment = True      # train_refnerf.py:648 (the assignment sits in the material branch)
     fg = torch.as_tensor(mask_images[viewpoint_cam.image_name]) if iteration > 10000 else None
-    geo, base, metal, rough, weight, _n = warp_consistency_loss(
+    geo, base, metal, rough, weight, _n, *ncc = warp_consistency_loss(
         viewpoint_cam, render_pkg, nearest_cam, nearest_pkg, fg, keep, iteration=iteration, seed=seed,
         patch_size=opt.multi_view_patch_size, sample_num=opt.multi_view_sample_num, pixel_noise_th=opt.multi_view_pixel_noise_th,
         samples=samples, geo_weight=opt.multi_view_geo_weight, ncc_weight=opt.multi_view_ncc_weight, metallic_weight=opt.metallic_warp_weight,
         roughness_weight=opt.roughness_warp_weight, use_metallic_warp=use_metallic_warp, use_roughness_warp=use_roughness_warp,
-        use_geo=refreal, schedule="refreal" if refreal else "refnerf")
+        use_geo=refreal, schedule="refreal" if refreal else "refnerf", **grey)
     material = iteration > 10000
     return (geo if refreal else None, base if material else None, metal if (material and use_metallic_warp) else None,
-            rough if (material and use_roughness_warp) else None, weight)
+            rough if (material and use_roughness_warp) else None, weight, *ncc)
 
 
 def calc_warp_loss(viewpoint_cam, scene, opt, gaussians, dataset, pipe, render, render_pkg, albeldo_images, mtl_images, rgh_images, mask_images,
@@ -254,18 +348,27 @@ def calc_warp_loss(viewpoint_cam, scene, opt, gaussians, dataset, pipe, render, 
 def calc_warp_loss_refreal(viewpoint_cam, scene, opt, gaussians, dataset, pipe, render, render_pkg, albeldo_images, mtl_images, rgh_images,
                            mask_images, iteration, debug_path, bg, use_metallic_warp=False, use_roughness_warp=False, *, edges_fn=None,
                            without_ncc=False, samples=None):
-    """train_refreal.py:405-729: (geo_loss, None, base_color_loss, metallic_warp_loss, roughness_warp_loss, original_weight,
-    visual_refweight, None).  train_refreal.py ALSO returns a grey-image NCC term (get_consistency_loss2, :707, :729) that its training
-    loop adds to the loss from iteration 7000 (:1227-1228) and whose homography trains rend_normal and rend_distance.  That term is not
-    built: this drop-in raises NotImplementedError unless the caller passes without_ncc=True, accepting that the term leaves the
-    loss; `ncc_loss` is then None and visual_refweight a CPU H x W map of zeros."""
+    """train_refreal.py:405-729: (geo_loss, ncc_loss, base_color_loss, metallic_warp_loss, roughness_warp_loss, original_weight,
+    visual_refweight, None).  ncc_loss is the grey-image NCC term (get_consistency_loss2, :707) that the training loop adds to its loss
+    (:1227-1228) and whose homography trains rend_normal and rend_distance; the grey images are the cameras' own (get_image()[1], else
+    original_image_gray, else the luminance of original_image).  Differences: where no sample is used ncc_loss is 0 with zero gradient
+    (None in the reference), and visual_refweight is a DEVICE H x W tensor (the reference builds it on the CPU, which costs a
+    synchronisation).  A camera without an image raises NotImplementedError;
+    without_ncc=True leaves the term out: ncc_loss is then None and visual_refweight a CPU H x W map of zeros."""
+    grey_v = None
     if not without_ncc:
-        raise NotImplementedError("calc_warp_loss_refreal: train_refreal.py adds the grey-image NCC term (get_consistency_loss2) to its "
-                                  "loss and it is not built; pass without_ncc=True to train without it (INTEGRATION.md section 4h)")
+        grey_v = _grey_image(viewpoint_cam)
+        if grey_v is None:
+            raise NotImplementedError("calc_warp_loss_refreal: the camera carries no image for the grey-image NCC term "
+                                      "(get_consistency_loss2); pass without_ncc=True to train without it (INTEGRATION.md section 4h)")
     r = _drop_in(viewpoint_cam, scene, opt, gaussians, pipe, render, render_pkg, mask_images, iteration, bg, use_metallic_warp,
-                 use_roughness_warp, edges_fn, True, samples)
+                 use_roughness_warp, edges_fn, True, samples, grey_v)
     H, W = render_pkg["surf_depth"].shape[-2:]
+    zeros = torch.zeros(H, W) if without_ncc else torch.zeros(H, W, device=render_pkg["surf_depth"].device)
     if r is None:
-        return None, None, None, None, None, None, torch.zeros(H, W), None
-    geo, base, metal, rough, weight = r
-    return geo, None, base, metal, rough, weight, torch.zeros(H, W), None
+        return None, None, None, None, None, None, zeros, None
+    if without_ncc:
+        geo, base, metal, rough, weight = r
+        return geo, None, base, metal, rough, weight, zeros, None
+    geo, base, metal, rough, weight, ncc, refw = r
+    return geo, ncc, base, metal, rough, weight, refw, None
