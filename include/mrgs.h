@@ -281,16 +281,10 @@ int mrgs_shade_specular_forward_composite(const MrgsEnvMips* mips, const MrgsSha
 int mrgs_shade_specular_backward(const MrgsEnvMips* mips, const MrgsShadeFrame* frame, const float* g_specular, const float* g_direct_light,
                                  const float* g_specular_weight, float* g_albedo, float* g_normal, float* g_alpha, float* g_refl,
                                  float* g_roughness, void* stream);
-/* The same backward as render_surfel needs it (ABI 6): the per-pixel gradients leave as the gradient of the rasterizer's [8,H,W]
- * feature map -- g_features = (g_refl + g_refl_composite, g_roughness, g_albedo[3], 0, 0, 0), channel-major, fully written -- and as
- * the TOTAL alpha gradient g_alpha[H,W] = g_alpha_composite + this kernel's, with mrgs_surfel_composite_backward's g_refl / g_alpha
- * as the two inputs (what mrgs_surfel_feature_grads assembles from five maps in a launch of its own).  g_normal[H,W,3] as above. */
-int mrgs_shade_specular_backward_features(const MrgsEnvMips* mips, const MrgsShadeFrame* frame, const float* g_specular,
-                                          const float* g_direct_light, const float* g_specular_weight, const float* g_refl_composite,
-                                          const float* g_alpha_composite, float* g_normal, float* g_features, float* g_alpha, void* stream);
 /* render_surfel's compositing backward AND the shading backward in ONE launch (ABI 9; gaussian_renderer/__init__.py:436-445 then
- * utils/refl_utils.py:364-419 backwards): what mrgs_surfel_composite_backward followed by mrgs_shade_specular_backward_features computes, with
- * the compositing's g_specular / g_refl / g_alpha shares kept in the pixel's registers.  g_render / g_diffuse [3,H,W]: upstream gradients
+ * utils/refl_utils.py:364-419 backwards): what mrgs_surfel_composite_backward followed by mrgs_shade_specular_backward computes, with
+ * the compositing's g_specular / g_refl / g_alpha shares kept in the pixel's registers and the per-pixel gradients leaving as the
+ * gradient of the rasterizer's [8,H,W] feature map: g_features = (g_refl, g_roughness, g_albedo[3], 0, 0, 0), channel-major.  g_render / g_diffuse [3,H,W]: upstream gradients
  * of the two composited maps (either may be NULL); g_specular_extra [3,H,W]: an upstream gradient of the specular map itself (NULL =
  * none); base_color, specular [3,H,W]: the forward's inputs / output; bg[3].  Outputs, fully written: g_base[3,H,W], g_normal[H,W,3],
  * g_features[8,H,W], g_alpha[H,W] (total).  The texel gradients are accumulated into mips->grad, which must be zero on entry
@@ -783,33 +777,11 @@ int mrgs_get_kernel_times(MrgsKernelTimes* out);
 const char* mrgs_strerror(int code);
 const char* mrgs_last_hip_error(void);
 const char* mrgs_version(void);
-/* A second stream beside the caller's, for work that depends on nothing the caller's stream will produce for a while (the environment
- * prefilter of a view: six latency-bound SpMVs and the mip chain, which only the shading reads -- next to the issue-bound blend kernels;
- * scene/light.py:72-86 is called once per iteration, train_refnerf.py:1157-1163).  The library keeps ONE side stream per
- * device (any host thread may fork or join).  fork: everything queued on `main_stream` so far happens-before whatever is queued on the returned stream afterwards (pass it
- * as the `stream` of the calls to overlap); join: everything queued on the side stream so far happens-before whatever is queued on
- * `main_stream` afterwards.  Two event records and two stream waits, no host synchronisation.  Buffers the side work reads or writes
- * must stay allocated until the join has been queued (a caching allocator would hand them to the main stream's next kernels otherwise).
- * ABI 7. */
-int mrgs_side_stream_fork(void* main_stream, void** side_stream);
-int mrgs_side_stream_join(void* main_stream);
-/* fork from the point of `main_stream` where a rasterizer forward launched its blend kernel: what is queued on the side stream then runs
- * beside the forward blend -- whose duration is the lifetime of a few long waves and which leaves issue slots and memory bandwidth idle --
- * instead of beside the bandwidth-bound kernels in front of it.  The point is a ONE-SHOT mark (ABI 9):
- *   mrgs_side_stream_arm_blend_mark(main_stream)   the caller owes side work and wants it forked from the NEXT forward's blend on this
- *                                                  stream; forgets any older mark.  Call it where the side work's inputs are final and
- *                                                  its buffers are allocated (EnvLight.build_mips does, after the optimizer step);
- *   the next mrgs_rasterize_forward* on that stream records the mark in front of its blend kernel;
- *   mrgs_side_stream_fork_at_blend(main_stream, &side) consumes it.  Without a mark recorded on `main_stream` since the arming (no forward
- *                                                  came, or it ran on another stream) this is a plain fork; a join drops an unconsumed mark.
- * Contract of the caller: every buffer the side work reads or writes was allocated BEFORE the arming call (a caching allocator may hand
- * out, after the forward, memory whose last reader is the very blend kernel the side work runs beside), and the side work's inputs are not
- * written on `main_stream` between the arming and the join. */
-int mrgs_side_stream_arm_blend_mark(void* main_stream);
-int mrgs_side_stream_fork_at_blend(void* main_stream, void** side_stream);
 
 /* Revision of this header's struct layouts and call signatures; a binding compares it with the MRGS_ABI_VERSION it was written
- * against before the first call (materialrefgs_amd/_lib.py does). */
+ * against before the first call (materialrefgs_amd/_lib.py does).  Entry points that come or go do not move it: revision 10 has lost
+ * the four side-stream calls and the feature-map form of the shading backward, and a binding that still names one of them fails at
+ * symbol lookup. */
 #define MRGS_ABI_VERSION 10
 int32_t mrgs_abi_version(void);
 

@@ -225,10 +225,6 @@ SYMBOLS = {
                                                   c_void_p, c_void_p]),
     "mrgs_sh_grad_expand_surfel_rows": (ctypes.c_int, [c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
                                                        c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "mrgs_side_stream_fork": (ctypes.c_int, [c_void_p, ctypes.POINTER(c_void_p)]),
-    "mrgs_side_stream_join": (ctypes.c_int, [c_void_p]),
-    "mrgs_side_stream_fork_at_blend": (ctypes.c_int, [c_void_p, ctypes.POINTER(c_void_p)]),
-    "mrgs_side_stream_arm_blend_mark": (ctypes.c_int, [c_void_p]),
     "mrgs_compact_ws_bytes": (c_size_t, [c_int64]),
     "mrgs_compact_count": (ctypes.c_int, [c_int64, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
     "mrgs_compact_rows": (ctypes.c_int, [c_int64, c_void_p, c_void_p, ctypes.POINTER(MrgsCompactTensor), c_int32, c_void_p]),
@@ -242,8 +238,6 @@ SYMBOLS = {
                                                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "mrgs_shade_specular_backward": (ctypes.c_int, [ctypes.POINTER(MrgsEnvMips), ctypes.POINTER(MrgsShadeFrame), c_void_p, c_void_p,
                                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "mrgs_shade_specular_backward_features": (ctypes.c_int, [ctypes.POINTER(MrgsEnvMips), ctypes.POINTER(MrgsShadeFrame), c_void_p, c_void_p,
-                                                             c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "mrgs_surfel_shade_composite_backward": (ctypes.c_int, [ctypes.POINTER(MrgsEnvMips), ctypes.POINTER(MrgsShadeFrame), c_int32] + [c_void_p] * 13),
     "mrgs_debug_export": (ctypes.c_int, [ctypes.POINTER(MrgsRasterConfig), c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p,
                                          c_void_p]),

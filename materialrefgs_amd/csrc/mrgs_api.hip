@@ -215,8 +215,6 @@ MrgsHintLayout mrgs_hint_layout(int H, int W)
     return l;
 }
 // with a per-camera hint buffer the blend kernels' queue state and the forward's dealt queues live in it (see MrgsHintLayout)
-static void side_mark_pre_blend(hipStream_t stream);     // (side stream, below) an event in front of the forward blend, when somebody forks from there
-
 static void img_use_hint(MrgsImgWs& img, const MrgsRasterInputs* in, int H, int W)
 {
     if (in->work_hint == nullptr) return;
@@ -304,7 +302,6 @@ static int enqueue_render(const MrgsRasterConfig* cfg, const MrgsRasterInputs* i
     t0.stop();
     STAGE_CHECK(cfg, stream);
 
-    side_mark_pre_blend(stream);
     StageTimer t1(stream, ST_FWD);
     mrgs_launch_render_fwd(*cfg, *in, g, b.plist[cur], b.qmask, b.cflag, img, out_color, out_feature, out_others, stream);
     t1.stop();
@@ -651,116 +648,6 @@ int mrgs_get_kernel_times(MrgsKernelTimes* out)
     float* dst[ST_COUNT] = {&out->preprocess_ms, &out->sort_ms, &out->duplicate_ms, &out->render_fwd_ms, &out->render_bwd_ms,
                             &out->preprocess_bwd_ms};
     for (int i = 0; i < ST_COUNT; i++) *dst[i] = cnt[i] ? (float)(sum[i] / cnt[i]) : 0.0f;
-    return MRGS_OK;
-}
-
-// ---- a second stream next to the caller's (mrgs.h: mrgs_side_stream_fork / _join) ---------------------------------------------------
-// One non-blocking side stream per device (shared by the host threads: a backward may fork on autograd's worker thread and be joined from
-// the thread that called backward()) and a ring of events without timing, created on first use and kept.  fork: the side stream waits
-// for what the caller's stream holds NOW; join: the caller's stream waits for what the side stream holds now.
-namespace {
-#define MRGS_SIDE_EVENTS 32
-struct SideStream {
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[MRGS_SIDE_EVENTS] = {};
-    unsigned next = 0;
-    hipEvent_t pre_blend = nullptr;     // recorded on the rasterizer's stream right before its forward blend (once somebody has asked for it)
-    // The mark is ONE-SHOT: armed by mrgs_side_stream_arm_blend_mark (whoever owes side work says so BEFORE the forward it wants to fork
-    // from), recorded by the next forward on `armed_on`, consumed by the first fork_at_blend, dropped by a join.  A mark of an earlier
-    // iteration can therefore never order side work (it would not cover what the caller's stream did since, e.g. an optimizer step).
-    bool want_pre_blend = false, have_pre_blend = false;
-    hipStream_t armed_on = nullptr, marked_on = nullptr;
-};
-SideStream g_side[MRGS_MAX_DEVICES];
-std::mutex g_side_mutex;
-static int side_of(SideStream** out)
-{
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    if (dev < 0 || dev >= MRGS_MAX_DEVICES) return MRGS_E_UNSUPPORTED;
-    SideStream& s = g_side[dev];
-    if (s.stream == nullptr) {
-        // LOWEST priority: the side work is filler -- the dispatcher hands a free wave slot to the caller's stream first, and what runs
-        // on the side stream takes what is left (the lone-wave tails of the blend kernels)
-        int least = 0, greatest = 0;
-        HIP_TRY(hipDeviceGetStreamPriorityRange(&least, &greatest));
-        HIP_TRY(hipStreamCreateWithPriority(&s.stream, hipStreamNonBlocking, least));
-        for (int i = 0; i < MRGS_SIDE_EVENTS; i++) HIP_TRY(hipEventCreateWithFlags(&s.ev[i], hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&s.pre_blend, hipEventDisableTiming));
-    }
-    *out = &s;
-    return MRGS_OK;
-}
-}   // namespace
-
-static void side_mark_pre_blend(hipStream_t stream)
-{
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MRGS_MAX_DEVICES) return;
-    std::lock_guard<std::mutex> lk(g_side_mutex);
-    SideStream& s = g_side[dev];
-    if (!s.want_pre_blend || s.pre_blend == nullptr || stream != s.armed_on) return;
-    s.have_pre_blend = hipEventRecord(s.pre_blend, stream) == hipSuccess;
-    s.marked_on = stream;
-    s.want_pre_blend = false;                    // the first forward after the arming is the one meant
-}
-
-int mrgs_side_stream_arm_blend_mark(void* main_stream)
-{
-    std::lock_guard<std::mutex> lk(g_side_mutex);
-    SideStream* s = nullptr;
-    int rc = side_of(&s);
-    if (rc) return rc;
-    s->want_pre_blend = true;
-    s->have_pre_blend = false;                   // whatever an earlier forward marked is history
-    s->armed_on = (hipStream_t)main_stream;
-    return MRGS_OK;
-}
-
-int mrgs_side_stream_fork_at_blend(void* main_stream, void** side_stream)
-{
-    if (!side_stream) return MRGS_E_BAD_ARG;
-    std::lock_guard<std::mutex> lk(g_side_mutex);
-    SideStream* s = nullptr;
-    int rc = side_of(&s);
-    if (rc) return rc;
-    if (s->have_pre_blend && s->marked_on == (hipStream_t)main_stream) {
-        s->have_pre_blend = false;               // consumed: a second fork without a new arming + forward takes the plain path
-        HIP_TRY(hipStreamWaitEvent(s->stream, s->pre_blend, 0));
-    } else {                                     // no forward on this stream has marked the point since the arming: everything the caller's stream holds
-        s->have_pre_blend = false;
-        hipEvent_t e = s->ev[s->next++ % MRGS_SIDE_EVENTS];
-        HIP_TRY(hipEventRecord(e, (hipStream_t)main_stream));
-        HIP_TRY(hipStreamWaitEvent(s->stream, e, 0));
-    }
-    *side_stream = (void*)s->stream;
-    return MRGS_OK;
-}
-
-int mrgs_side_stream_fork(void* main_stream, void** side_stream)
-{
-    if (!side_stream) return MRGS_E_BAD_ARG;
-    std::lock_guard<std::mutex> lk(g_side_mutex);
-    SideStream* s = nullptr;
-    int rc = side_of(&s);
-    if (rc) return rc;
-    hipEvent_t e = s->ev[s->next++ % MRGS_SIDE_EVENTS];
-    HIP_TRY(hipEventRecord(e, (hipStream_t)main_stream));
-    HIP_TRY(hipStreamWaitEvent(s->stream, e, 0));
-    *side_stream = (void*)s->stream;
-    return MRGS_OK;
-}
-
-int mrgs_side_stream_join(void* main_stream)
-{
-    std::lock_guard<std::mutex> lk(g_side_mutex);
-    SideStream* s = nullptr;
-    int rc = side_of(&s);
-    if (rc) return rc;
-    hipEvent_t e = s->ev[s->next++ % MRGS_SIDE_EVENTS];
-    HIP_TRY(hipEventRecord(e, s->stream));
-    HIP_TRY(hipStreamWaitEvent((hipStream_t)main_stream, e, 0));
-    s->have_pre_blend = false;                   // a mark older than a join is stale
     return MRGS_OK;
 }
 

@@ -705,7 +705,7 @@ __global__ void __launch_bounds__(MRGS_SHADE_FUSED_THREADS) shade_fused_bwd_kern
                 g_refl_c -= b * gd;
                 gs_[c] += gl;
             }
-        } else if (g_features != nullptr) {
+        } else if (g_features != nullptr) {     // unreachable: no entry point launches the <false> instance with g_features any more
             g_refl_c = g_refl_composite[pix];
             g_alpha_c = g_alpha_composite[pix];
         }
@@ -1391,15 +1391,14 @@ struct ShadeCompositeArgs { int srgb; const float *base, *spec_fwd, *bg, *g_rend
 
 static int shade_specular_backward_impl(const MrgsEnvMips* mips, const MrgsShadeFrame* fr, const float* g_specular, const float* g_direct_light,
                                         const float* g_specular_weight, float* g_albedo, float* g_normal, float* g_alpha, float* g_refl,
-                                        float* g_roughness, float* g_features, const float* g_refl_composite, const float* g_alpha_composite,
-                                        const ShadeCompositeArgs* composite, void* stream)
+                                        float* g_roughness, float* g_features, const ShadeCompositeArgs* composite, void* stream)
 {
     EnvMips m;
     int rc = make_mips(mips, m);
     if (rc) return rc;
     if (!fr || fr->H <= 0 || fr->W <= 0 || !fr->R || !fr->T || !fr->lut || !g_normal || !g_alpha) return MRGS_E_BAD_ARG;
     if (composite ? (!g_features || !composite->base || !composite->spec_fwd || !composite->bg || !composite->g_base)
-                  : (g_features ? (!g_refl_composite || !g_alpha_composite) : (!g_albedo || !g_refl || !g_roughness))) return MRGS_E_BAD_ARG;
+                  : (!g_albedo || !g_refl || !g_roughness)) return MRGS_E_BAD_ARG;
     // the scatter keys pack (level << 24 | texel index): a level with 6 res^2 >= 2^24 texels (res >= 1673) would alias into the level bits
     for (int l = 0; l < m.n; l++)
         if (m.grad[l] != nullptr && 6ll * m.res[l] * m.res[l] >= (1ll << 24)) return MRGS_E_UNSUPPORTED;
@@ -1426,12 +1425,12 @@ static int shade_specular_backward_impl(const MrgsEnvMips* mips, const MrgsShade
     if (composite)
         hipLaunchKernelGGL((shade_fused_bwd_kernel<true>), grid, block, 0, (hipStream_t)stream, m, cam, fr->H, fr->W, to_map(fr->albedo), to_map(fr->normal),
                            to_map(fr->alpha), to_map(fr->refl), to_map(fr->roughness), fr->lut, fr->lut_res, g_specular, g_direct_light, g_specular_weight,
-                           g_albedo, g_normal, g_alpha, g_refl, g_roughness, tiles_x, ntiles, lds_floats, g_features, g_refl_composite, g_alpha_composite,
+                           g_albedo, g_normal, g_alpha, g_refl, g_roughness, tiles_x, ntiles, lds_floats, g_features, (const float*)nullptr, (const float*)nullptr,
                            composite->srgb, composite->base, composite->spec_fwd, composite->bg, composite->g_render, composite->g_diffuse, composite->g_base);
     else
         hipLaunchKernelGGL((shade_fused_bwd_kernel<false>), grid, block, 0, (hipStream_t)stream, m, cam, fr->H, fr->W, to_map(fr->albedo), to_map(fr->normal),
                            to_map(fr->alpha), to_map(fr->refl), to_map(fr->roughness), fr->lut, fr->lut_res, g_specular, g_direct_light, g_specular_weight,
-                           g_albedo, g_normal, g_alpha, g_refl, g_roughness, tiles_x, ntiles, lds_floats, g_features, g_refl_composite, g_alpha_composite,
+                           g_albedo, g_normal, g_alpha, g_refl, g_roughness, tiles_x, ntiles, lds_floats, g_features, (const float*)nullptr, (const float*)nullptr,
                            0, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (float*)nullptr);
     return hipGetLastError() == hipSuccess ? MRGS_OK : MRGS_E_HIP;
 }
@@ -1441,16 +1440,7 @@ int mrgs_shade_specular_backward(const MrgsEnvMips* mips, const MrgsShadeFrame* 
                                  float* g_roughness, void* stream)
 {
     return shade_specular_backward_impl(mips, fr, g_specular, g_direct_light, g_specular_weight, g_albedo, g_normal, g_alpha, g_refl, g_roughness,
-                                        nullptr, nullptr, nullptr, nullptr, stream);
-}
-
-int mrgs_shade_specular_backward_features(const MrgsEnvMips* mips, const MrgsShadeFrame* fr, const float* g_specular, const float* g_direct_light,
-                                          const float* g_specular_weight, const float* g_refl_composite, const float* g_alpha_composite,
-                                          float* g_normal, float* g_features, float* g_alpha, void* stream)
-{
-    if (!g_features) return MRGS_E_BAD_ARG;
-    return shade_specular_backward_impl(mips, fr, g_specular, g_direct_light, g_specular_weight, nullptr, g_normal, g_alpha, nullptr, nullptr,
-                                        g_features, g_refl_composite, g_alpha_composite, nullptr, stream);
+                                        nullptr, nullptr, stream);
 }
 
 int mrgs_surfel_shade_composite_backward(const MrgsEnvMips* mips, const MrgsShadeFrame* fr, int32_t srgb, const float* base_color, const float* specular,
@@ -1461,7 +1451,7 @@ int mrgs_surfel_shade_composite_backward(const MrgsEnvMips* mips, const MrgsShad
     if (!g_features) return MRGS_E_BAD_ARG;
     const ShadeCompositeArgs ca = {srgb, base_color, specular, bg, g_render, g_diffuse, g_base};
     return shade_specular_backward_impl(mips, fr, g_specular_extra, g_direct_light, g_specular_weight, nullptr, g_normal, g_alpha, nullptr, nullptr,
-                                        g_features, nullptr, nullptr, &ca, stream);
+                                        g_features, &ca, stream);
 }
 
 int mrgs_cubemap_filter_count(int32_t res, int32_t kind, float roughness, float cos_cutoff, uint32_t* row_count, float* row_wsum, void* stream)

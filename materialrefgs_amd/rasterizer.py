@@ -201,10 +201,6 @@ def _camera_f32c(t):
     return c
 
 
-def _stream(device):
-    return _lib.stream_ptr(device)
-
-
 _RESOLVE = object()
 # MrgsRasterInputs::features_live of the render being issued on this thread (GaussianRasterizer.features_live: the settings tuple keeps
 # the reference's fields); the autograd node notes it for its backward
@@ -360,7 +356,7 @@ def _rasterize_forward_native(raster_settings, means3D, sh, colors_precomp, feat
                                       sh_rest, grad_ws, extra_flags=_lib.MRGS_HINT_VISIBLE_BYTES)
     P, S = cfg.P, cfg.S
     with _lib.guard(dev):
-        st = _stream(dev)
+        st = _lib.stream_ptr(dev)
         contrib = _zero_contrib(dev, H, W)   # allocated, never written
         color = torch.empty((3, H, W), dtype=torch.float32, device=dev)
         feature = torch.empty((S, H, W), dtype=torch.float32, device=dev)
@@ -441,7 +437,7 @@ def _rasterize_backward_native(raster_settings, means3D, radii, colors_precomp, 
                                    sh_rest, prepared_grad_ws, work_hint)
     P, S, M = cfg.P, cfg.S, cfg.M
     with _lib.guard(dev):
-        st = _stream(dev)
+        st = _lib.stream_ptr(dev)
         opts = dict(dtype=torch.float32, device=dev)
         fused = glue is not None and P > 0
         keep = (lambda name, shape: None) if fused else (lambda name, shape: torch.empty(shape, **opts))    # what the glue epilogue replaces
@@ -606,7 +602,7 @@ class GaussianRasterizer(nn.Module):
             present = torch.zeros((P,), dtype=torch.uint8, device=positions.device)
             with _lib.guard(positions.device):
                 _lib.check(_lib.lib().mrgs_mark_visible(P, _ptr(positions), _ptr(_f32c(rs.viewmatrix)), _ptr(_f32c(rs.projmatrix)),
-                                                        _ptr(present), _stream(positions.device)))
+                                                        _ptr(present), _lib.stream_ptr(positions.device)))
             visible = present.bool()
         return visible
 

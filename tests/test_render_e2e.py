@@ -308,31 +308,44 @@ def test_glue_epilogue_launches_no_glue_backward_kernel(gpu_device, monkeypatch)
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("grad_mode", [True, False])
-def test_lazy_prefilter_on_the_side_stream_equals_the_plain_path(gpu_device, grad_mode):
-    """EnvLight.overlap_prefilter (MRGS_SIDE_STREAM=1): the prefilter launched lazily on the library's side stream, forked from the point
-    where the rasterizer's forward launched its blend kernel (mrgs_side_stream_arm_blend_mark / _fork_at_blend), over several iterations
-    with an in-place write of the texels between them (what the optimizer step does) -- images, levels and gradients bit-equal to the
-    plain path.  Under no_grad the rasterizer frees its scratch on return while the blend still reads it: the side work's buffers were
-    allocated before that forward (EnvLight.build_mips), so nothing it writes can be that memory.  Also: a lazy read with NO forward
-    since build_mips (env(dirs) alone) takes the plain fork -- it must see the texels the 'optimizer' just wrote."""
+def test_build_mips_rebuilds_after_a_texel_write_and_skips_without_one(gpu_device, grad_mode):
+    """A long-lived EnvLight that goes through build_mips() every iteration, with an in-place write of the texels between them (what the
+    optimizer step does), against an EnvLight constructed afresh from a copy of the same texels in each iteration: images and levels
+    bit-equal, gradients equal to rounding.  build_mips() runs under the grad mode of the render, so without gradients its "nothing to
+    rebuild" stamp is on the path: it must never serve levels of texels that have since been written, and a second call with nothing
+    written in between must leave the very same tensors in place.  Also: a look-up with NO forward since build_mips (env(dirs) alone)
+    must see the texels the 'optimizer' just wrote."""
     from materialrefgs_amd.renderer import render_surfel
+    from materialrefgs_amd.shading import EnvLight
     dev = gpu_device
     P, H, W = 20000, 256, 256
     pipe = SimpleNamespace(depth_ratio=0.0, debug=False)
     bg = torch.tensor([0.1, 0.2, 0.3], device=dev)
     cam = orbit_camera(1, H, W).to(dev)
     results = {}
-    for overlap in (False, True):
+    for fresh in (False, True):
         _, _, pc_h, env = _models(P, H, W, seed=4, dev=dev, env_res=128, env_min=16)
-        env.overlap_prefilter = overlap
+        texels = env.base.detach().clone()
         rows = []
         g = torch.Generator().manual_seed(7)
         for it in range(4):
-            with torch.no_grad():
-                env.base.add_(0.05 * torch.randn(env.base.shape, generator=g).to(dev))      # the optimizer step
+            step = 0.05 * torch.randn(env.base.shape, generator=g).to(dev)
+            if fresh:
+                texels.add_(step)
+                env = pc_h.env_map = EnvLight(device=dev, min_res=16, max_res=128, trainable=True)
+                with torch.no_grad():
+                    env.base.copy_(texels)
+            else:
+                with torch.no_grad():
+                    env.base.add_(step)                                                     # the optimizer step
             for t_ in pc_h.parameters() + [env.base]:
                 t_.grad = None
-            env.build_mips()
+            with torch.set_grad_enabled(grad_mode):
+                env.build_mips()
+                if not grad_mode:
+                    built = list(env.specular)
+                    env.build_mips()                                                        # nothing written since: nothing rebuilt
+                    assert len(env.specular) == len(built) and all(a is b for a, b in zip(env.specular, built)), it
             if it == 2:
                 # no rasterizer forward between build_mips and the first look at the levels
                 d = torch.nn.functional.normalize(torch.randn(4096, 3, generator=g), dim=1).to(dev)
@@ -341,14 +354,12 @@ def test_lazy_prefilter_on_the_side_stream_equals_the_plain_path(gpu_device, gra
                 rows.append(("fwd", look.detach().clone()))
             with torch.set_grad_enabled(grad_mode):
                 out = render_surfel(cam, pc_h, pipe, bg, srgb=False, opt=SimpleNamespace(indirect=False))
-                junk = [torch.full((1 << 20,), float(it), device=dev) for _ in range(8)]     # allocations right behind the render: candidates for freed scratch
             rows += [("fwd", t_.detach().clone()) for t_ in [out["render"], out["specular_map"]] + list(env.specular)]
             if grad_mode:
                 (out["render"].sum() + out["specular_map"].sum() * 0.5).backward()
                 rows += [("grad", env.base.grad.clone()), ("grad", pc_h._roughness.grad.clone())]
-            del junk
         torch.cuda.synchronize(dev)
-        results[overlap] = rows
+        results[fresh] = rows
     assert len(results[False]) == len(results[True])
     for i, ((kind, a), (_, b)) in enumerate(zip(results[False], results[True])):
         assert torch.isfinite(a).all()
