@@ -317,6 +317,12 @@ def f32c(t):
     return t.detach().to(torch.float32).contiguous()
 
 
+def ptr(t):
+    """Address of a tensor's data as an int, None (NULL) for None: ctypes converts either for the `void*` parameters and struct fields.
+    (An empty tensor's address 0 is NULL as well.)"""
+    return None if t is None else t.data_ptr()
+
+
 def check(rc):
     if rc != 0:
         L = lib()

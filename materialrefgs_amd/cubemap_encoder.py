@@ -4,16 +4,15 @@ arguments, parameter names and shapes ([6,C,L,L] textures, [C] fail value), outp
 [B,levels*C] of the modules.  The native side is libmrgs.so (mrgs_cubemap_encode_forward / _backward, include/mrgs.h); CPU tensors
 are rejected -- there is no fallback.
 """
-import ctypes
-
 import numpy as np
 import torch
 import torch.nn as nn
 
 from . import _lib
 
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t.numel() else None
+# (an empty tensor's address may be non-NULL where the old helper here gave NULL: that is the B == 0 call, which the library answers
+#  before it looks at a pointer)
+_p = _lib.ptr
 
 
 class _cubemap_encode(torch.autograd.Function):

@@ -16,8 +16,7 @@ import torch
 from . import _lib
 
 
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+_p = _lib.ptr
 
 
 def _f32(t):

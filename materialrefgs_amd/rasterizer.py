@@ -56,7 +56,7 @@ class _Hint:
 _GENERATION = [0]       # bumped by note_surfel_set_changed(): a surfel set of the same size as before is still another set
 
 
-def _hint_entry(raster_settings, device, P=None):
+def _hint_entry(raster_settings, device):
     """The entry of this camera, or None when it was never rendered or when its matrices were written in place since."""
     key = _hint_key(raster_settings, device)
     ent = _WORK_HINTS.get(key)
@@ -69,7 +69,7 @@ def _hint_entry(raster_settings, device, P=None):
     return ent
 
 
-def _hint_is_warm(raster_settings, device, P=None):
+def _hint_is_warm(raster_settings, device):
     """True when this camera was rendered before, i.e. its hint holds measured work (of whichever surfel set).  Only then may the forward
     set up the backward's queues (they are a copy of its own): built from the cull counts alone they balance the backward a third worse
     than the backward's own ordering by what the forward waves walked."""
@@ -99,7 +99,7 @@ def _hint_flags(raster_settings, device, P, forward=False):
     return 0
 
 
-def _work_hint(raster_settings, device, P=None, count_visit=False):
+def _work_hint(raster_settings, device, count_visit=False):
     ent = _hint_entry(raster_settings, device)
     if ent is None:
         n = _lib.lib().mrgs_work_hint_bytes(int(raster_settings.image_height), int(raster_settings.image_width)) // 4
@@ -168,8 +168,7 @@ def cpu_deep_copy_tuple(input_tuple):
     return tuple(x.detach().cpu().clone() if torch.is_tensor(x) else x for x in input_tuple)
 
 
-def _ptr(t):
-    return None if t is None else (t.data_ptr() or None)      # (an int, NULL for an empty tensor: ctypes converts it for the `void*` parameters and struct fields)
+_ptr = _lib.ptr
 
 
 def _f32c(t):
@@ -202,13 +201,20 @@ def _camera_f32c(t):
 
 
 _RESOLVE = object()
-# MrgsRasterInputs::features_live of the render being issued on this thread (GaussianRasterizer.features_live: the settings tuple keeps
-# the reference's fields); the autograd node notes it for its backward
-_LIVE = threading.local()
+
+
+class _RenderCall:
+    """What one GaussianRasterizer.forward hands its autograd node besides the reference's arguments (the settings tuple keeps the
+    reference's fields): `features_live` (MrgsRasterInputs::features_live) and `glue` (the glue epilogue of the backward,
+    _rasterize_backward_native) on the way in; `visible`, the forward's radii > 0 bytes as a bool tensor, on the way out."""
+    __slots__ = ("features_live", "glue", "visible")
+
+    def __init__(self, features_live=0, glue=None):
+        self.features_live, self.glue, self.visible = int(features_live or 0), glue, None
 
 
 def _make_cfg_inputs(raster_settings, means3D, sh, colors_precomp, features, opacities, scales, rotations, cov3Ds_precomp, sh_rest=None,
-                     bwd_grad_ws=None, work_hint=_RESOLVE, extra_flags=0):
+                     bwd_grad_ws=None, work_hint=_RESOLVE, extra_flags=0, features_live=0):
     """work_hint: the camera's hint buffer (or None) -- the BACKWARD passes the very tensor its forward used (the queue state, the tickets
     and the forward's item assignment live in it: a buffer resolved anew at backward time could be a fresh, zeroed one after
     reset_work_hints(), an eviction or an in-place pose change, and a prepared backward would then pull item 0 in every wave); the
@@ -230,7 +236,7 @@ def _make_cfg_inputs(raster_settings, means3D, sh, colors_precomp, features, opa
                            _ptr(raster_settings.viewmatrix), _ptr(raster_settings.projmatrix), _ptr(raster_settings.campos),
                            _ptr(work_hint), _ptr(sh_rest),
                            _ptr(bwd_grad_ws), (_hint_flags(raster_settings, means3D.device, P, forward=is_forward) if means3D.is_cuda else 0) | extra_flags,
-                           int(getattr(_LIVE, "n", 0) or 0))
+                           features_live)
     return cfg, inp, work_hint
 
 
@@ -336,10 +342,10 @@ def deferred_raster_count(render_fn):
 
 
 def _rasterize_forward_native(raster_settings, means3D, sh, colors_precomp, features, opacities, scales, rotations, cov3Ds_precomp,
-                              sh_rest=None, prepare_backward=False):
+                              sh_rest=None, prepare_backward=False, call=None):
     """Counterpart of `_C.rasterize_gaussians` (rasterize_points.cu:41-144).  prepare_backward: also allocate the backward's gradient-row
     workspace and let the forward clear it and set up the backward's work queues (MrgsRasterInputs::bwd_grad_ws); it is appended to
-    the returned tuple."""
+    the returned tuple.  call (_RenderCall): its features_live goes into the inputs, its `visible` receives the radii > 0 bytes."""
     if means3D.dim() != 2 or means3D.shape[1] != 3:
         raise RuntimeError("means3D must have dimensions (num_points, 3)")
     if not means3D.is_cuda:
@@ -353,7 +359,8 @@ def _rasterize_forward_native(raster_settings, means3D, sh, colors_precomp, feat
         with _lib.guard(dev):
             grad_ws = torch.empty((L.mrgs_grad_bytes(means3D.shape[0], S_),), dtype=torch.uint8, device=dev)
     cfg, inp, hint = _make_cfg_inputs(raster_settings, means3D, sh, colors_precomp, features, opacities, scales, rotations, cov3Ds_precomp,
-                                      sh_rest, grad_ws, extra_flags=_lib.MRGS_HINT_VISIBLE_BYTES)
+                                      sh_rest, grad_ws, extra_flags=_lib.MRGS_HINT_VISIBLE_BYTES,
+                                      features_live=0 if call is None else call.features_live)
     P, S = cfg.P, cfg.S
     with _lib.guard(dev):
         st = _lib.stream_ptr(dev)
@@ -364,7 +371,8 @@ def _rasterize_forward_native(raster_settings, means3D, sh, colors_precomp, feat
         # radii [P] int32 and, right behind them, a byte per gaussian that takes radii > 0 (MRGS_HINT_VISIBLE_BYTES): one allocation
         rbuf = torch.empty((5 * P,), dtype=torch.uint8, device=dev)
         radii = rbuf[:4 * P].view(torch.int32)
-        _LIVE.visible = rbuf[4 * P:].view(torch.bool)
+        if call is not None:
+            call.visible = rbuf[4 * P:].view(torch.bool)
         geom = torch.empty((L.mrgs_geom_bytes(P, H, W),), dtype=torch.uint8, device=dev)
         img = torch.empty((L.mrgs_img_bytes(H, W),), dtype=torch.uint8, device=dev)
         R = ctypes.c_int64(0)
@@ -422,7 +430,7 @@ def _rasterize_forward_native(raster_settings, means3D, sh, colors_precomp, feat
 
 def _rasterize_backward_native(raster_settings, means3D, radii, colors_precomp, features, scales, rotations, cov3Ds_precomp,
                                grad_out_color, grad_out_feature, grad_out_others, sh, opacities, geom, num_rendered, binning, img,
-                               sh_rest=None, prepared_grad_ws=None, work_hint=_RESOLVE, glue=None):
+                               sh_rest=None, prepared_grad_ws=None, work_hint=_RESOLVE, glue=None, features_live=0):
     """Counterpart of `_C.rasterize_gaussians_backward` (rasterize_points.cu:146-252).  prepared_grad_ws: the workspace the forward of
     this render was given (cleared, queues set up) -- valid for one backward.  work_hint: the hint buffer that forward used (its ctx
     keeps it); a prepared backward without it takes the non-prepared path (it orders and clears by itself).
@@ -434,7 +442,7 @@ def _rasterize_backward_native(raster_settings, means3D, radii, colors_precomp, 
     if prepared_grad_ws is not None and (work_hint is _RESOLVE or work_hint is None):
         prepared_grad_ws = None            # the forward's queues cannot be named: never guess them
     cfg, inp, _ = _make_cfg_inputs(raster_settings, means3D, sh, colors_precomp, features, opacities, scales, rotations, cov3Ds_precomp,
-                                   sh_rest, prepared_grad_ws, work_hint)
+                                   sh_rest, prepared_grad_ws, work_hint, features_live=features_live)
     P, S, M = cfg.P, cfg.S, cfg.M
     with _lib.guard(dev):
         st = _lib.stream_ptr(dev)
@@ -480,25 +488,26 @@ def _rasterize_backward_native(raster_settings, means3D, radii, colors_precomp, 
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, features, opacities, scales, rotations, cov3Ds_precomp,
-                        raster_settings, sh_rest=None):
+                        raster_settings, sh_rest=None, call=None):
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, features, opacities, scales, rotations,
-                                     cov3Ds_precomp, raster_settings, sh_rest)
+                                     cov3Ds_precomp, raster_settings, sh_rest, call)
 
 
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, features, opacities, scales, rotations, cov3Ds_precomp,
-                raster_settings, sh_rest=None):
+                raster_settings, sh_rest=None, call=None):
         ctx.set_materialize_grads(False)   # output gradients nobody supplied arrive as None (handled in backward), not as zero-filled maps
         # sh_rest: split SH layout (extension over the reference's signature): sh = _features_dc [P,1,3], sh_rest = _features_rest
         # [P,M-1,3] -- the model's own tensors, no torch.cat per render and no slicing of the gradient in its backward
         means3D, sh, colors_precomp, features = _f32c(means3D), _f32c(sh), _f32c(colors_precomp), _f32c(features)
         sh_rest = None if sh_rest is None else _f32c(sh_rest)
+        ctx.call = call = call if call is not None else _RenderCall()      # (features_live and the glue link: the backward's too)
         opacities, scales, rotations, cov3Ds_precomp = _f32c(opacities), _f32c(scales), _f32c(rotations), _f32c(cov3Ds_precomp)
         rs = raster_settings._replace(bg=_f32c(raster_settings.bg), viewmatrix=_camera_f32c(raster_settings.viewmatrix),
                                       projmatrix=_camera_f32c(raster_settings.projmatrix), campos=_camera_f32c(raster_settings.campos))
         args = (rs, means3D, sh, colors_precomp, features, opacities, scales, rotations, cov3Ds_precomp, sh_rest,
-                any(ctx.needs_input_grad) and means3D.is_cuda and _hint_is_warm(rs, means3D.device))
+                any(ctx.needs_input_grad) and means3D.is_cuda and _hint_is_warm(rs, means3D.device), call)
         if raster_settings.debug:
             cpu_args = cpu_deep_copy_tuple(args[1:])   # copy them before they can be corrupted
             try:
@@ -510,8 +519,6 @@ class _RasterizeGaussians(torch.autograd.Function):
         else:
             out = _rasterize_forward_native(*args)
         (num_rendered, binning_pairs), contrib, color, feature, depth, radii, geomBuffer, binningBuffer, imgBuffer, grad_ws, hint = out
-        ctx.features_live = int(getattr(_LIVE, "n", 0) or 0)
-        ctx.glue = getattr(_LIVE, "glue", None)          # the glue epilogue of the backward (GaussianRasterizer.glue, set by render_surfel)
         ctx.prepared_grad_ws = grad_ws       # cleared by the forward, queues of the backward set up: good for ONE backward
         ctx.work_hint = hint                 # the buffer those queues live in: the backward is handed this very tensor (never a re-resolved one)
         ctx.raster_settings = rs
@@ -542,21 +549,17 @@ class _RasterizeGaussians(torch.autograd.Function):
         prepared, ctx.prepared_grad_ws = ctx.prepared_grad_ws, None
         args = (rs, means3D, radii, colors_precomp, features, scales, rotations, cov3Ds_precomp, _f32c(grad_out_color),
                 _f32c(grad_out_feature), _f32c(grad_depth), sh, opacities, geomBuffer, num_rendered, binningBuffer, imgBuffer, sh_rest, prepared,
-                ctx.work_hint, getattr(ctx, "glue", None))
-        _LIVE.n = getattr(ctx, "features_live", 0)       # (the autograd engine's thread: the forward's hint again)
-        try:
-            if rs.debug:
-                cpu_args = cpu_deep_copy_tuple(args[1:-1])
-                try:
-                    out = _rasterize_backward_native(*args)
-                except Exception as ex:
-                    torch.save(cpu_args, "snapshot_bw.dump")
-                    print("\nAn error occured in backward. Writing snapshot_bw.dump for debugging.\n")
-                    raise ex
-            else:
+                ctx.work_hint, ctx.call.glue, ctx.call.features_live)
+        if rs.debug:
+            cpu_args = cpu_deep_copy_tuple(args[1:-2])
+            try:
                 out = _rasterize_backward_native(*args)
-        finally:
-            _LIVE.n = 0
+            except Exception as ex:
+                torch.save(cpu_args, "snapshot_bw.dump")
+                print("\nAn error occured in backward. Writing snapshot_bw.dump for debugging.\n")
+                raise ex
+        else:
+            out = _rasterize_backward_native(*args)
         (grad_means2D, grad_colors_precomp, grad_features, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh, grad_scales,
          grad_rotations, grad_sh_rest) = out
         # empty inputs (the `torch.Tensor([])` placeholders) get empty gradients of matching shape
@@ -570,7 +573,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         if cov3Ds_precomp.numel() == 0:
             grad_cov3Ds_precomp = None
         return (grad_means3D, grad_means2D, grad_sh, grad_colors_precomp, grad_features, grad_opacities, grad_scales,
-                grad_rotations, grad_cov3Ds_precomp, None, grad_sh_rest)
+                grad_rotations, grad_cov3Ds_precomp, None, grad_sh_rest, None)
 
 
 class GaussianRasterizationSettings(NamedTuple):
@@ -589,6 +592,12 @@ class GaussianRasterizationSettings(NamedTuple):
 
 
 class GaussianRasterizer(nn.Module):
+    # extensions over the reference's module, plain attributes: the first two are set before a call, the third is read after it
+    features_live = 0        # n > 0: the feature channels n .. S - 1 are zero padding of the rows (MrgsRasterInputs::features_live)
+    glue = None              # the glue epilogue of the backward (_rasterize_backward_native)
+    visible = None           # radii > 0 of the last render as a bool tensor, written by the forward itself (every render function of the
+    #                          reference returns it as "visibility_filter"; `radii > 0` is a torch kernel per view otherwise)
+
     def __init__(self, raster_settings):
         super().__init__()
         self.raster_settings = raster_settings
@@ -638,17 +647,9 @@ class GaussianRasterizer(nn.Module):
         if cov3D_precomp is None:
             cov3D_precomp = empty
 
-        _LIVE.n = int(getattr(self, "features_live", 0) or 0)      # (extension: feature channels n .. S - 1 are zero padding of the rows)
-        _LIVE.glue = getattr(self, "glue", None)                   # (extension: the glue epilogue of the backward, _rasterize_backward_native)
-        _LIVE.visible = None
-        try:
-            out = rasterize_gaussians(means3D, means2D, shs, colors_precomp, features, opacities, scales, rotations, cov3D_precomp,
-                                      raster_settings, shs_rest)
-            # extension: radii > 0 of this render as a bool tensor, written by the forward itself (every render function of the reference
-            # returns it as "visibility_filter"; `radii > 0` is a torch kernel per view otherwise)
-            self.visible = getattr(_LIVE, "visible", None)
-            return out
-        finally:
-            _LIVE.n = 0
-            _LIVE.glue = None
-            _LIVE.visible = None
+        call = _RenderCall(self.features_live, self.glue)
+        self.visible = None
+        out = rasterize_gaussians(means3D, means2D, shs, colors_precomp, features, opacities, scales, rotations, cov3D_precomp,
+                                  raster_settings, shs_rest, call)
+        self.visible = call.visible
+        return out

@@ -24,7 +24,7 @@ from ._lib import MrgsMapsFrame, MrgsSurfelGrads, MrgsSurfelParams
 
 from .gs_utils import build_scaling_rotation, eval_sh, flip_align_view, linear_to_srgb, safe_normalize
 from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer, deferred_raster_count
-from .shading import (EnvLight, get_full_color_volume, get_full_color_volume_indirect, get_specular_color_surfel,
+from .shading import (EnvLight, GradStackHandoff, get_full_color_volume, get_full_color_volume_indirect, get_specular_color_surfel,
                       shade_and_composite_surfel)
 
 
@@ -95,10 +95,7 @@ class SurfelModel:
         return safe_normalize(normals_raw)
 
 
-def _p(t):
-    return None if t is None else t.data_ptr()      # (an int: ctypes converts it for the `void*` parameters and struct fields)
-
-
+_p = _lib.ptr
 _c = _lib.f32c
 
 
@@ -115,25 +112,14 @@ def set_after_features_hook(fn):
 class _GlueLink:
     """What ties a _SurfelFeatures node to the rasterizer node that consumes its outputs (the glue epilogue, MrgsRasterGrads::glue_params):
     `raw` = the node's nine raw parameter tensors; the rasterizer's backward leaves their gradients in `results`, the node's own backward
-    hands them on instead of launching its kernel."""
+    hands them on instead of launching its kernel.  render_surfel makes one per call, hands it to surfel_features (whose node fills in
+    `raw` / `viewmatrix`) and, where the epilogue applies, to the rasterizer."""
     __slots__ = ("raw", "results", "viewmatrix")
 
-    def __init__(self, raw, viewmatrix=None):
-        self.raw, self.results, self.viewmatrix = raw, None, viewmatrix       # viewmatrix: the "pgsr" rows' (plane distance in channel 8)
-
-
-class _LastLink(__import__("threading").local):      # the link of the most recent _SurfelFeatures.forward on THIS thread (render_surfel picks it up)
     def __init__(self):
-        self.link = None
-
-    def __getitem__(self, i):
-        return self.link
-
-    def __setitem__(self, i, v):
-        self.link = v
+        self.raw = self.results = self.viewmatrix = None       # viewmatrix: the "pgsr" rows' (plane distance in channel 8)
 
 
-_LAST_LINK = _LastLink()
 _FUSE_GLUE = os.environ.get("MRGS_NO_GLUE_EPILOGUE", "0") != "1"
 
 
@@ -143,7 +129,7 @@ class _SurfelFeatures(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, xyz, scaling, rotation, opacity, refl, rough, ori_color, ind_dc, ind_rest, campos, pass_xyz=False, viewmatrix=None,
-                indirect_live=True):
+                indirect_live=True, link=None):
         ctx.set_materialize_grads(False)   # unused outputs arrive as None in backward, not as zero-filled tensors
         ctx.indirect_live = bool(indirect_live)
         if not xyz.is_cuda:
@@ -161,7 +147,8 @@ class _SurfelFeatures(torch.autograd.Function):
             st = _lib.stream_ptr(dev)
             _lib.check(L.mrgs_surfel_features_forward(ctypes.byref(prm), _p(op), _p(sc), _p(rot), _p(feat), st))
         ctx.save_for_backward(*ts, *(() if vm is None else (vm,)))
-        ctx.link = _LAST_LINK[0] = _GlueLink(ts[:9], vm)
+        ctx.link = link = link if link is not None else _GlueLink()
+        link.raw, link.viewmatrix = ts[:9], vm
         if pass_xyz:
             # the centres as a fifth output (the input itself): whoever consumes THEM -- the rasterizer -- sends its gradient through this
             # node, whose backward kernel adds it to its own: one sum inside a kernel instead of autograd's accumulation kernel
@@ -178,7 +165,7 @@ class _SurfelFeatures(torch.autograd.Function):
             # the rasterizer's per-gaussian backward has applied this node's backward already (the glue epilogue): nothing to launch
             if _AFTER_FEATURES_HOOK[0] is not None:
                 _AFTER_FEATURES_HOOK[0](None)              # (only without a reader of the indirect radiance: its factor is structurally zero)
-            return (*fused, None, None, None, None)
+            return (*fused, None, None, None, None, None)
         L = _lib.lib()
         prm = MrgsSurfelParams(P, *[_p(t) for t in ts], _p(vm))
         outs = [torch.empty_like(t) for t in ts[:9]]
@@ -194,16 +181,17 @@ class _SurfelFeatures(torch.autograd.Function):
             # (indirect_live False: the caller's step does not look at the blended indirect radiance -- its gradient is zero by the structure of
             #  the step, on every rank: the hook is told so instead of being handed a tensor of zeros to gather)
             _AFTER_FEATURES_HOOK[0](outs[7] if ctx.indirect_live else None)
-        return (*outs, None, None, None, None)
+        return (*outs, None, None, None, None, None)
 
 
-def surfel_features(pc, camera_center, pass_xyz=False, viewmatrix=None, indirect_live=True):
+def surfel_features(pc, camera_center, pass_xyz=False, viewmatrix=None, indirect_live=True, link=None):
     """(opacity[P,1], scales[P,2], rotations[P,4], features[P,8]) for `render_surfel` from the raw parameters of `pc`; with `pass_xyz`
     also the centres [P,3] as an output of the same node (hand THOSE to the rasterizer: its dL/dmeans3D is then summed with this node's
     own gradient of the centres inside the backward kernel).  `viewmatrix` (the camera's world_view_transform; "pgsr" flavour): features
-    [P,12] with the plane distance of get_distance in channel 8 and zeros behind it."""
+    [P,12] with the plane distance of get_distance in channel 8 and zeros behind it.  `link`: the caller's _GlueLink for this node (the
+    glue epilogue: the caller hands the same object to the rasterizer that consumes the outputs); without one the node keeps its own."""
     return _SurfelFeatures.apply(pc._xyz, pc._scaling, pc._rotation, pc._opacity, pc._refl_strength, pc._roughness, pc._ori_color,
-                                 pc._indirect_dc, pc._indirect_rest, camera_center, bool(pass_xyz), viewmatrix, bool(indirect_live))
+                                 pc._indirect_dc, pc._indirect_rest, camera_center, bool(pass_xyz), viewmatrix, bool(indirect_live), link)
 
 
 _MAPS_FRAME_CACHE = {}
@@ -387,7 +375,7 @@ def _black_like(bg_color):
 
 def _visibility(rasterizer, radii):
     """radii > 0: the mask the rasterizer's forward wrote next to the radii (GaussianRasterizer.visible), else the torch comparison."""
-    vis = getattr(rasterizer, "visible", None)
+    vis = rasterizer.visible
     return vis if vis is not None and vis.shape == radii.shape else radii > 0
 
 
@@ -407,25 +395,28 @@ class _SplitChannels(torch.autograd.Function):
     would otherwise each pad their gradient to [S,H,W] with a fill and a copy and meet in an accumulation kernel."""
 
     @staticmethod
-    def forward(ctx, maps, k, tail_unread=False):
+    def forward(ctx, maps, k, tail_unread=False, handoff=None):
         # tail_unread: the maps behind k + 1 are padding whose gradient the rasterizer's backward does not read (features_live)
+        # handoff (shading.GradStackHandoff): where the head's consumer leaves the gradient stack it allocates for this node
         ctx.set_materialize_grads(False)
-        ctx.k, ctx.shape, ctx.tail_unread = k, tuple(maps.shape), bool(tail_unread)
+        ctx.k, ctx.shape, ctx.tail_unread, ctx.handoff = k, tuple(maps.shape), bool(tail_unread), handoff
         return maps[:k], maps[k:k + 1]
 
     @staticmethod
     def backward(ctx, g_head, g_one):
         if g_head is None and g_one is None:
-            return None, None, None
+            return None, None, None, None
         k, shape = ctx.k, ctx.shape
         ref = g_head if g_head is not None else g_one
         hb = getattr(g_head, "_base", None) if g_head is not None else None
-        from . import shading as _sh
-        if hb is not None and tuple(hb.shape) == shape and g_head.storage_offset() == 0 and hb.is_contiguous() and hb.dtype == ref.dtype and \
-                _sh.take_owned_stack(hb):
-            # the producer laid its maps out as the head of a stack it allocated FOR this node (shading._SurfelShade.backward marks it):
-            # nothing to copy.  A base of the right shape that is not so marked (e.g. the gradient of torch.cat((the eight maps, other
-            # maps)): its rows behind the head belong to another branch) is left alone and copied from.
+        given = None
+        if ctx.handoff is not None:
+            given, ctx.handoff.stack = ctx.handoff.stack, None          # good for one take-over
+        if hb is not None and hb is given and tuple(hb.shape) == shape and g_head.storage_offset() == 0 and hb.is_contiguous() and \
+                hb.dtype == ref.dtype:
+            # the head gradient is the head of the very stack shading._SurfelShade.backward allocated FOR this node: nothing to copy.  A
+            # base of the right shape that is not that tensor (e.g. the gradient of torch.cat((the eight maps, other maps)): its rows
+            # behind the head belong to another branch) is left alone and copied from.
             g = hb
         else:
             g = torch.empty(shape, dtype=ref.dtype, device=ref.device)
@@ -433,7 +424,7 @@ class _SplitChannels(torch.autograd.Function):
         (g[k:k + 1].copy_(g_one) if g_one is not None else g[k:k + 1].zero_())
         if shape[0] > k + 1 and not ctx.tail_unread:
             g[k + 1:].zero_()
-        return g, None, None
+        return g, None, None, None
 
 
 def cov3D_precomp_of(pc, viewpoint_camera, scaling_modifier=1.0):
@@ -544,9 +535,10 @@ def render_surfel(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, ov
     fused_distance = flag != "2dgs" and not use_asg
     # (indirect_live: the blended indirect radiance reaches an output only under opt.indirect -- :423-430, 472-473 --; without it the SH
     #  indirect term's gradient is zero by construction, which a view-parallel step's exchange is told: dist.SurfelGradReducer.begin_early_ind)
+    link = _GlueLink()
     opacities, scales, rotations, features, means3D = surfel_features(pc, viewpoint_camera.camera_center, pass_xyz=True,
                                                                       viewmatrix=viewpoint_camera.world_view_transform if fused_distance else None,
-                                                                      indirect_live=bool(getattr(opt, "indirect", False)) and not use_asg)
+                                                                      indirect_live=bool(getattr(opt, "indirect", False)) and not use_asg, link=link)
     if use_asg:                 # the lobes instead of the SH indirect term in channels 5..7 (:312-336)
         features = torch.cat((features[:, :5], _asg_indirect_of(pc, viewpoint_camera, scaling_modifier)), dim=-1)
         if flag != "2dgs":
@@ -564,14 +556,15 @@ def render_surfel(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, ov
     # ("pgsr": with the padded rows of the fused node only -- nine channels in twelve floats -- ; the plane distance's gradient is part of the epilogue)
     if (_FUSE_GLUE and not indirect_live and not use_asg and (padded or not fused_distance) and cov3D_precomp is None and means3D.is_cuda
             and torch.is_grad_enabled()):
-        rasterizer.glue = _LAST_LINK[0]
-    _LAST_LINK[0] = None
+        rasterizer.glue = link
     contrib, rendered_image, rendered_features, radii, allmap = rasterizer(
         means3D=means3D, means2D=means2D, shs=shs, colors_precomp=colors_precomp, features=features, opacities=opacities,
         scales=scales, rotations=rotations, cov3D_precomp=cov3D_precomp)
-    rend_distance = None
+    rend_distance = grad_stack = None
     if flag != "2dgs":          # the eight material maps and the plane distance out of the 9 (12: padded rows) rasterized channels
-        rendered_features, rend_distance = _SplitChannels.apply(rendered_features, 8, padded)
+        # (grad_stack ties the split to the shading node below: one gradient stack for both, shading.GradStackHandoff)
+        grad_stack = GradStackHandoff(int(rendered_features.shape[0]))
+        rendered_features, rend_distance = _SplitChannels.apply(rendered_features, 8, padded, grad_stack)
     elif rendered_features.shape[0] != 8:        # (a slice of the full range is still an autograd node: a zero fill and a copy of 8 maps)
         rendered_features = rendered_features[:8]
 
@@ -598,7 +591,8 @@ def render_surfel(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, ov
     tracer = getattr(pc, "ray_tracer", None) if indirect else None
     final_image, diffuse_map, specular, extra_dict = shade_and_composite_surfel(
         pc.get_envmap, base_color, rendered_features, viewpoint_camera.HWK, viewpoint_camera.R, viewpoint_camera.T, reg["normal_map"],
-        reg["render_alpha_twin"], bg_color, srgb, ray_tracer=tracer, surf_depth=reg["surf_depth"])   # (the shading's own copy of the alpha map)
+        reg["render_alpha_twin"], bg_color, srgb, ray_tracer=tracer, surf_depth=reg["surf_depth"],      # (the shading's own copy of the alpha map)
+        grad_stack=grad_stack)
     if srgb:
         albedo = linear_to_srgb(albedo)
         specular = linear_to_srgb(specular)

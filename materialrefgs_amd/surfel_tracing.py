@@ -42,8 +42,7 @@ class SurfelTracingSettings(NamedTuple):
     specular_threshold: float = 0.0
 
 
-def _ptr(t):
-    return None if t is None else t.data_ptr()      # (an int: ctypes converts it for the `void*` parameters and struct fields)
+_ptr = _lib.ptr
 
 
 def _stream(dev):

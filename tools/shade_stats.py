@@ -21,10 +21,10 @@ def main():
     cap = {}
     orig = shading._SurfelShade.forward
 
-    def spy(ctx, base_color, features, normal_map, render_alpha, bg, srgb, lut, R, T, Kinv, lo, hi, vis, *mips):
+    def spy(ctx, base_color, features, normal_map, render_alpha, bg, srgb, lut, R, T, Kinv, lo, hi, vis, grad_stack, *mips):
         cap.update(normal=normal_map.detach().clone(), rough=features[1].detach().clone(), alpha=render_alpha.detach().clone(), R=R.clone(),
                    T=T.clone(), Kinv=Kinv, lo=lo, hi=hi, res=[m.shape[1] for m in mips])
-        return orig(ctx, base_color, features, normal_map, render_alpha, bg, srgb, lut, R, T, Kinv, lo, hi, vis, *mips)
+        return orig(ctx, base_color, features, normal_map, render_alpha, bg, srgb, lut, R, T, Kinv, lo, hi, vis, grad_stack, *mips)
     shading._SurfelShade.forward = staticmethod(spy)
     pipe = SimpleNamespace(depth_ratio=0.0, debug=False, compute_cov3D_python=False, convert_SHs_python=False)
     env.build_mips()
