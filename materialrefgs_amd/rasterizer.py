@@ -17,19 +17,19 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from ._cache import Bounded, constant, derived
 from ._lib import MrgsRasterConfig, MrgsRasterGrads, MrgsRasterInputs, MrgsRasterTicket
 
 
-_PAIR_GUESS = {}   # (device index, P, H, W) -> pair capacity to try first (previous count of that configuration + 25 %)
 _PAIR_GUESS_MAX = 64
+_PAIR_GUESS = Bounded(_PAIR_GUESS_MAX)   # (device index, P, H, W) -> pair capacity to try first (previous count of that configuration + 25 %)
 # Per-camera work hints (MrgsRasterInputs::work_hint): the forward orders its blend waves by what each 8x8 block cost the last time the
 # same camera was rendered.  Keyed by the camera's matrices (the tensors a training loop keeps per camera), bounded, and purely a
 # scheduling aid: results do not depend on it.  An entry holds its two matrices, so their storage cannot be handed to another camera's
 # tensors while the entry exists (the address is the key), and a hit must be the same storage at the same version.
-_WORK_HINTS = {}
 _WORK_HINTS_MAX = 2048                    # cameras ...
 _WORK_HINTS_MAX_BYTES = 256 << 20         # ... and device bytes the cache may pin (a buffer is ~100 KB at 800x800, ~340 KB at 1600x1600), least recently used first out
-_WORK_HINTS_BYTES = [0]
+_WORK_HINTS = Bounded(_WORK_HINTS_MAX, _WORK_HINTS_MAX_BYTES, lambda ent: ent.buf.numel() * 4)
 
 
 def _hint_key(raster_settings, device):
@@ -57,15 +57,12 @@ _GENERATION = [0]       # bumped by note_surfel_set_changed(): a surfel set of t
 
 
 def _hint_entry(raster_settings, device):
-    """The entry of this camera, or None when it was never rendered or when its matrices were written in place since."""
-    key = _hint_key(raster_settings, device)
-    ent = _WORK_HINTS.get(key)
-    if ent is None:
+    """The entry of this camera, or None when it was never rendered or when its matrices were written in place since.  The key holds
+    the matrices' addresses and the forward hands over contiguous fp32 matrices (_camera_f32c), so the versions are all that is left
+    to compare; a hint served for a camera that moved some other way would cost balance, never a value."""
+    ent = _WORK_HINTS.get(_hint_key(raster_settings, device))      # (a hit makes it the most recently used)
+    if ent is None or ent.versions != (raster_settings.viewmatrix._version, raster_settings.projmatrix._version):
         return None
-    vm, pm = raster_settings.viewmatrix, raster_settings.projmatrix
-    if ent.versions != (vm._version, pm._version):
-        return None
-    _WORK_HINTS[key] = _WORK_HINTS.pop(key)      # most recently used last (dicts keep insertion order)
     return ent
 
 
@@ -103,15 +100,9 @@ def _work_hint(raster_settings, device, count_visit=False):
     ent = _hint_entry(raster_settings, device)
     if ent is None:
         n = _lib.lib().mrgs_work_hint_bytes(int(raster_settings.image_height), int(raster_settings.image_width)) // 4
-        key = _hint_key(raster_settings, device)
-        old = _WORK_HINTS.pop(key, None)              # (stale: its matrices were written in place)
-        if old is not None:
-            _WORK_HINTS_BYTES[0] -= old.buf.numel() * 4
-        while _WORK_HINTS and (len(_WORK_HINTS) >= _WORK_HINTS_MAX or _WORK_HINTS_BYTES[0] + 4 * n > _WORK_HINTS_MAX_BYTES):
-            _WORK_HINTS_BYTES[0] -= _WORK_HINTS.pop(next(iter(_WORK_HINTS))).buf.numel() * 4      # (a render in flight keeps its buffer alive through its ctx)
-        ent = _Hint(torch.zeros(max(int(n), 1), dtype=torch.int32, device=device), raster_settings.viewmatrix, raster_settings.projmatrix)
-        _WORK_HINTS[key] = ent
-        _WORK_HINTS_BYTES[0] += ent.buf.numel() * 4
+        # (replaces a stale entry, whose matrices were written in place; a render in flight keeps an evicted buffer alive through its ctx)
+        ent = _WORK_HINTS[_hint_key(raster_settings, device)] = _Hint(torch.zeros(max(int(n), 1), dtype=torch.int32, device=device),
+                                                                      raster_settings.viewmatrix, raster_settings.projmatrix)
     if count_visit:
         ent.visits += 1
     return ent.buf
@@ -121,7 +112,6 @@ def reset_work_hints():
     """Forget every camera's measured work (the next render of each camera is a first visit again); bench.py uses it to time first
     visits.  A training loop does NOT need to call this after densification / pruning: see note_surfel_set_changed()."""
     _WORK_HINTS.clear()
-    _WORK_HINTS_BYTES[0] = 0
     _CAM_COPIES.clear()
 
 
@@ -131,21 +121,6 @@ def note_surfel_set_changed():
     orders its blend waves anew instead of reusing the deal made for the old set.  A change of the surfel COUNT is seen by the
     rasterizer itself and needs no call."""
     _GENERATION[0] += 1
-
-
-_ZERO_CONTRIB = {}
-
-
-def _zero_contrib(dev, H, W):
-    """`out_contrib` of the reference is allocated zero-filled and never written by any kernel (rasterize_points.cu:89); one read-only
-    zero tensor per (device, size) stands in for it instead of a 4 H W byte fill per render."""
-    key = (dev.index, H, W)
-    t = _ZERO_CONTRIB.get(key)
-    if t is None:
-        if len(_ZERO_CONTRIB) > 16:
-            _ZERO_CONTRIB.clear()
-        t = _ZERO_CONTRIB[key] = torch.zeros((1, H, W), dtype=torch.int32, device=dev)
-    return t
 
 
 _AFTER_BLEND_HOOK = [None]
@@ -177,8 +152,7 @@ def _f32c(t):
     return t.contiguous()
 
 
-_CAM_COPIES = {}     # (data_ptr, strides, dtype) of a camera matrix as the caller holds it -> (that tensor, its version, contiguous fp32 copy)
-_CAM_COPIES_MAX = 4096
+_CAM_COPIES = Bounded(4096)     # (data_ptr, strides, dtype, device) of a camera matrix as the caller holds it -> its contiguous fp32 copy (_cache.derived)
 
 
 def _camera_f32c(t):
@@ -189,15 +163,7 @@ def _camera_f32c(t):
     strides, dtype; the entry keeps the source alive, so the address cannot be reused) and redone when the source was written in place."""
     if t.dtype == torch.float32 and t.is_contiguous():
         return t
-    key = (t.data_ptr(), tuple(t.stride()), t.dtype, t.device.index)
-    ent = _CAM_COPIES.get(key)
-    if ent is not None and ent[1] == t._version and ent[0].shape == t.shape:
-        return ent[2]
-    if ent is None and len(_CAM_COPIES) >= _CAM_COPIES_MAX:
-        _CAM_COPIES.pop(next(iter(_CAM_COPIES)))
-    c = _f32c(t)
-    _CAM_COPIES[key] = (t, t._version, c)
-    return c
+    return derived(_CAM_COPIES, (t.data_ptr(), t.stride(), t.dtype, t.device), (t,), lambda: _f32c(t))
 
 
 _RESOLVE = object()
@@ -254,8 +220,6 @@ _TICKET_RING = 16          # MRGS_TICKET_RING of csrc/mrgs_api.hip (include/mrgs
 
 def _note_count(guess_key, num_rendered, hint_settings, dev):
     """Bookkeeping once a view's pair count is known: the next view's workspace guess, this camera's work hint."""
-    if guess_key not in _PAIR_GUESS and len(_PAIR_GUESS) >= _PAIR_GUESS_MAX:
-        _PAIR_GUESS.pop(next(iter(_PAIR_GUESS)))
     _PAIR_GUESS[guess_key] = max(int(num_rendered * 1.25) + 65536, 1)
     if hint_settings is not None:
         _work_hint(hint_settings, dev, count_visit=True)   # this camera's hint now holds measured work
@@ -364,7 +328,9 @@ def _rasterize_forward_native(raster_settings, means3D, sh, colors_precomp, feat
     P, S = cfg.P, cfg.S
     with _lib.guard(dev):
         st = _lib.stream_ptr(dev)
-        contrib = _zero_contrib(dev, H, W)   # allocated, never written
+        # `out_contrib` of the reference is allocated zero-filled and never written by any kernel (rasterize_points.cu:89):
+        # the shared read-only zeros stand in for it instead of a 4 H W byte fill per render
+        contrib = constant((1, H, W), torch.int32, dev)
         color = torch.empty((3, H, W), dtype=torch.float32, device=dev)
         feature = torch.empty((S, H, W), dtype=torch.float32, device=dev)
         others = torch.empty((7, H, W), dtype=torch.float32, device=dev)

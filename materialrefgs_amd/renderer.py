@@ -20,12 +20,13 @@ from types import SimpleNamespace
 import torch
 
 from . import _lib
+from ._cache import Bounded, constant, derived, zero_leaf
 from ._lib import MrgsMapsFrame, MrgsSurfelGrads, MrgsSurfelParams
 
 from .gs_utils import build_scaling_rotation, eval_sh, flip_align_view, linear_to_srgb, safe_normalize
 from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer, deferred_raster_count
-from .shading import (EnvLight, GradStackHandoff, get_full_color_volume, get_full_color_volume_indirect, get_specular_color_surfel,
-                      shade_and_composite_surfel)
+from .shading import (EnvLight, GradStackHandoff, _kinv_tuple, get_full_color_volume, get_full_color_volume_indirect,
+                      get_specular_color_surfel, shade_and_composite_surfel)
 
 
 class SurfelModel:
@@ -194,34 +195,27 @@ def surfel_features(pc, camera_center, pass_xyz=False, viewmatrix=None, indirect
                                  pc._indirect_dc, pc._indirect_rest, camera_center, bool(pass_xyz), viewmatrix, bool(indirect_live), link)
 
 
-_MAPS_FRAME_CACHE = {}
+_MAPS_FRAME_CACHE = Bounded(4096)
 
 
 def _maps_frame(view, depth_ratio):
     """Camera constants of depths_to_points (utils/point_utils.py:9-24) for the fused kernels.  Built once per camera on the
     host (float64) from the camera's matrices and cached: the reference rebuilds them with ~10 small GPU kernels per view."""
     wvt, fpt = view.world_view_transform, view.full_proj_transform
-    key = (wvt.data_ptr(), fpt.data_ptr(), wvt._version, fpt._version, int(view.image_width), int(view.image_height))
-    ent = _MAPS_FRAME_CACHE.get(key)
-    # An entry keeps its two matrices alive, so their addresses cannot be handed to other tensors while it exists; a hit must be
-    # the very same tensor objects' storage at the same version (in-place writes bump _version).
-    if ent is not None and not (ent[3].data_ptr() == wvt.data_ptr() and ent[4].data_ptr() == fpt.data_ptr()):
-        ent = None
-    if ent is None:
+    W, H = int(view.image_width), int(view.image_height)
+
+    def build():
         import numpy as np
         wv = wvt.detach().cpu().double().numpy()
         fp = fpt.detach().cpu().double().numpy()
-        W, H = int(view.image_width), int(view.image_height)
         c2w = np.linalg.inv(wv.T)
         ndc2pix = np.array([[W / 2, 0, 0, W / 2], [0, H / 2, 0, H / 2], [0, 0, 0, 1]], dtype=np.float64).T
         intrins = ((c2w.T @ fp) @ ndc2pix)[:3, :3].T
         M = c2w[:3, :3] @ np.linalg.inv(intrins)
-        ent = (wv[:3, :3].reshape(-1).tolist(), M.reshape(-1).tolist(), c2w[:3, 3].tolist(), wvt, fpt)
-        if len(_MAPS_FRAME_CACHE) > 4096:
-            _MAPS_FRAME_CACHE.clear()
-        _MAPS_FRAME_CACHE[key] = ent
+        return wv[:3, :3].reshape(-1).tolist(), M.reshape(-1).tolist(), c2w[:3, 3].tolist()
+    ent = derived(_MAPS_FRAME_CACHE, (wvt.data_ptr(), fpt.data_ptr(), W, H), (wvt, fpt), build)
     fr = MrgsMapsFrame()
-    fr.H, fr.W = int(view.image_height), int(view.image_width)
+    fr.H, fr.W = H, W
     for i in range(9):
         fr.view_rot[i] = ent[0][i]
         fr.ray_matrix[i] = ent[1][i]
@@ -358,21 +352,6 @@ def compute_2dgs_normal_and_regularizations(allmap, viewpoint_camera, pipe, retu
     return out
 
 
-_BLACK = {}
-
-
-def _black_like(bg_color):
-    """A zero background of bg_color's shape / device / dtype, shared between renders (read-only: nothing writes a background): the
-    reference fills a fresh one per render."""
-    key = (bg_color.device, bg_color.dtype, tuple(bg_color.shape))
-    t = _BLACK.get(key)
-    if t is None:
-        if len(_BLACK) > 16:
-            _BLACK.clear()
-        t = _BLACK[key] = torch.zeros_like(bg_color)
-    return t
-
-
 def _visibility(rasterizer, radii):
     """radii > 0: the mask the rasterizer's forward wrote next to the radii (GaussianRasterizer.visible), else the torch comparison."""
     vis = rasterizer.visible
@@ -380,10 +359,12 @@ def _visibility(rasterizer, radii):
 
 
 def _raster_settings(viewpoint_camera, pc, pipe, bg_color, scaling_modifier):
+    # the rasterizer always composites over black (__init__.py:247): the shared zeros, where the reference fills a background per render
+    bg_color = constant(bg_color.shape, bg_color.dtype, bg_color.device)
     return GaussianRasterizationSettings(
         image_height=int(viewpoint_camera.image_height), image_width=int(viewpoint_camera.image_width),
         tanfovx=math.tan(viewpoint_camera.FoVx * 0.5), tanfovy=math.tan(viewpoint_camera.FoVy * 0.5),
-        bg=_black_like(bg_color),                           # the rasterizer always composites over black (__init__.py:247)
+        bg=bg_color,
         scale_modifier=scaling_modifier, viewmatrix=viewpoint_camera.world_view_transform,
         projmatrix=viewpoint_camera.full_proj_transform, sh_degree=pc.active_sh_degree, campos=viewpoint_camera.camera_center,
         prefiltered=False, debug=getattr(pipe, "debug", False))
@@ -443,23 +424,6 @@ def cov3D_precomp_of(pc, viewpoint_camera, scaling_modifier=1.0):
     return (splat2world[:, [0, 1, 3]] @ world2pix[:, [0, 1, 3]]).permute(0, 2, 1).reshape(-1, 9)      # column major, as glm wants it
 
 
-_ZERO_POINTS = {}
-
-
-def _screenspace_points(pc):
-    """screenspace_points of the reference (gaussian_renderer/__init__.py:229-233): a zero tensor whose .grad receives the
-    2D-mean gradients.  A leaf here (the reference adds 0 and calls retain_grad(): same .grad, one kernel more)."""
-    xyz = pc.get_xyz
-    key = (xyz.device, xyz.shape[0], xyz.dtype)
-    z = _ZERO_POINTS.get(key)
-    if z is None:
-        if len(_ZERO_POINTS) > 8:
-            _ZERO_POINTS.clear()
-        z = _ZERO_POINTS[key] = torch.zeros_like(xyz)
-    # a new leaf over the shared zeros (nothing reads or writes its values: the rasterizer only routes a gradient to it): no fill per view
-    return z.detach().requires_grad_(True)
-
-
 def get_distance(scaling_modifier, means3D, viewpoint_camera, pc):
     """gaussian_renderer/envgs_renderer.py:30-38: |facing normal . centre| in the camera frame, [P,1] (the plane distance the "pgsr"
     flavour rasterizes as its last feature channel)."""
@@ -489,7 +453,7 @@ def render_initial(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, o
     (arguments/config.py:1): the plane distance of get_distance rides as the one feature channel and comes back as "rend_distance"
     (:170-176, 215-218) -- blended by the vendored rasterizer's rule -- and surf_depth / surf_normal come from the flavour's unbiased
     depth (pgsr_unbiased_depth; parity unpinned)."""
-    means2D = _screenspace_points(pc)
+    means2D = zero_leaf(pc.get_xyz)       # screenspace_points (gaussian_renderer/__init__.py:229-233): its .grad receives the 2D-mean gradients
     dist_feature = get_distance(scaling_modifier, pc.get_xyz, viewpoint_camera, pc) if flag != "2dgs" else None
     rasterizer = GaussianRasterizer(raster_settings=_raster_settings(viewpoint_camera, pc, pipe, bg_color, scaling_modifier))
     shs, colors_precomp = ((pc._features_dc, pc._features_rest), None) if override_color is None else (None, override_color)
@@ -521,7 +485,7 @@ def render_surfel(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, ov
     blended by the rasterizer, then deferred split-sum shading."""
     if opt is None:
         opt = SimpleNamespace(indirect=False)
-    means2D = _screenspace_points(pc)
+    means2D = zero_leaf(pc.get_xyz)       # screenspace_points (gaussian_renderer/__init__.py:229-233): its .grad receives the 2D-mean gradients
     rasterizer = GaussianRasterizer(raster_settings=_raster_settings(viewpoint_camera, pc, pipe, bg_color, scaling_modifier))
     means3D = pc.get_xyz
     shs, colors_precomp = ((pc._features_dc, pc._features_rest), None) if override_color is None else (None, override_color)
@@ -617,7 +581,7 @@ def render_volume(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, ov
     libmrgs.so; the per-gaussian elementwise glue is torch, as in the reference.  `pipe.compute_cov3D_python`: cov3D_precomp_of."""
     if opt is None:
         opt = SimpleNamespace(indirect=False)
-    means2D = _screenspace_points(pc)
+    means2D = zero_leaf(pc.get_xyz)       # screenspace_points (gaussian_renderer/__init__.py:229-233): its .grad receives the 2D-mean gradients
     rasterizer = GaussianRasterizer(raster_settings=_raster_settings(viewpoint_camera, pc, pipe, bg_color, scaling_modifier))
     means3D, opacity = pc.get_xyz, pc.get_opacity
     refl, ori_color, roughness = pc.get_refl, pc.get_ori_color, pc.get_rough
@@ -794,33 +758,19 @@ class _MirrorRaysBlended(torch.autograd.Function):
         return g_n.permute(2, 0, 1), g_al.reshape(ctx.shapes[0]), g_sd.reshape(ctx.shapes[1]), None, None, None
 
 
-_CAM_CONSTS = {}
-
-
-def _fingerprint(x):
-    """What a cached constant was built from: the bytes of a host array (a few dozen), address and version counter of a tensor."""
-    if torch.is_tensor(x):
-        return (x.data_ptr(), x._version, tuple(x.shape))
-    import numpy as np
-    return np.asarray(x).tobytes()
+_CAM_CONSTS = Bounded(4096)
 
 
 def _camera_consts(viewpoint_camera, dev):
     """K^-1 (host tuple), Camera.R and Camera.T as device tensors, built once per camera object AND pose: an entry is only reused while
-    R, T and the intrinsics are what it was built from (a pose refinement or a resolution change on the same object rebuilds it)."""
-    import numpy as np
-    H, W, K = viewpoint_camera.HWK
-    key = id(viewpoint_camera)
-    stamp = (_fingerprint(viewpoint_camera.R), _fingerprint(viewpoint_camera.T), _fingerprint(K), int(H), int(W))
-    ent = _CAM_CONSTS.get(key)
-    if ent is None or ent[0] is not viewpoint_camera or ent[4] != dev or ent[5] != stamp:
-        Kinv = tuple(np.linalg.inv(np.asarray(K, dtype=np.float32)).astype(np.float32).reshape(-1).tolist())
+    R, T and the intrinsics are what it was built from (a pose refinement or new intrinsics on the same object rebuild it)."""
+    K = viewpoint_camera.HWK[2]
+
+    def build():
         R = torch.as_tensor(viewpoint_camera.R, dtype=torch.float32, device=dev).contiguous()
         T = torch.as_tensor(viewpoint_camera.T, dtype=torch.float32, device=dev).contiguous()
-        if len(_CAM_CONSTS) > 4096:
-            _CAM_CONSTS.clear()
-        ent = _CAM_CONSTS[key] = (viewpoint_camera, Kinv, R, T, dev, stamp)      # holds the camera: its id stays its own
-    return ent[1], ent[2], ent[3]
+        return viewpoint_camera, _kinv_tuple(K), R, T       # holds the camera: its id stays its own
+    return derived(_CAM_CONSTS, (id(viewpoint_camera), dev), (viewpoint_camera.R, viewpoint_camera.T, K), build)[1:]
 
 
 def _mirror_rays_blended(viewpoint_camera, rend_normal, rend_alpha, surf_depth):
@@ -915,8 +865,8 @@ def render_surfel2(indirect_renderer, env, viewpoint_camera, pc, pipe, bg_color,
     runs."""
     if opt is None:
         opt = SimpleNamespace(indirect=False)
-    means2D = _screenspace_points(pc)
-    settings = _raster_settings(viewpoint_camera, pc, pipe, _black_like(bg_color), scaling_modifier)     # bg = 0 as at :483
+    means2D = zero_leaf(pc.get_xyz)       # screenspace_points (gaussian_renderer/__init__.py:229-233): its .grad receives the 2D-mean gradients
+    settings = _raster_settings(viewpoint_camera, pc, pipe, bg_color, scaling_modifier)     # bg = 0 as at :483
     rasterizer = GaussianRasterizer(raster_settings=settings)
     means3D = pc.get_xyz
     shs, colors_precomp = ((pc._features_dc, pc._features_rest), None) if override_color is None else (None, override_color)

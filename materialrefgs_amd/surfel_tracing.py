@@ -19,6 +19,7 @@ import torch
 from torch import nn
 
 from . import _lib
+from ._cache import Bounded, constant, derived, zero_leaf as _zero_leaf
 from .gs_utils import build_rotation, eval_sh
 
 MID_CHANNELS = 16    # optix_utils.py:28-35: ray_o 3, ray_d 3, dpt 1, acc 1, norm 3, aux 2, rgb 3 per tracing depth
@@ -209,7 +210,7 @@ class SurfelTracer(nn.Module):
         self._blob_saved = False         # a trace that a backward may follow holds self._blob: the next build / trace must not write into it
         self._ws = None
         self._n = 0
-        self._bg_host = {}               # settings.bg -> its three floats on the host (read back once per tensor, not once per trace)
+        self._bg_host = Bounded(64)      # settings.bg -> its three floats on the host (read back once per tensor, not once per trace)
         self.want_mid = True             # the per-depth record `mid` (41 MB for an 800x800 view): HardwareRendering reads it only for max_trace_depth > 0
         self.build_on_trace = False      # HardwareRendering sets it: build from the corners the record kernel writes (= get_disks')
 
@@ -244,13 +245,7 @@ class SurfelTracer(nn.Module):
         `.tolist()` per trace is a device-to-host synchronisation in the middle of the stream-ordered pipeline."""
         if not bg.is_cuda:
             return tuple(float(x) for x in bg.detach().reshape(-1)[:3].tolist())
-        key = _bg_key(bg)
-        ent = self._bg_host.get(key)
-        if ent is None or ent[1] is not bg:
-            if len(self._bg_host) > 64:
-                self._bg_host.clear()
-            ent = self._bg_host[key] = (tuple(float(x) for x in bg.detach().reshape(-1)[:3].tolist()), bg)   # holds bg: the address stays its own
-        return ent[0]
+        return derived(self._bg_host, bg.data_ptr(), (bg,), lambda: tuple(float(x) for x in bg.detach().reshape(-1)[:3].tolist()))
 
     def forward(self, ray_o, ray_d, v=None, means3D=None, grads3D=None, shs=None, colors_precomp=None, others_precomp=None, opacities=None,
                 scales=None, rotations=None, cov3D_precomp=None, tracer_settings=None, start_from_first=True, records=None):
@@ -327,31 +322,6 @@ def record_summary(tracer):
             "record_usable": have_hdr and st.numel() >= off[4] and pick(off[2] + 1) == 0}
 
 
-_ZERO_LEAVES, _OTHERS = {}, {}
-
-
-def _zero_leaf(like):
-    """A leaf of zeros shaped like `like` whose .grad receives a gradient: a fresh tensor object over one shared, never written block of
-    zeros (no fill kernel per view)."""
-    key = (like.device, tuple(like.shape), like.dtype)
-    z = _ZERO_LEAVES.get(key)
-    if z is None:
-        if len(_ZERO_LEAVES) > 8:
-            _ZERO_LEAVES.clear()
-        z = _ZERO_LEAVES[key] = torch.zeros_like(like, requires_grad=False)
-    return z.detach().requires_grad_(True)
-
-
-def _const_others(P, device):
-    key = (device, P)
-    t = _OTHERS.get(key)
-    if t is None:
-        if len(_OTHERS) > 8:
-            _OTHERS.clear()
-        t = _OTHERS[key] = torch.full((P, 2), 0.01, device=device)
-    return t
-
-
 def _raw_model(pcd, pipe, override_color):
     """(xyz, scaling, rotation, opacity, features_dc, features_rest) when `pcd` stores GaussianModel's raw tensors under their usual names
     with the usual activations and the colour comes from its SH coefficients; None -> the getters are used."""
@@ -371,24 +341,6 @@ def _raw_model(pcd, pipe, override_color):
         if getattr(pcd, attr, fn) is not fn:
             return None
     return ts
-
-
-def _bg_key(bg):
-    return (bg.data_ptr(), bg._version, bg.device)
-
-
-_ZERO_MAPS = {}
-
-
-def _zero_map(like):
-    """A shared all-zero map of `like`'s shape (read-only by convention: it stands for a per-view torch.zeros_like whose value never changes)."""
-    key = (str(like.device), tuple(like.shape), like.dtype)
-    z = _ZERO_MAPS.get(key)
-    if z is None:
-        if len(_ZERO_MAPS) >= 8:
-            _ZERO_MAPS.pop(next(iter(_ZERO_MAPS)))
-        z = _ZERO_MAPS[key] = torch.zeros(like.shape, dtype=like.dtype, device=like.device)
-    return z
 
 
 def _depth_to_normal(view, depth):
@@ -453,7 +405,7 @@ class HardwareRendering(nn.Module):
             means3D = raw[0]
             P = means3D.shape[0]
             grads3D = _zero_leaf(means3D)                                                 # receives dL/dmeans3D, as the reference's (:131-135)
-            others = _const_others(P, means3D.device)                                     # the reference's placeholder (:173-177)
+            others = constant((P, 2), torch.float32, means3D.device, 0.01)                # the reference's placeholder (:173-177)
             recs = (means3D.new_zeros((0, 16)), means3D.new_zeros((0, 8)), None) if P == 0 else \
                 _PrepRaw.apply(*raw, others, grads3D, settings.campos.reshape(3), settings.sh_degree, float(settings.scale_modifier))
             rgb, dpt, acc, norm, dist, aux, mid, wet = self.tracer(ray_o.contiguous(), ray_d.contiguous(), v, means3D=means3D, tracer_settings=settings,
@@ -503,7 +455,7 @@ class HardwareRendering(nn.Module):
         if start_from_first:
             out["surf_normal"] = chw(_depth_to_normal(camera, dpt[..., 0]) * acc.detach())
         else:
-            out["surf_normal"] = _zero_map(chw(norm))        # (the reference's zeros_like(:231); a constant, not filled per view)
+            out["surf_normal"] = constant(chw(norm).shape, norm.dtype, norm.device)    # (the reference's zeros_like(:231); shared and read-only, not filled per view)
         out["specular"] = chw(aux[..., :1])
         out["roughness"] = chw(aux[..., 1:2])
         return out
