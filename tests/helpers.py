@@ -35,7 +35,8 @@ def raster_settings(cam, device, sh_degree=3, scale_modifier=1.0, bg=None, debug
 class HipRender:
     """Forward (+ optional backward) through materialrefgs_amd.rasterizer, keeping handles for introspection."""
 
-    def __init__(self, scene, cam, device, sh_degree=3, scale_modifier=1.0, colors_precomp=None, bg=None, use_features=True, rs=None, features_live=0):
+    def __init__(self, scene, cam, device, sh_degree=3, scale_modifier=1.0, colors_precomp=None, bg=None, use_features=True, rs=None, features_live=0,
+                 features_misalign=False):
         from materialrefgs_amd.rasterizer import GaussianRasterizer
         self.dev = device
         sc = scene.to(device)
@@ -51,6 +52,15 @@ class HipRender:
         scales = leaf("scales", sc.scales)
         rots = leaf("rotations", sc.rotations)
         feats = leaf("features", sc.features) if (use_features and sc.features.shape[1] > 0) else None
+        feats_in = feats
+        if features_misalign and feats is not None:
+            # the rows as a contiguous view that starts 4 bytes into a larger buffer (the allocator hands out 512-byte aligned blocks), filled
+            # from the leaf: no 16-byte piece of a row is aligned, the blend kernels must take their 4-byte staging (the non-FV instances);
+            # copy_ is differentiable, the gradient of the view arrives at the leaf
+            buf = torch.zeros(feats.numel() + 8, dtype=feats.dtype, device=device)
+            feats_in = buf[1:1 + feats.numel()].view(feats.shape)
+            feats_in.copy_(feats)
+            assert feats_in.is_contiguous() and feats_in.data_ptr() % 16 == 4, feats_in.data_ptr()
         kw = {}
         if colors_precomp is None:
             kw["shs"] = leaf("sh", sc.shs)
@@ -59,8 +69,10 @@ class HipRender:
         rast = GaussianRasterizer(self.rs)
         rast.features_live = features_live         # extension: feature channels from here on are zero padding of the rows
         self.contrib, self.color, self.feature, self.radii, self.others = rast(
-            means3D=means3D, means2D=means2D, opacities=opac, features=feats, scales=scales, rotations=rots, **kw)
+            means3D=means3D, means2D=means2D, opacities=opac, features=feats_in, scales=scales, rotations=rots, **kw)
         self.fn = self.color.grad_fn
+        if features_misalign and feats is not None:      # ... and that address is the one the kernels were handed (no aligned copy on the way)
+            assert self.fn.saved_tensors[1].data_ptr() == feats_in.data_ptr()
         self.P = sc.means3D.shape[0]
         self.H, self.W = cam.image_height, cam.image_width
         self.S = 0 if feats is None else feats.shape[1]

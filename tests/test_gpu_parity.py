@@ -35,6 +35,18 @@ CASES = [
     (3000, 24, 64, 64, 6.0, 0, 4),        # MAX_FEATURES
     (20000, 8, 400, 400, 7.0, 3, 5),
 ]
+# Feature widths that reach the blend instances no row above does (mrgs_launch_render_fwd / _bwd): S = 13 ... 23 and 16 take <24, false, 24>
+# (rows staged float by float; S = 24 itself takes the 16-byte instance), S = 9 takes <12, false, 12>.  Each also has to send pixels through
+# the exact-redo path of its instance (mrgs_redo_pixel<S_ROW>): test_parity_against_oracle asserts the count.  The count is a property of
+# the scene (the forward's decisions are deterministic): 5000 surfels of 16 pixels mark the number of pixels noted per row, where 3000 of
+# 6 pixels marked 0 ... 2.
+INSTANCE_CASES = [
+    (5000, 13, 97, 211, 16.0, 1, 3),      # odd stride, odd image size; 5 pixels redone
+    (5000, 23, 64, 64, 16.0, 2, 6),       # the widest odd stride; 7
+    (5000, 16, 64, 64, 16.0, 0, 4),       # a multiple of four that has no 16-byte instance of its own; 7
+    (5000, 9, 80, 72, 16.0, 3, 2),        # 7
+]
+CASES += INSTANCE_CASES
 
 
 def _map_ok(a, b, tol, absolute=False):
@@ -45,7 +57,8 @@ def _map_ok(a, b, tol, absolute=False):
     return (d <= tol).reshape(-1, *d.shape[-2:]).all(0), float(d.max())
 
 
-def compare_all(scene, cam, dev, sh_degree=3, scale_modifier=1.0, colors_precomp=None, bg=None, check_grads=True, pixel_allowance=0, features_live=0):
+def compare_all(scene, cam, dev, sh_degree=3, scale_modifier=1.0, colors_precomp=None, bg=None, check_grads=True, pixel_allowance=0, features_live=0,
+                features_misalign=False):
     """`pixel_allowance`: number of pixels that may sit outside the map tolerances.  Zero everywhere in the suite since round 4 (the
     kernels take the blend's decisions exactly); the parameter remains for developer builds that switch that off."""
     from oracle import raster_oracle as ro
@@ -54,7 +67,7 @@ def compare_all(scene, cam, dev, sh_degree=3, scale_modifier=1.0, colors_precomp
     orc = ro.render_scene(scene, cam, sh_degree=sh_degree, scale_modifier=scale_modifier, colors_precomp=colors_precomp, bg=bg)
     hr = HipRender(scene, cam, dev, sh_degree=sh_degree, scale_modifier=scale_modifier,
                    colors_precomp=None if colors_precomp is None else torch.as_tensor(colors_precomp), bg=None if bg is None else torch.as_tensor(bg),
-                   features_live=features_live)     # (features_live: the caller has zeroed the scene's padding channels; the oracle blends all of them)
+                   features_live=features_live, features_misalign=features_misalign)     # (features_live: the caller has zeroed the scene's padding channels; the oracle blends all of them)
     # ---- integer / geometry state: bit exact
     assert hr.num_rendered == orc.R
     np.testing.assert_array_equal(hr.radii.cpu().numpy(), orc.radii)
@@ -84,6 +97,7 @@ def compare_all(scene, cam, dev, sh_degree=3, scale_modifier=1.0, colors_precomp
         assert worst <= (tol if pixel_allowance == 0 else 5e-3), (name, worst)   # one pair at the alpha = 1/255 threshold: <= 3.9e-3 of a map's range
     assert int((~good).sum()) <= pixel_allowance, int((~good).sum())
     assert int(hr.contrib.abs().sum()) == 0   # out_contrib is allocated and returned but never written
+    hr.redo_pixels = int(hr.export("redo_list")[0])     # pixels the forward rendered again with the oracle's arithmetic (read before the backward frees the state)
     # ---- gradients
     if check_grads:
         g = upstream_grads(S, H, W)
@@ -122,7 +136,43 @@ def compare_all(scene, cam, dev, sh_degree=3, scale_modifier=1.0, colors_precomp
 @pytest.mark.parametrize("P,S,H,W,rpx,deg,view", CASES)
 def test_parity_against_oracle(gpu_device, P, S, H, W, rpx, deg, view):
     scene = make_shell_scene(P, S=S, seed=P + S, radius_px=rpx, image_size=max(H, W))
-    compare_all(scene, orbit_camera(view, H, W), gpu_device, sh_degree=deg)
+    hr = compare_all(scene, orbit_camera(view, H, W), gpu_device, sh_degree=deg)
+    if (P, S, H, W, rpx, deg, view) in INSTANCE_CASES:
+        _assert_redo_ran(hr, f"S = {S}")
+
+
+def _assert_redo_ran(hr, what):
+    """The forward marked pixels whose decisions sat inside their error bands and rendered them again with the oracle's arithmetic
+    (mrgs_redo_pixel of the instance that ran): the count the kernel leaves in its redo list."""
+    redo = hr.redo_pixels
+    print(f"{what}: {redo} of {hr.H * hr.W} pixels through the exact-redo path")
+    assert redo > 0, what
+
+
+# S, features_live, misaligned rows, P, H, W, radius_px, view (scene seed 23; behind each row the pixels its forward renders again)
+BLEND_INSTANCE_CASES = [
+    (12, 9, False, 6000, 176, 144, 7.0, 3),      # <8, true, 9>: the scene of test_padding_channels_left_out_of_the_blend; 3
+    (8, 0, True, 5000, 96, 80, 16.0, 1),         # <8, false, 8> at S = 8; 6
+    (12, 0, True, 5000, 80, 96, 16.0, 2),        # <12, false, 12> at S = 12; 8
+    (24, 0, True, 5000, 64, 64, 16.0, 4),        # <24, false, 24> at S = 24; 7
+    (12, 9, True, 5000, 80, 96, 16.0, 5),        # the padding hint without alignment: falls back to <12, false, 12>; 6
+]
+
+
+@pytest.mark.parametrize("S,live,misalign,P,H,W,rpx,view", BLEND_INSTANCE_CASES)
+def test_blend_instances_against_the_oracle(gpu_device, S, live, misalign, P, H, W, rpx, view):
+    """The blend instances that only a padding hint or a feature tensor off the 16-byte grid selects, forward and gradients against the C
+    oracle at zero pixel allowance: <8, true, 9> (twelve-float rows, nine live channels: the "pgsr" rows) and the three non-FV instances
+    at the widths that otherwise take a 16-byte instance (the rows start 4 bytes into a buffer).  The oracle blends all S channels; the
+    padding columns are zero in the scene."""
+    scene = make_shell_scene(P, S=S, seed=23, radius_px=rpx, image_size=max(H, W))
+    if live:
+        scene.features[:, live:] = 0.0
+    hr = compare_all(scene, orbit_camera(view, H, W), gpu_device, features_live=live, features_misalign=misalign)
+    if live:
+        assert float(hr.feature[live:].detach().abs().max()) == 0.0
+        assert float(hr.leaves["features"].grad[:, live:].abs().max()) == 0.0
+    _assert_redo_ran(hr, f"S = {S}, features_live = {live}, misaligned = {misalign}")
 
 
 def test_scale_modifier_background_and_precomputed_colours(gpu_device):

@@ -205,6 +205,150 @@ def test_render_surfel_matches_the_composed_oracle(gpu_device, indirect, srgb):
     assert ok, rows
 
 
+PGSR_SCENE = dict(P=3000, H=96, W=128, seed=1, view=1)      # conditioning: test_pgsr_scene_is_well_conditioned_for_the_unbiased_depth
+PGSR_CASES = [("a", True, False), ("b", False, False), ("c", True, True)]       # case, _FUSE_GLUE, opt.indirect (c: the epilogue does not apply)
+
+
+def _pgsr_loss(out, H, W, indirect, dev):
+    """_loss plus a fixed-weight sum over the flavour's blended plane distance."""
+    g = torch.Generator().manual_seed(17)
+    w = torch.rand(out["rend_distance"].shape, generator=g).to(out["rend_distance"].dtype).to(dev)
+    return _loss(out, H, W, indirect, dev) + (out["rend_distance"] * w).sum()
+
+
+def test_pgsr_scene_is_well_conditioned_for_the_unbiased_depth():
+    """The "pgsr" flavour's surf_depth is the blended plane distance divided by -(blended normal . pixel ray): a few grazing pixels can
+    dominate the max-norm of a gradient, and then fp32 arithmetic anywhere in front of them -- the reference's own included -- cannot hold
+    1e-4.  The scene of test_render_surfel_pgsr_matches_the_composed_oracle is measured here on the CPU: the reference's torch ops behind
+    the rasterizer (glue_oracle.pgsr_allmap8, compute_2dgs_normal_and_regularizations_reference) on the checker's all-map, under the
+    geometry terms of that test's loss, in float32 against float64: max-norm relative error of d loss / d all-map and of d loss / d blended
+    distance over the covered pixels (an uncovered pixel is 0 x inf = NaN in the torch ops; the rasterizer's backward never reads its upstream
+    gradient there).  Bound: a quarter of the gradient bar of 1e-4."""
+    from oracle import glue_oracle as go, render_oracle
+    P, H, W = PGSR_SCENE["P"], PGSR_SCENE["H"], PGSR_SCENE["W"]
+    pc, _base, _, _ = _models(P, H, W, seed=PGSR_SCENE["seed"])
+    cam = orbit_camera(PGSR_SCENE["view"], H, W)
+    pipe = SimpleNamespace(depth_ratio=0.0, debug=False)
+    with torch.no_grad():
+        op, sc, rot, feat = go.surfel_features_reference(pc, cam.camera_center.double())
+        feat = torch.cat((feat, go.get_distance(pc, cam)), -1)
+        _color, f, allmap, _radii = render_oracle._OracleRaster.apply(pc.get_xyz, torch.zeros_like(pc._xyz), op, pc.get_features, feat, sc, rot, cam,
+                                                                      pc.active_sh_degree, "fused")
+    covered = allmap[1] > 0
+    assert 0.2 < float(covered.double().mean()) < 1.0
+    res = {}
+    for dt in (torch.float64, torch.float32):
+        am, rd = allmap.detach().clone().to(dt).requires_grad_(True), f[-1:].detach().clone().to(dt).requires_grad_(True)
+        camd = cam._replace(world_view_transform=cam.world_view_transform.to(dt), full_proj_transform=cam.full_proj_transform.to(dt))
+        reg = go.compute_2dgs_normal_and_regularizations_reference(go.pgsr_allmap8(am, rd, camd), camd, pipe)
+        out = {k: torch.zeros(n, H, W, dtype=dt) for k, n in zip(MAP_KEYS, (3, 1, 3, 3, 3, 3, 1))}          # the maps the shading makes: no part here
+        out.update({"rend_alpha": reg["render_alpha"], "rend_normal": reg["render_normal"], "rend_dist": reg["render_dist"],
+                    "surf_depth": reg["surf_depth"], "surf_normal": reg["surf_normal"], "rend_distance": rd})
+        _pgsr_loss(out, H, W, False, "cpu").backward()
+        res[dt] = (am.grad.double()[:, covered], rd.grad.double()[:, covered])
+    for name, a, b in zip(("all-map", "blended distance"), res[torch.float64], res[torch.float32]):
+        assert bool(torch.isfinite(a).all()) and bool(torch.isfinite(b).all()), name
+        e = float((a - b).abs().max() / a.abs().max())
+        print(f"d loss / d {name}: the reference's ops in float32 are {e:.2e} from float64 (max-norm, covered pixels)")
+        assert e <= 2.5e-5, (name, e)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case,fused,indirect", PGSR_CASES)
+def test_render_surfel_pgsr_matches_the_composed_oracle(gpu_device, case, fused, indirect, monkeypatch):
+    """render_surfel(flag="pgsr") -- the flavour the reference ships -- against the composed checker, every map and every leaf gradient, as
+    test_render_surfel_matches_the_composed_oracle does for "2dgs".  The plane distance |n_cam . c_cam| is differentiated by hand in two
+    places: the glue epilogue of the rasterizer's per-gaussian backward (case a) and the glue's own backward kernel (case b; case c under
+    opt.indirect, where the mirror direction and the plane distance both send a gradient to the facing normal and the <8, true, 9> blend
+    instances run with live indirect channels).  The captured rows are twelve floats: columns 0..7 go to the checker's rasterizer as they
+    are, column 8 is compared with glue_oracle.get_distance in float64 -- which is what the checker rasterizes, and whose gradient reaches
+    the raw leaves by itself --, 9..11 are zero."""
+    import materialrefgs_amd.renderer as renderer_mod
+    from materialrefgs_amd.raytracing import RayTracer
+    from materialrefgs_amd.renderer import render_surfel
+    from oracle import glue_oracle, render_oracle
+    P, H, W = PGSR_SCENE["P"], PGSR_SCENE["H"], PGSR_SCENE["W"]
+    pc_o, base_o, pc_h, env = _models(P, H, W, seed=PGSR_SCENE["seed"], dev=gpu_device)
+    cam = orbit_camera(PGSR_SCENE["view"], H, W)
+    pipe = SimpleNamespace(depth_ratio=0.0, debug=False)
+    bg = torch.tensor([0.1, 0.2, 0.3])
+    mesh = None
+    if indirect:
+        v1, t1 = sphere_mesh(24, 36, 0.9)
+        v2, t2 = sphere_mesh(12, 16, 0.8)
+        v2 = v2 + np.array([0.0, 2.2, 0.0], dtype=np.float32)
+        mesh = (np.concatenate([v1, v2]), np.concatenate([t1, t2 + len(v1)]))
+        pc_h.ray_tracer = RayTracer(*mesh)
+    env.build_mips()
+    monkeypatch.setattr(renderer_mod, "_FUSE_GLUE", fused)
+    stash, glue = {}, renderer_mod.surfel_features
+
+    def capturing(pc_, campos_, **kw):
+        o = glue(pc_, campos_, **kw)
+        stash["o"] = [t_.detach().cpu().double() for t_ in o[:4]]
+        return o
+    renderer_mod.surfel_features = capturing
+    try:
+        out_h = render_surfel(cam.to(gpu_device), pc_h, pipe, bg.to(gpu_device), srgb=False, opt=SimpleNamespace(indirect=indirect), flag="pgsr")
+    finally:
+        renderer_mod.surfel_features = glue
+    vis_bits = out_h["visibility"].detach().cpu()[0] if indirect else None
+    rows = stash["o"][3]
+    assert rows.shape == (P, 12)
+    inter_o = [t_.clone().requires_grad_(True) for t_ in stash["o"][:3] + [rows[:, :8]]]
+    glue_f64 = glue_oracle.surfel_features_reference(pc_o, cam.camera_center.double())
+    for a_, b_ in zip(inter_o, glue_f64):                # the captured inputs ARE the glue's values, to fp32 rounding
+        assert float((a_ - b_).abs().max()) <= 2e-6 * max(1.0, float(b_.abs().max()))
+    dist_o = glue_oracle.get_distance(pc_o, cam)
+    dist_o.retain_grad()
+    assert float((rows[:, 8:9] - dist_o.detach()).abs().max()) <= 2e-6 * float(dist_o.abs().max())
+    assert float(rows[:, 9:].abs().max()) == 0.0
+    out_o = render_oracle.render_surfel_oracle(cam, pc_o, base_o, 8, pipe, bg, srgb=False, indirect=indirect, mesh=mesh, visibility_bits=vis_bits,
+                                               raster_inputs=tuple(inter_o), flag="pgsr", distance=dist_o)
+    assert set(out_o) - {"visibility_traced"} <= set(out_h), set(out_o) - set(out_h)
+    assert "rend_distance" in out_o and ("specular_weight" in out_h) == indirect
+    assert torch.equal(out_h["radii"].cpu(), out_o["radii"]) and torch.equal(out_h["visibility_filter"].cpu(), out_o["visibility_filter"])
+    if indirect:
+        vh, vo = out_h["visibility"].cpu()[0], out_o["visibility_traced"][0].float()
+        assert float((vh != vo).float().mean()) < 2e-3           # ray set-up rounding at silhouettes only
+        print(f"case {case}: occluded share {float((vo == 0).float().mean()):.4f}")
+        assert 0.02 < float((vo == 0).float().mean()) < 0.98
+    keys = MAP_KEYS + ("rend_distance",) + (("indirect_color", "direct_light", "indirect_light") if indirect else ())
+    for k in keys:                                          # (surf_depth: the flavour's unbiased depth)
+        a, b = out_h[k].detach().cpu().double(), out_o[k].detach()
+        scale = max(float(b.abs().max()), 1e-6)
+        tol = 2e-4 if k in ("surf_normal",) else 5e-5       # surf_normal: normalised cross product of depth differences
+        d = (a - b).abs()
+        if k == "rend_dist":                                # O(1e-5) values from O(1) terms: absolute bar (test_gpu_parity.DIST_ABS_TOL)
+            scale, tol = 1.0, 5e-6
+        if k == "rend_distance":                            # 5e-5 of its range
+            scale = float(b.max() - b.min())
+        bad = float((d > tol * scale).float().mean())
+        assert bad < (2e-3 if k == "surf_normal" else 1e-4), (k, float(d.max()), scale, bad)
+    if indirect:
+        w_h = out_h["specular_weight"].detach().cpu().double()
+        assert float((w_h - out_o["specular_weight"].detach()).abs().max()) < 5e-5
+    # ---- gradients of one scalar that reads every map, the blended plane distance included
+    _pgsr_loss(out_h, H, W, indirect, gpu_device).backward()
+    _pgsr_loss(out_o, H, W, indirect, "cpu").backward()
+    g_inter = [t_.grad for t_ in inter_o]
+    torch.autograd.backward(list(glue_f64), g_inter)      # ... on through the float64 glue to the raw leaves (the distance column went there by itself)
+    names = [n[1:] for n in PARAMS]
+    hip = {n: getattr(pc_h, "_" + n).grad.detach().cpu().numpy() for n in names}
+    total = {n: getattr(pc_o, "_" + n).grad.numpy() for n in names}
+    hip["env.base"], total["env.base"] = env.base.grad.detach().cpu().numpy(), base_o.grad.numpy()
+    hip["viewspace_points"], total["viewspace_points"] = out_h["viewspace_points"].grad.detach().cpu().numpy(), out_o["viewspace_points"].grad.numpy()
+    # the truth leg covers the plane distance: both of its pull-backs include get_distance under the gradient that arrived at the column
+    total["lit32"] = render_oracle.glue_lit32_leg([getattr(pc_o, n) for n in PARAMS], cam.camera_center, g_inter, total, distance=(cam, dist_o.grad))
+    rows_, ok = render_oracle.leaf_gradient_report(hip, total, names + ["env.base", "viewspace_points"], bar=1e-4)
+    print(f"case {case}:\n" + "\n".join(f"{n:18s} max-norm err {r_['err']:.2e}  max|g| {float(np.abs(total[n]).max()):.3e}  {r_['rule']}" +
+                                       (f" (fp32 torch glue {r_['lit32_err']:.2e})" if "lit32_err" in r_ else "") for n, r_ in rows_.items()))
+    assert ok, rows_
+    assert float(np.abs(dist_o.grad.numpy()).max()) > 0.0
+    if indirect:
+        assert float(np.abs(total["indirect_dc"]).max()) > 0.0 and float(np.abs(total["indirect_rest"]).max()) > 0.0
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("extra_reader,flag", [(False, "2dgs"), (True, "2dgs"), (False, "pgsr"), (True, "pgsr")])
 def test_glue_epilogue_equals_the_two_kernel_backward(gpu_device, extra_reader, flag, monkeypatch):

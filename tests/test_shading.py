@@ -309,6 +309,95 @@ def test_surfel_features_match_the_reference_ops(gpu_device):
             assert float((a - b).abs().max()) <= 1e-5 * max(1e-3, float(b.abs().max())), (P, zero_ind, k)
 
 
+PD_LEAVES = ("xyz", "scaling", "rotation", "opacity", "refl", "rough", "ori", "idc", "irest")     # the glue node's nine raw leaves, in its order
+PD_KINK = 1e-2              # |n_cam . c_cam| below this: the row sits on the kink of |.|, its plane distance takes no upstream gradient
+# (name, pass_xyz, the outputs that receive an upstream gradient; the others arrive at the node as None)
+PD_VARIANTS = [("four outputs", False, (0, 1, 2, 3)), ("five outputs", True, (0, 1, 2, 3, 4))] + \
+              [(f"output {i} alone", True, (i,)) for i in range(5)]
+
+
+def _plane_distance_case(P):
+    """Raw leaves, camera and upstream gradients of the plane-distance test for P rows (fixed per P), and the float64 checker's outputs:
+    (opacity, scales, rotations, [features 8 | plane distance | 0 0 0], centres) with glue_oracle.surfel_features_reference and
+    glue_oracle.get_distance.  Camera centre and view matrix come from ONE camera.  Returns the share of kink rows as well."""
+    from materialrefgs_amd.renderer import SurfelModel
+    from materialrefgs_amd.synthetic import orbit_camera
+    from oracle.glue_oracle import get_distance, surfel_features_reference
+    g = torch.Generator().manual_seed(1000 + P)
+    rnd = lambda *s: torch.randn(*s, generator=g)
+    raw = dict(xyz=rnd(P, 3) * 2, scaling=rnd(P, 2) * 0.5 - 2, rotation=rnd(P, 4), opacity=rnd(P, 1), refl=rnd(P, 1), rough=rnd(P, 1),
+               ori=rnd(P, 3), idc=rnd(P, 1, 3) * 0.5, irest=rnd(P, 15, 3) * 0.2)
+    cam = orbit_camera(3, 48, 64)
+
+    def model(dev, dtype):
+        t = {k: v.to(device=dev, dtype=dtype).clone().requires_grad_(True) for k, v in raw.items()}
+        pc = SurfelModel(t["xyz"], t["scaling"], t["rotation"], t["opacity"], torch.zeros(P, 1, 3, device=dev, dtype=dtype),
+                         torch.zeros(P, 15, 3, device=dev, dtype=dtype), refl_strength=t["refl"], roughness=t["rough"],
+                         ori_color=t["ori"], indirect_dc=t["idc"], indirect_rest=t["irest"])
+        return pc, [t[k] for k in PD_LEAVES]
+
+    pc_c, leaves_c = model("cpu", torch.float64)
+    op, sc, rot, feat = surfel_features_reference(pc_c, cam.camera_center.double())
+    outs_c = (op, sc, rot, torch.cat((feat, get_distance(pc_c, cam), torch.zeros(P, 3, dtype=torch.float64)), dim=-1), pc_c.get_xyz)
+    with torch.no_grad():       # the signed n_cam . c_cam of get_distance, float64
+        Wv = cam.world_view_transform.double()
+        d = pc_c.get_xyz - cam.camera_center.double()
+        signed = ((pc_c.get_normal(1.0, d / d.norm(dim=1, keepdim=True)) @ Wv[:3, :3]) * (pc_c.get_xyz @ Wv[:3, :3] + Wv[3, :3])).sum(-1)
+    kink = signed.abs() < PD_KINK
+    ups = [rnd(*o.shape).double() for o in outs_c]
+    ups[3][:, 9:] = 0.0
+    ups[3][kink, 8] = 0.0
+    return cam, model, leaves_c, outs_c, ups, float(kink.double().mean())
+
+
+def _grads_of(outs, leaves, ups, which):
+    got = torch.autograd.grad([outs[i] for i in which], leaves, [ups[i].to(outs[i].dtype) for i in which], retain_graph=True, allow_unused=True)
+    return [torch.zeros_like(t) if g_ is None else g_ for g_, t in zip(got, leaves)]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("P", [1, 63, 64, 65, 1000, 4097])
+def test_surfel_features_with_the_plane_distance_match_float64(gpu_device, P):
+    """mrgs_surfel_features_forward/backward with a view matrix (the "pgsr" rows: twelve floats, the plane distance |n_cam . c_cam| of
+    get_distance in column 8, zeros behind it) against the reference's torch ops in float64 on the CPU: glue_oracle.surfel_features_reference
+    next to glue_oracle.get_distance.  Forward: columns 0..7 as in the test above, column 8 within 2e-6 max(1, max|ref|) of the float64
+    distance, columns 9..11 exact zeros.  Backward, every raw leaf within 1e-5 max(1e-3, max|ref|), for: all four outputs with an upstream
+    gradient; all five with pass_xyz (the centres' own gradient joins inside the kernel); each of the five outputs alone (the others reach
+    the node as None: set_materialize_grads(False)).  The node writes into torch.empty_like buffers: NaN-filled tensors of the leaves'
+    shapes are allocated and dropped just before each backward, so that a leaf the kernel left unwritten reads NaN.  Rows within 1e-2 of
+    the kink of |.| (at most 1 % of the rows) take no upstream gradient on column 8; their forward value is compared all the same."""
+    from materialrefgs_amd.renderer import surfel_features
+    cam, model, leaves_c, outs_c, ups, kink_share = _plane_distance_case(P)
+    assert kink_share <= 0.01, kink_share
+    camd = cam.to(gpu_device)
+    worst = {}
+    for name, pass_xyz, which in PD_VARIANTS:
+        pc_g, leaves_g = model(gpu_device, torch.float32)
+        outs_g = surfel_features(pc_g, camd.camera_center, pass_xyz=pass_xyz, viewmatrix=camd.world_view_transform)
+        assert len(outs_g) == (5 if pass_xyz else 4)
+        for i, og in enumerate(outs_g):
+            a, b = og.detach().cpu().double(), outs_c[i].detach()
+            assert a.shape == b.shape, (name, i)
+            if i == 3:
+                assert float((a[:, :8] - b[:, :8]).abs().max()) <= 2e-6 * max(1.0, float(b[:, :8].abs().max())), name
+                assert float((a[:, 8] - b[:, 8]).abs().max()) <= 2e-6 * max(1.0, float(b[:, 8].abs().max())), (name, float((a[:, 8] - b[:, 8]).abs().max()))
+                assert float(a[:, 9:].abs().max()) == 0.0, name
+            else:
+                assert float((a - b).abs().max()) <= 2e-6 * max(1.0, float(b.abs().max())), (name, i)
+        want = _grads_of(outs_c, leaves_c, ups, which)
+        poison = [torch.full_like(t, float("nan")) for t in leaves_g]
+        del poison
+        torch.autograd.backward([outs_g[i] for i in which], [ups[i].float().to(gpu_device) for i in which])
+        for k, t, b in zip(PD_LEAVES, leaves_g, want):
+            assert t.grad is not None, (name, k)
+            a = t.grad.detach().cpu().double()
+            assert bool(torch.isfinite(a).all()), (P, name, k)
+            e = float((a - b).abs().max()) / max(1e-3, float(b.abs().max()))
+            worst[k] = max(worst.get(k, 0.0), e)
+            assert e <= 1e-5, (P, name, k, e)
+    print(f"P={P}: kink share {kink_share:.4f}; worst leaf errors " + ", ".join(f"{k} {e:.1e}" for k, e in worst.items()))
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("depth_ratio", [0.0, 0.3, 1.0])
 def test_fused_maps_match_the_reference_ops(gpu_device, depth_ratio):
