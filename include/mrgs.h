@@ -755,6 +755,23 @@ int mrgs_sh_grad_expand_surfel_rows(int32_t P, int32_t D, int32_t V, const float
                                     int64_t rgb_stride, const float* ind_rows, int64_t ind_stride, const float* campos_rows, int64_t campos_stride,
                                     float* g_features_dc, float* g_features_rest, float* g_indirect_dc, float* g_indirect_rest, void* stream);
 
+/* ---- initial scales of a point cloud ---------------------------------------------------------------------------------------
+ * Replaces simple_knn's distCUDA2 (submodules/simple-knn/simple_knn.cu:147-221, spatial.cu:14-26), called by
+ * GaussianModel.create_from_pcd (scene/gaussian_model.py:367, env_gaussian_model.py:147): out[i] = mean of the squared distances from
+ * points[i] to its three nearest OTHER points (other by index: a duplicate at another index is a neighbour at distance 0).
+ * A squared distance is (dx dx + dy dy) + dz dz in fp32, un-fused; out[i] = ((b0 + b1) + b2) / 3.0f over the three smallest, a missing
+ * neighbour counting as FLT_MAX (P = 1, 2: +inf; P = 3: ~1.1e38): a pure function of the input, bitwise repeatable, invariant under a
+ * permutation of the rows and bit-equal to the float32 brute force (the reference, compiled with nvcc's contraction, may differ by an
+ * ulp).  Any extent is served, zero on one, two or three axes included.  Rows with a non-finite coordinate, and their neighbours, get
+ * unspecified values; the call still completes inside its buffers.
+ * points [P,3] and out [P] are device pointers; ws (mrgs_knn_ws_bytes(P) <= 64 P + 1 MiB bytes, 16-byte aligned, contents arbitrary:
+ * the call clears what it needs) is scratch that may be reused once the call's kernels have run.  Everything is queued on `stream`;
+ * nothing is read back to the host.  MRGS_E_BAD_ARG (before any HIP call): P < 0, P >= 2^31, or a null / misaligned pointer with
+ * P > 0; MRGS_E_WORKSPACE: ws_bytes too small; P = 0 returns MRGS_OK and launches nothing.  mrgs_knn_ws_bytes is 0 outside
+ * 0 <= P < 2^31. */
+size_t mrgs_knn_ws_bytes(int64_t P);
+int mrgs_knn_mean_dist2(const float* points, int64_t P, float* out, void* ws, size_t ws_bytes, void* stream);
+
 /* Introspection used by the parity tests: copies of internal state in the reference's layouts.
  * which: 0 depths f32[P], 1 means2D f32[P,2], 2 transMat f32[P,9], 3 normal_opacity f32[P,4], 4 rgb f32[P,3],
  * 5 tiles_touched u32[P], 6 clamped u8[P,3], 7 point_list u32[R], 8 ranges u32[tiles,2], 9 final_T f32[3,H,W],

@@ -49,13 +49,23 @@ def _quat_from_z_to(n, spin, rng):
     return q / np.linalg.norm(q, axis=1, keepdims=True)
 
 
-def make_shell_scene(P: int, S: int = 0, seed: int = 0, radius_px: float = 7.0, image_size: int = 800,
-                     sh_degree_filled: int = 3, device: Optional[str] = None, scale_sigma: float = 0.35) -> Scene:
-    rng = np.random.default_rng(seed)
+def _shell_centres(rng, P):
+    """Unit directions and centres at radius 0.95 .. 1.05 along them: the first two draws of a shell scene."""
     d = rng.normal(size=(P, 3))
     d /= np.linalg.norm(d, axis=1, keepdims=True)
     r = rng.uniform(0.95, 1.05, size=(P, 1))
-    xyz = d * r
+    return d, d * r
+
+
+def shell_centres(P: int, seed: int = 0) -> np.ndarray:
+    """means3D of make_shell_scene(P, seed=seed) as a float32 array, without the rest of the scene (a point cloud of any size)."""
+    return np.ascontiguousarray(_shell_centres(np.random.default_rng(seed), P)[1], dtype=np.float32)
+
+
+def make_shell_scene(P: int, S: int = 0, seed: int = 0, radius_px: float = 7.0, image_size: int = 800,
+                     sh_degree_filled: int = 3, device: Optional[str] = None, scale_sigma: float = 0.35) -> Scene:
+    rng = np.random.default_rng(seed)
+    d, xyz = _shell_centres(rng, P)
     q = _quat_from_z_to(d, rng.uniform(0, 2 * math.pi, size=P), rng)
     focal = fov2focal(FOV, image_size)
     s_bar = radius_px * CAM_DISTANCE / (3.0 * focal)
