@@ -730,6 +730,62 @@ size_t mrgs_compact_ws_bytes(int64_t n_rows);
 int mrgs_compact_count(int64_t n_rows, const uint8_t* keep, void* ws, size_t ws_bytes, int64_t* count_dev, void* stream);
 int mrgs_compact_rows(int64_t n_rows, const uint8_t* keep, const void* ws, const MrgsCompactTensor* tensors, int32_t n_tensors, void* stream);
 
+/* ---- densify_and_prune and the densification statistics -------------------------------------------------------------------
+ * Replaces GaussianModel.densify_and_prune (scene/gaussian_model.py:975-1057: clone + cat, split + cat + prune, final prune) and the two
+ * per-iteration statistics lines (add_densification_stats :1059-1061 and `max_radii2D[visibility_filter] = max(...)` of the training
+ * loops).  Everything the three stages decide follows per SOURCE row from accum, denom, the two raw scalings and the raw opacity:
+ *   g = accum / denom (IEEE, NaN -> 0), s = exp(scaling_raw), o = sigmoid(opacity_raw), t = percent_dense_extent
+ *   clone  = |g| >= max_grad and max(s) <= t;          split = g >= max_grad and max(s) > t        (disjoint; max_grad > 0)
+ *   gone(x) = o < min_opacity or (world_size_limit > 0 and x > world_size_limit)
+ *   original kept: not split and not gone(max(s));      clone emitted: clone and not gone(max(s));
+ *   N children emitted: split and not gone(max(s_child)), s_child = exp(log(s / (0.8 N)))
+ * (the reference's third prune term, max_radii2D > max_screen_size, reads a vector that densification_postfix has zeroed: it never fires).
+ * Output rows: kept originals in row order, then clones in row order, then child 0 of every split row in row order, then child 1, ...
+ *
+ * mrgs_densify_classify writes a class byte per row and the per-block offsets of the three segments into ws (mrgs_densify_ws_bytes) and
+ * {n_keep, n_clone, n_child} (n_child = split rows with surviving children, i.e. children per k) to counts_dev (device int64[3]).  The
+ * caller reads those 24 bytes once -- the only synchronisation --, allocates destinations of n_keep + n_clone + N n_child rows and calls
+ * mrgs_densify_emit with the same cfg / ws and the counts: one launch per MRGS_COMPACT_MAX_TENSORS tensors streams every source once.
+ * Roles: COPY every output row is its source row; MOMENT kept originals are copied, every new row is zero; XYZ ([.,3]) a child gets
+ * xyz + R(normalize(rotation_raw)) (s_x z0, s_y z1, 0); SCALING ([.,2]) a child gets log(exp(scaling_raw) / (0.8 N)).
+ * z0, z1: noise[(row * N + k) * 2 + {0,1}] when `noise` (device fp32 [P,N,2], indexed by SOURCE row) is given; otherwise Philox4x32-10
+ * with key (seed low word, seed high word) and counter (row low word, row high word, k, 0): with x0, x1 its first two output words,
+ * u_i = ((x_i >> 8) + 1) 2^-24 in (0, 1], z0 = sqrt(-2 ln u0) cos(2 pi u1), z1 = sqrt(-2 ln u0) sin(2 pi u1).  Stateless, independent
+ * of the grid, nothing drawn for rows that are not split.
+ * Codes, all before any launch: MRGS_E_BAD_ARG for a wrong struct_size, P < 0, N outside 1..8, max_grad not > 0, a NULL pointer with
+ * P > 0 (a dst may be NULL when the three counts are zero: an empty destination has no address), ws too small or not 4-byte aligned, row_floats outside 0..2^20, an XYZ row not 3 or a SCALING row not 2 wide, negative counts or counts beyond P;
+ * MRGS_E_UNSUPPORTED when P max(2, N) >= 2^31; P = 0 returns MRGS_OK, launches nothing and writes nothing (counts_dev included). */
+#define MRGS_DENSIFY_COPY 0
+#define MRGS_DENSIFY_MOMENT 1
+#define MRGS_DENSIFY_XYZ 2
+#define MRGS_DENSIFY_SCALING 3
+typedef struct MrgsDensifyConfig {
+    uint32_t struct_size;            /* = sizeof(MrgsDensifyConfig); checked like MrgsRasterConfig::struct_size */
+    int32_t N;                       /* children per split row, 1..8 (the reference: 2) */
+    int64_t P;                       /* rows before the call */
+    float max_grad, min_opacity, percent_dense_extent;
+    float world_size_limit;          /* 0.1 * extent when max_screen_size is truthy, <= 0: that term is off */
+    const float* xyz_raw;            /* [P,3]  read by mrgs_densify_emit when a table entry has role XYZ */
+    const float* scaling_raw;        /* [P,2]  ... role XYZ or SCALING */
+    const float* rotation_raw;       /* [P,4]  (w,x,y,z), un-normalised; role XYZ */
+} MrgsDensifyConfig;
+typedef struct MrgsDensifyTensor {
+    const float* src;      /* [P, row_floats] */
+    float* dst;            /* [n_keep + n_clone + N n_child, row_floats] */
+    int32_t row_floats;
+    int32_t role;          /* MRGS_DENSIFY_* */
+} MrgsDensifyTensor;
+size_t mrgs_densify_ws_bytes(int64_t P);
+int mrgs_densify_classify(const MrgsDensifyConfig* cfg, const float* accum, const float* denom, const float* scaling_raw,
+                          const float* opacity_raw, void* ws, size_t ws_bytes, int64_t* counts_dev, void* stream);
+int mrgs_densify_emit(const MrgsDensifyConfig* cfg, const void* ws, const int64_t* counts_host, const MrgsDensifyTensor* tensors,
+                      int32_t n_tensors, uint64_t seed, const float* noise, void* stream);
+/* For rows with visible[i] != 0: accum[i] += ||grad[i, 0:3]||_2 (all three columns, as the reference's line), denom[i] += 1 and, when
+ * radii and max_radii are both given, max_radii[i] = max(max_radii[i], (float)radii[i]).  In place, one launch, nothing read back.
+ * grad fp32 [P,3], visible bytes [P], radii int32 [P] or NULL, accum / denom / max_radii fp32 [P] (max_radii may be NULL). */
+int mrgs_densify_stats(int64_t P, const float* grad, const uint8_t* visible, const int32_t* radii, float* accum, float* denom,
+                       float* max_radii, void* stream);
+
 /* View-parallel training (materialrefgs_amd/dist.py): sum over V views of the SH colour gradients from each view's masked colour
  * gradient dRGB_v = dL/dsh_v[:,0,:] / SH_C0 and camera centre: dL_dsh[p][k][c] = sum_v B_k(normalize(means3D[p] - campos_v)) dRGB_v[p][c]
  * for k < (D+1)^2, 0 beyond (backward.cu:22-141).  gathered = V rows of row_stride floats, row v = [dRGB_v (P x 3) | campos_v (3)]

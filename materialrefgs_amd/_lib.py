@@ -119,6 +119,19 @@ class MrgsCompactTensor(ctypes.Structure):
     _fields_ = [("src", c_void_p), ("dst", c_void_p), ("row_floats", c_int32)]
 
 
+MRGS_DENSIFY_COPY, MRGS_DENSIFY_MOMENT, MRGS_DENSIFY_XYZ, MRGS_DENSIFY_SCALING = 0, 1, 2, 3
+
+
+class MrgsDensifyConfig(_Sized):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("N", c_int32), ("P", c_int64), ("max_grad", c_float), ("min_opacity", c_float),
+                ("percent_dense_extent", c_float), ("world_size_limit", c_float), ("xyz_raw", c_void_p), ("scaling_raw", c_void_p),
+                ("rotation_raw", c_void_p)]
+
+
+class MrgsDensifyTensor(ctypes.Structure):
+    _fields_ = [("src", c_void_p), ("dst", c_void_p), ("row_floats", c_int32), ("role", c_int32)]
+
+
 class MrgsKernelTimes(ctypes.Structure):
     _fields_ = [(n, c_float) for n in ("preprocess_ms", "sort_ms", "duplicate_ms", "render_fwd_ms", "render_bwd_ms",
                                        "preprocess_bwd_ms")]
@@ -228,6 +241,12 @@ SYMBOLS = {
     "mrgs_compact_ws_bytes": (c_size_t, [c_int64]),
     "mrgs_compact_count": (ctypes.c_int, [c_int64, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
     "mrgs_compact_rows": (ctypes.c_int, [c_int64, c_void_p, c_void_p, ctypes.POINTER(MrgsCompactTensor), c_int32, c_void_p]),
+    "mrgs_densify_ws_bytes": (c_size_t, [c_int64]),
+    "mrgs_densify_classify": (ctypes.c_int, [ctypes.POINTER(MrgsDensifyConfig), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                             c_void_p, c_void_p]),
+    "mrgs_densify_emit": (ctypes.c_int, [ctypes.POINTER(MrgsDensifyConfig), c_void_p, ctypes.POINTER(c_int64),
+                                         ctypes.POINTER(MrgsDensifyTensor), c_int32, ctypes.c_uint64, c_void_p, c_void_p]),
+    "mrgs_densify_stats": (ctypes.c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "mrgs_knn_ws_bytes": (c_size_t, [c_int64]),
     "mrgs_knn_mean_dist2": (ctypes.c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
     "mrgs_mark_visible": (ctypes.c_int, [c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
