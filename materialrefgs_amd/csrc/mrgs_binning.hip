@@ -25,6 +25,7 @@
 // Five short launches and ~45 MB of traffic at C2 (P = 300k, R = 1.15 M) where the radix pipeline had eleven launches and
 // 116 MB; point_list, ranges and n_contrib stay bit-identical to the reference's 64-bit-key sort (tests/test_gpu_parity.py).
 #include "mrgs_blend_math.h"
+#include "mrgs_wave.h"
 
 #define BIN_THREADS 1024
 #define SORT_SMALL_CAP 4096       // keys per tile the bucket sort of tile_sort_kernel holds in LDS
@@ -33,9 +34,6 @@
 #define SORT_BIG_CAP 16384
 
 namespace {
-
-__device__ __forceinline__ uint32_t ld_agent(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void st_agent(uint32_t* p, uint32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 // Visits every tile of the rectangles of one wave's surfels: lanes with few tiles walk them serially, a surfel with many tiles
 // (a heavy-tailed scene has splats of hundreds of tiles) is spread over the 64 lanes.  own() / take(src) switch the caller's

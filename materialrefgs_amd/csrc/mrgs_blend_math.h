@@ -12,6 +12,7 @@
 // T > 0.5) are taken exactly all the same -- "Exact decisions" below.
 #pragma once
 #include "mrgs_internal.h"
+#include "mrgs_wave.h"
 
 #define MRGS_ALPHA_MIN (1.0f / 255.0f)
 #define MRGS_T_MIN 0.0001f
@@ -434,12 +435,4 @@ __device__ __forceinline__ void mrgs_stage_wait()
 {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_wave_barrier();
-}
-
-// wave64 sum with DPP; every lane of the wave must be active.
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ float mrgs_dpp_add(float v)
-{
-    const int moved = __builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, ROW_MASK, 0xf, false);
-    return v + __int_as_float(moved);
 }

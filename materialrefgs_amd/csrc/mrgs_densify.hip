@@ -14,6 +14,7 @@
 // (source row, child): no state, no dependence on the grid, nothing drawn for rows that are not split.
 //   stats     one thread per row, in place: 17 B read and up to 12 B written per visible row, 1 B per invisible one.
 #include "mrgs_internal.h"
+#include "mrgs_wave.h"
 
 namespace {
 
@@ -26,23 +27,6 @@ constexpr unsigned long long FIELD_MASK = (1ull << FIELD) - 1;
 __device__ __forceinline__ unsigned long long pack_counts(unsigned cls)
 {
     return (unsigned long long)(cls & 1u) | ((unsigned long long)((cls >> 1) & 1u) << FIELD) | ((unsigned long long)((cls >> 2) & 1u) << (2 * FIELD));
-}
-
-__device__ __forceinline__ unsigned long long block_exclusive_scan_256(unsigned long long v, unsigned long long* s_wave, unsigned long long& total)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned long long inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned long long n = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += n;
-    }
-    if (lane == 63) s_wave[wave] = inc;
-    __syncthreads();
-    unsigned long long base = 0;
-    for (int w = 0; w < wave; ++w) base += s_wave[w];
-    total = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
-    return base + inc - v;
 }
 
 struct ClassifyArgs {

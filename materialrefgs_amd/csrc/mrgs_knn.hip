@@ -15,7 +15,7 @@
 //
 // Everything below only prunes.  Six steps on the caller's stream (one memset, ten launches, five of them the sort's), no host read, no
 // allocation:
-//   1. knn_bounds_kernel   extent of the finite coordinates (per-block partial rows, the last block folds them: st_aabb_kernel's shape)
+//   1. knn_bounds_kernel   extent of the finite coordinates (per-block partial rows, the last block folds them: grid_max6_last_block_folds)
 //   2. knn_morton_kernel   30-bit Morton key (10 bits per axis; an axis of zero extent gets code 0, the reference divides by zero there:
 //                          simple_knn.cu:56-58), value = row index; the float -> integer conversion is clamped first, a non-finite
 //                          coordinate lands in cell 0
@@ -41,6 +41,7 @@
 #include <cstdint>
 
 #include "mrgs_internal.h"
+#include "mrgs_wave.h"
 
 namespace {
 
@@ -72,44 +73,11 @@ KnnWs knn_ws(int64_t P)
     return w;
 }
 
-__device__ __forceinline__ uint32_t ord_f(float f)          // order-preserving float -> uint
-{
-    const uint32_t u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float unord_f(uint32_t u)
-{
-    return __uint_as_float((u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u);
-}
-__device__ __forceinline__ uint32_t ld_agent_u(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void st_agent_u(uint32_t* p, uint32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-__device__ __forceinline__ uint32_t wave_max_u(uint32_t v)
-{
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, s));
-    return v;
-}
-__device__ __forceinline__ float wave_max_f(float v)
-{
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) v = fmaxf(v, __shfl_xor(v, s));
-    return v;
-}
-__device__ __forceinline__ float wave_min_f(float v)
-{
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) v = fminf(v, __shfl_xor(v, s));
-    return v;
-}
-
 // bounds[k] = max ord(x_k), bounds[3 + k] = max ~ord(x_k) over the finite coordinates (a non-finite one is left out: it is clamped into
-// the grid later).  One partial row per block, folded by the last block to finish (see st_aabb_kernel in mrgs_surfel_trace.hip).
+// the grid later).  One partial row per block, folded by the last block to finish (grid_max6_last_block_folds, as st_aabb_kernel of mrgs_surfel_trace.hip).
 __global__ __launch_bounds__(256) void knn_bounds_kernel(int P, const float* __restrict__ pts, uint32_t* __restrict__ partial,
                                                          uint32_t* __restrict__ ticket, uint32_t* __restrict__ bounds)
 {
-    __shared__ uint32_t red[4][6];
-    __shared__ bool last;
     uint32_t ext[6] = {0, 0, 0, 0, 0, 0};
     for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < P; p += (int64_t)gridDim.x * 256) {
         const float* q = pts + (size_t)p * 3;
@@ -119,42 +87,7 @@ __global__ __launch_bounds__(256) void knn_bounds_kernel(int P, const float* __r
             if (fabsf(v) <= FLT_MAX) { ext[k] = max(ext[k], ord_f(v)); ext[3 + k] = max(ext[3 + k], ~ord_f(v)); }
         }
     }
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-        const uint32_t m = wave_max_u(ext[k]);
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][k] = m;
-    }
-    __syncthreads();
-    if (threadIdx.x < 6) {
-        const int k = threadIdx.x;
-        st_agent_u(partial + blockIdx.x * 6 + k, max(max(red[0][k], red[1][k]), max(red[2][k], red[3][k])));
-    }
-    __threadfence();
-    __syncthreads();
-    if (threadIdx.x == 0) last = atomicAdd(ticket, 1u) == gridDim.x - 1;
-    __syncthreads();
-    if (!last) return;
-    __threadfence();
-    uint32_t mine[6];                      // thread b folds block b's row (gridDim.x <= 256 = blockDim.x)
-#pragma unroll
-    for (int k = 0; k < 6; ++k) mine[k] = threadIdx.x < gridDim.x ? ld_agent_u(partial + threadIdx.x * 6 + k) : 0u;
-    __syncthreads();                       // `red` is reused
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-        const uint32_t m = wave_max_u(mine[k]);
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][k] = m;
-    }
-    __syncthreads();
-    if (threadIdx.x < 6) bounds[threadIdx.x] = max(max(red[0][threadIdx.x], red[1][threadIdx.x]), max(red[2][threadIdx.x], red[3][threadIdx.x]));
-}
-
-__device__ __forceinline__ uint32_t spread10(uint32_t v)      // 10 bits -> every third bit
-{
-    v = (v | (v << 16)) & 0x030000FFu;
-    v = (v | (v << 8)) & 0x0300F00Fu;
-    v = (v | (v << 4)) & 0x030C30C3u;
-    v = (v | (v << 2)) & 0x09249249u;
-    return v;
+    grid_max6_last_block_folds(ext, partial, ticket, bounds);
 }
 
 __global__ __launch_bounds__(256) void knn_morton_kernel(int P, const float* __restrict__ pts, const uint32_t* __restrict__ bounds,
@@ -195,7 +128,7 @@ __global__ __launch_bounds__(64 * KNN_WAVES) void knn_gather_kernel(int P, int L
         lo[0] = hi[0] = x; lo[1] = hi[1] = y; lo[2] = hi[2] = z;
     }
 #pragma unroll
-    for (int k = 0; k < 3; ++k) { lo[k] = wave_min_f(lo[k]); hi[k] = wave_max_f(hi[k]); }
+    for (int k = 0; k < 3; ++k) { lo[k] = wave_shfl_min(lo[k]); hi[k] = wave_shfl_max(hi[k]); }
     if (lane == 0) {
         leafbox[2 * (size_t)leaf] = make_float4(lo[0], lo[1], lo[2], 0.f);
         leafbox[2 * (size_t)leaf + 1] = make_float4(hi[0], hi[1], hi[2], 0.f);
@@ -209,8 +142,8 @@ __global__ __launch_bounds__(64) void knn_top_kernel(int L, const float4* __rest
     const int l = blockIdx.x * 64 + lane;
     float4 lo = make_float4(INFINITY, INFINITY, INFINITY, 0.f), hi = make_float4(-INFINITY, -INFINITY, -INFINITY, 0.f);
     if (l < L) { lo = leafbox[2 * (size_t)l]; hi = leafbox[2 * (size_t)l + 1]; }
-    lo.x = wave_min_f(lo.x); lo.y = wave_min_f(lo.y); lo.z = wave_min_f(lo.z);
-    hi.x = wave_max_f(hi.x); hi.y = wave_max_f(hi.y); hi.z = wave_max_f(hi.z);
+    lo.x = wave_shfl_min(lo.x); lo.y = wave_shfl_min(lo.y); lo.z = wave_shfl_min(lo.z);
+    hi.x = wave_shfl_max(hi.x); hi.y = wave_shfl_max(hi.y); hi.z = wave_shfl_max(hi.z);
     if (lane == 0) { topbox[2 * (size_t)blockIdx.x] = lo; topbox[2 * (size_t)blockIdx.x + 1] = hi; }
 }
 
@@ -278,7 +211,7 @@ __global__ __launch_bounds__(64 * KNN_WAVES) void knn_search_kernel(int P, int L
         const int ncnt = min(64, P - (base + 64));
         knn_tile<false>(sorted[base + 64 + min(lane, ncnt - 1)], ncnt, lane, px, py, pz, b0, b1, b2);
     }
-    float R = wave_max_f(valid ? b2 : 0.f);                           // no lane of the wave needs anything at this distance or beyond
+    float R = wave_shfl_max(valid ? b2 : 0.f);                           // no lane of the wave needs anything at this distance or beyond
     const float4 qlo = leafbox[2 * (size_t)leaf], qhi = leafbox[2 * (size_t)leaf + 1];
     for (int t0 = 0; t0 < T; t0 += 64) {
         const int t = t0 + lane;
@@ -306,7 +239,7 @@ __global__ __launch_bounds__(64 * KNN_WAVES) void knn_search_kernel(int P, int L
                 const int cbase = (tt * 64 + k) * 64;
                 const int ccnt = min(64, P - cbase);
                 knn_tile<false>(sorted[cbase + min(lane, ccnt - 1)], ccnt, lane, px, py, pz, b0, b1, b2);
-                R = wave_max_f(valid ? b2 : 0.f);
+                R = wave_shfl_max(valid ? b2 : 0.f);
             }
         }
     }

@@ -11,6 +11,7 @@
 //                     pixel values into dL/dimage; L1 sign term, normal and distortion gradients are added in the same pass.
 // Zero padding as F.conv2d(padding=5): pixels outside the image count as 0 in the moments and carry no derivative.
 #include "mrgs_internal.h"
+#include "mrgs_wave.h"
 
 namespace {
 
@@ -26,13 +27,6 @@ struct LossArgs {
     float w[2 * LR + 1];
     float lambda_dssim, lambda_normal, lambda_dist;
 };
-
-__device__ __forceinline__ float wave_sum(float v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 __global__ __launch_bounds__(256) void loss_fwd_kernel(LossArgs a, const float* __restrict__ img, const float* __restrict__ gt,
                                                         const float* __restrict__ rn, const float* __restrict__ sn,
@@ -136,7 +130,7 @@ __global__ __launch_bounds__(256) void loss_fwd_kernel(LossArgs a, const float* 
         }
     }
 #pragma unroll
-    for (int k = 0; k < 5; ++k) part[k] = wave_sum(part[k]);
+    for (int k = 0; k < 5; ++k) part[k] = wave_shfl_sum(part[k]);
     if ((tid & 63) == 0)
 #pragma unroll
         for (int k = 0; k < 5; ++k) red[tid >> 6][k] = part[k];

@@ -10,6 +10,7 @@
 // one pixel per lane, channel-first maps read and written coalesced.  The backward of the finite-difference normals is a
 // gather (each pixel recomputes the four neighbouring normals it contributed to): deterministic, no atomics.
 #include "mrgs_internal.h"
+#include "mrgs_model_math.h"
 
 namespace {
 
@@ -280,17 +281,6 @@ __global__ void __launch_bounds__(256) surfel_maps_bwd_kernel(MapsFrameDev f, co
 }
 
 // ---- compositing ----------------------------------------------------------------------------------------------
-__device__ __forceinline__ float lin2srgb(float x)
-{
-    const float eps = 1.1920928955078125e-07f;
-    return x <= 0.0031308f ? (323.0f / 25.0f) * x : (211.0f * powf(fmaxf(x, eps), 5.0f / 12.0f) - 11.0f) / 200.0f;
-}
-__device__ __forceinline__ float lin2srgb_grad(float x)
-{
-    const float eps = 1.1920928955078125e-07f;
-    if (x <= 0.0031308f) return 323.0f / 25.0f;
-    return x >= eps ? (211.0f / 200.0f) * (5.0f / 12.0f) * powf(x, -7.0f / 12.0f) : 0.0f;
-}
 
 __global__ void __launch_bounds__(256) surfel_composite_fwd_kernel(int HW, int srgb, const float* __restrict__ base, const float* __restrict__ refl,
                                                                    const float* __restrict__ spec, const float* __restrict__ alpha,

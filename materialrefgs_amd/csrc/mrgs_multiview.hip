@@ -22,6 +22,7 @@
 // warp_ncc_bwd, described where they stand at the end of the file.
 // The file is compiled with -ffp-contract=off: the tap positions of the backward kernels repeat the forward's arithmetic bit for bit.
 #include "mrgs_internal.h"
+#include "mrgs_wave.h"
 
 namespace {
 
@@ -466,17 +467,6 @@ __device__ __forceinline__ float sgn(float x) { return x > 0.f ? 1.f : (x < 0.f 
 __device__ __forceinline__ float Lf(float d) { return d < 0.2f ? 0.2f * (d / 0.2f) * (d / 0.2f) * (d / 0.2f) : d + (expf(5.f * (d - 0.2f)) - 1.f) / 5.f; }
 __device__ __forceinline__ float dLf(float d) { return d < 0.2f ? 3.f * (d / 0.2f) * (d / 0.2f) : 1.f + expf(5.f * (d - 0.2f)); }
 
-__device__ __forceinline__ float wsum(float v)
-{
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ float wmin(float v)
-{
-    for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-
 __global__ __launch_bounds__(WB) void warp_patch_fwd(WarpArgs a, WarpWs w, Maps m, const float* __restrict__ camv,
                                                      const float* __restrict__ camn, const float* __restrict__ weight)
 {
@@ -515,7 +505,7 @@ __global__ __launch_bounds__(WB) void warp_patch_fwd(WarpArgs a, WarpWs w, Maps 
             sr1 = fabsf(rv - mn); sr2 = fabsf(rn - mn);
         }
     }
-    sb = wsum(sb); sM = wsum(sM); sm1 = wsum(sm1); sm2 = wsum(sm2); sr1 = wsum(sr1); sr2 = wsum(sr2); fg = wmin(fg);
+    sb = wave_shfl_sum(sb); sM = wave_shfl_sum(sM); sm1 = wave_shfl_sum(sm1); sm2 = wave_shfl_sum(sm2); sr1 = wave_shfl_sum(sr1); sr2 = wave_shfl_sum(sr2); fg = wave_shfl_min(fg);
     if (lane < 9) w.homog[(size_t)s * 9 + lane] = Hs[lane];
     if (lane == 0) {
         const float P = (float)a.P, wt = weight[p];
@@ -869,12 +859,6 @@ size_t ncc_layout(int H, int W, int k, NccWs* n, char* base)
     return o;
 }
 
-__device__ __forceinline__ double wsumd(double v)
-{
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 struct NccIn {
     const float *normal_v, *dist_v, *metal_v, *metal_n, *grey_v, *grey_n, *camv, *camn, *weight;
     const int32_t* samples;
@@ -959,9 +943,9 @@ __global__ __launch_bounds__(WB) void warp_ncc_fwd(WarpArgs a, NccIn in, NccWs n
         }
     }
     const double P = (double)a.P;
-    const double rbar = wsumd(r) / P, qbar = wsumd(q) / P, m_s = wsumd(mv) / P + wsumd(mn) / P;
+    const double rbar = wave_shfl_sum(r) / P, qbar = wave_shfl_sum(q) / P, m_s = wave_shfl_sum(mv) / P + wave_shfl_sum(mn) / P;
     const double rc = tap ? r - rbar : 0.0, qc = tap ? q - qbar : 0.0;
-    const double cross = wsumd(rc * qc), var_r = wsumd(rc * rc), var_q = wsumd(qc * qc);
+    const double cross = wave_shfl_sum(rc * qc), var_r = wave_shfl_sum(rc * rc), var_q = wave_shfl_sum(qc * qc);
     const double D = var_r * var_q + 1e-8;
     const double raw = 1.0 - cross * cross / D;
     const double ncc = raw < 0.0 ? 0.0 : (raw > 2.0 ? 2.0 : raw);
@@ -971,7 +955,7 @@ __global__ __launch_bounds__(WB) void warp_ncc_fwd(WarpArgs a, NccIn in, NccWs n
     const double al_ = 2.0 * cross / D, be_ = 2.0 * cross * cross * var_r / (D * D);
     const double c = (ok && use && raw >= 0.0 && raw <= 2.0) ? -(al_ * rc - be_ * qc) * dq : 0.0;
     double g[4];
-    for (int i = 0; i < 4; ++i) g[i] = wsumd(c != 0.0 ? c * e[i] : 0.0);
+    for (int i = 0; i < 4; ++i) g[i] = wave_shfl_sum(c != 0.0 ? c * e[i] : 0.0);
     if (lane == 0) {
         n.val[s] = use ? ncc * (double)wt : 0.0;
         n.use[s] = (uint8_t)use;

@@ -11,6 +11,7 @@
 //   param      <- param - step_size * exp_avg / (sqrt(exp_avg_sq) / sqrt(1 - beta2^t) + eps),   step_size = lr / (1 - beta1^t)
 // (torch/optim/adam.py _single_tensor_adam, non-capturable, amsgrad = False, weight_decay = 0, maximize = False).
 #include "mrgs_internal.h"
+#include "mrgs_wave.h"
 
 namespace {
 
@@ -129,24 +130,6 @@ struct CompactTable {
     float* dst[MRGS_COMPACT_MAX_TENSORS];
     int row_floats[MRGS_COMPACT_MAX_TENSORS];
 };
-
-__device__ __forceinline__ unsigned block_exclusive_scan_256(unsigned v, unsigned* s_wave, unsigned& total)
-{
-    // v = this thread's count; returns the exclusive prefix over the 256 threads of the workgroup
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned n = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += n;
-    }
-    if (lane == 63) s_wave[wave] = inc;
-    __syncthreads();
-    unsigned base = 0;
-    for (int w = 0; w < wave; ++w) base += s_wave[w];
-    total = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
-    return base + inc - v;
-}
 
 __global__ __launch_bounds__(256) void compact_count_kernel(long long n, const uint8_t* __restrict__ keep, unsigned* __restrict__ block_count)
 {

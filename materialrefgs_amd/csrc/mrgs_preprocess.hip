@@ -12,14 +12,13 @@
 // kernels are bandwidth-trivial (~320 B/gaussian), so the un-fused arithmetic costs nothing measurable.
 // The 35 camera floats are read from the caller's device tensors through wave-uniform (scalar) loads.
 #include "mrgs_internal.h"
+#include "mrgs_model_math.h"
 
-__device__ __constant__ float kSH_C0 = 0.28209479177387814f;
-__device__ __constant__ float kSH_C1 = 0.4886025119029199f;
-__device__ __constant__ float kSH_C2[5] = {1.0925484305920792f, -1.0925484305920792f, 0.31539156525252005f,
-                                           -1.0925484305920792f, 0.5462742152960396f};
-__device__ __constant__ float kSH_C3[7] = {-0.5900435899266435f, 2.890611442640554f, -0.4570457994644658f,
-                                           0.3731763325901154f,  -0.4570457994644658f, 1.445305721320277f,
-                                           -0.5900435899266435f};
+// external linkage on purpose (see mrgs_model_math.h): the numbers come from its lists
+__device__ __constant__ float kSH_C0 = MRGS_SH_C0;
+__device__ __constant__ float kSH_C1 = MRGS_SH_C1;
+__device__ __constant__ float kSH_C2[5] = MRGS_SH_C2;
+__device__ __constant__ float kSH_C3[7] = MRGS_SH_C3;
 
 __device__ __forceinline__ int f2i_sat(float v)
 {
@@ -614,52 +613,35 @@ struct GlueBwd {
     float *d_xyz, *d_scaling, *d_rotation, *d_opacity, *d_refl, *d_rough, *d_ori_color, *d_indirect_dc, *d_indirect_rest;
     const float* plane_view;        // "pgsr" (rows of 12 floats, channel 8 = get_distance): the camera's world_view_transform as stored, else NULL
 };
-__device__ __forceinline__ float glue_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }     // mrgs_surfel.hip's sigmoidf
 
-// "pgsr": the plane distance |n_cam . c_cam| (gaussian_renderer/envgs_renderer.py:30-38; mrgs_surfel.hip: make_frame, plane_distance) sends its
-// gradient gd to the raw rotation (through the facing unit normal = third column of R(q / |q|), flipped towards the camera) and to the
-// centre: d_q[4] is ADDED to, d_p[3] is set.  The formulas of surfel_features_bwd_kernel with a zero gradient at the mirror direction.
+// "pgsr": the plane distance |n_cam . c_cam| (gaussian_renderer/envgs_renderer.py:30-38) sends its gradient gd to the raw rotation (through the
+// facing unit normal = third column of R(q / |q|), flipped towards the camera) and to the centre: d_q[4] is ADDED to, d_p[3] is set.
+// What surfel_features_bwd_kernel computes with a zero gradient at the mirror direction, from the same make_frame, plane_distance and
+// frame_nr_bwd (mrgs_model_math.h); the two unit-vector steps between them are three lines each and written out in both places.
 __device__ __forceinline__ void glue_plane_distance_bwd(const float* __restrict__ Wv, const float (&p)[3], const float4 q, const float* __restrict__ campos,
                                                         float gd, float (&d_q)[4], float (&d_p)[3])
 {
-    const float qlen = sqrtf(q.x * q.x + q.y * q.y + q.z * q.z + q.w * q.w);
-    const float qn[4] = {q.x / qlen, q.y / qlen, q.z / qlen, q.w / qlen};
-    const float w = qn[0], x = qn[1], y = qn[2], z = qn[3];
-    const float nr[3] = {2.0f * (x * z + w * y), 2.0f * (y * z - w * x), 1.0f - 2.0f * (x * x + y * y)};
-    const float d[3] = {p[0] - campos[0], p[1] - campos[1], p[2] - campos[2]};
-    const float dlen = sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-    const float v[3] = {d[0] / dlen, d[1] / dlen, d[2] / dlen};
-    const float flip = -(nr[0] * v[0] + nr[1] * v[1] + nr[2] * v[2]) >= 0.0f ? 1.0f : -1.0f;
-    const float nf[3] = {nr[0] * flip, nr[1] * flip, nr[2] * flip};
-    const float nflen = fmaxf(sqrtf(nf[0] * nf[0] + nf[1] * nf[1] + nf[2] * nf[2]), 1e-20f);
-    const float nn[3] = {nf[0] / nflen, nf[1] / nflen, nf[2] / nflen};
-    float nc[3], cc[3];
-#pragma unroll
-    for (int j = 0; j < 3; j++) {
-        nc[j] = nn[0] * Wv[j] + nn[1] * Wv[4 + j] + nn[2] * Wv[8 + j];
-        cc[j] = p[0] * Wv[j] + p[1] * Wv[4 + j] + p[2] * Wv[8 + j] + Wv[12 + j];
-    }
-    const float sdist = nc[0] * cc[0] + nc[1] * cc[1] + nc[2] * cc[2];
-    const float sg = sdist > 0.0f ? gd : (sdist < 0.0f ? -gd : 0.0f);           // d|s| = sign(s) (torch: 0 at 0)
+    const Frame f = make_frame(p, q, campos);
+    const PlaneDist pd = plane_distance(Wv, f.nn, p);
+    const float sg = pd.s > 0.0f ? gd : (pd.s < 0.0f ? -gd : 0.0f);           // d|s| = sign(s) (torch: 0 at 0)
     float d_nn[3];
 #pragma unroll
     for (int i = 0; i < 3; i++) {
         const float* Wi = Wv + 4 * i;
-        d_nn[i] = sg * (Wi[0] * cc[0] + Wi[1] * cc[1] + Wi[2] * cc[2]);
-        d_p[i] = sg * (Wi[0] * nc[0] + Wi[1] * nc[1] + Wi[2] * nc[2]);
+        d_nn[i] = sg * (Wi[0] * pd.cc[0] + Wi[1] * pd.cc[1] + Wi[2] * pd.cc[2]);
+        d_p[i] = sg * (Wi[0] * pd.nc[0] + Wi[1] * pd.nc[1] + Wi[2] * pd.nc[2]);
     }
-    const float nn_dot = nn[0] * d_nn[0] + nn[1] * d_nn[1] + nn[2] * d_nn[2];
+    // n = nf / |nf|, nf = nr * flip
+    const float nn_dot = f.nn[0] * d_nn[0] + f.nn[1] * d_nn[1] + f.nn[2] * d_nn[2];
     float a[3];
 #pragma unroll
-    for (int i = 0; i < 3; i++) a[i] = (d_nn[i] - nn[i] * nn_dot) / nflen * flip;
+    for (int i = 0; i < 3; i++) a[i] = (d_nn[i] - f.nn[i] * nn_dot) / f.nflen * f.flip;
     float d_qn[4];
-    d_qn[0] = 2.0f * y * a[0] - 2.0f * x * a[1];
-    d_qn[1] = 2.0f * z * a[0] - 2.0f * w * a[1] - 4.0f * x * a[2];
-    d_qn[2] = 2.0f * w * a[0] + 2.0f * z * a[1] - 4.0f * y * a[2];
-    d_qn[3] = 2.0f * x * a[0] + 2.0f * y * a[1];
-    const float dot1 = ((qn[0] * d_qn[0] + qn[1] * d_qn[1]) + qn[2] * d_qn[2]) + qn[3] * d_qn[3];
+    frame_nr_bwd(f, a, d_qn);
+    // qn = q / |q|
+    const float dot1 = ((f.qn[0] * d_qn[0] + f.qn[1] * d_qn[1]) + f.qn[2] * d_qn[2]) + f.qn[3] * d_qn[3];
 #pragma unroll
-    for (int i = 0; i < 4; i++) d_q[i] += (d_qn[i] - qn[i] * dot1) / qlen;
+    for (int i = 0; i < 4; i++) d_q[i] += (d_qn[i] - f.qn[i] * dot1) / f.qlen;
 }
 
 template <bool GLUE>
@@ -970,7 +952,7 @@ __global__ void __launch_bounds__(64 * MRGS_PREB_WAVES) preprocess_bwd_kernel(
                 float d_ori[3];
 #pragma unroll
                 for (int c = 0; c < 3; c++) {
-                    const float so = glue_sigmoid(gl.ori_color_raw[3 * (size_t)idx + c]);
+                    const float so = sigmoidf(gl.ori_color_raw[3 * (size_t)idx + c]);
                     d_ori[c] = gfe[2 + c] * so * (1.0f - so);
                 }
                 wave_store_rows<3>(tile, d_ori, gl.d_ori_color + 3 * r0, nrows, lane);
@@ -988,7 +970,7 @@ __global__ void __launch_bounds__(64 * MRGS_PREB_WAVES) preprocess_bwd_kernel(
                     }
                 }
                 if (in_range) {
-                    const float s0 = glue_sigmoid(gl.refl_raw[idx]), s1 = glue_sigmoid(gl.rough_raw[idx]), so = glue_sigmoid(gl.opacity_raw[idx]);
+                    const float s0 = sigmoidf(gl.refl_raw[idx]), s1 = sigmoidf(gl.rough_raw[idx]), so = sigmoidf(gl.opacity_raw[idx]);
                     gl.d_refl[idx] = gfe[0] * s0 * (1.0f - s0);
                     gl.d_rough[idx] = gfe[1] * s1 * (1.0f - s1);
                     gl.d_opacity[idx] = dop * so * (1.0f - so);

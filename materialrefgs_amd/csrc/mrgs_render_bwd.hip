@@ -13,6 +13,7 @@
 // K independent wave reductions) -- and K/4 atomic instructions, each with four lanes writing four different
 // floats of the surfel's packed gradient row, replace K single-lane atomics.
 #include "mrgs_blend_math.h"
+#include "mrgs_wave.h"
 
 #ifndef MRGS_BWD_STAGES
 #define MRGS_BWD_STAGES 1   // see MRGS_FWD_STAGES in mrgs_render_fwd.hip
@@ -85,10 +86,10 @@ __device__ __forceinline__ float rows_reduce2(float a0, float a1)
 }
 __device__ __forceinline__ float rows_reduce1(float v)   // every lane of a 16-lane row gets the row total
 {
-    v = mrgs_dpp_add<0x128, 0xf>(v);   // row_ror:8
-    v = mrgs_dpp_add<0x124, 0xf>(v);   // row_ror:4
-    v = mrgs_dpp_add<0x122, 0xf>(v);   // row_ror:2
-    v = mrgs_dpp_add<0x121, 0xf>(v);   // row_ror:1
+    v = dpp_add<0x128, 0xf>(v);   // row_ror:8
+    v = dpp_add<0x124, 0xf>(v);   // row_ror:4
+    v = dpp_add<0x122, 0xf>(v);   // row_ror:2
+    v = dpp_add<0x121, 0xf>(v);   // row_ror:1
     return v;
 }
 

@@ -22,6 +22,7 @@
 #include <type_traits>
 
 #include "mrgs_blend_math.h"
+#include "mrgs_wave.h"
 
 // MRGS_FWD_REFINE_LIVE: the cull against the live pixels' bounding box runs for chunks that start with at most this many live pixels
 // (8 ... 40 measure the same, 64 = every chunk is 11 % slower than never).
@@ -58,12 +59,12 @@ extern "C" int mrgs_wave_stats_min_total(int n) { return (int)hipMemcpyToSymbol(
 // 0), then lane 15 / lane 31 of the rows before into the rows behind.  Every lane of the wave must be active.
 __device__ __forceinline__ float wave_inclusive_sum(float v)
 {
-    v = mrgs_dpp_add<0x111, 0xf>(v);   // row_shr:1
-    v = mrgs_dpp_add<0x112, 0xf>(v);   // row_shr:2
-    v = mrgs_dpp_add<0x114, 0xf>(v);   // row_shr:4
-    v = mrgs_dpp_add<0x118, 0xf>(v);   // row_shr:8
-    v = mrgs_dpp_add<0x142, 0xa>(v);   // row_bcast:15 into rows 1 and 3
-    v = mrgs_dpp_add<0x143, 0xc>(v);   // row_bcast:31 into rows 2 and 3
+    v = dpp_add<0x111, 0xf>(v);   // row_shr:1
+    v = dpp_add<0x112, 0xf>(v);   // row_shr:2
+    v = dpp_add<0x114, 0xf>(v);   // row_shr:4
+    v = dpp_add<0x118, 0xf>(v);   // row_shr:8
+    v = dpp_add<0x142, 0xa>(v);   // row_bcast:15 into rows 1 and 3
+    v = dpp_add<0x143, 0xc>(v);   // row_bcast:31 into rows 2 and 3
     return v;
 }
 

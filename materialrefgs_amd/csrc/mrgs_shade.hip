@@ -17,6 +17,8 @@
 // Memory-bound by design: one pixel per lane, ~100 B/pixel in, 36 B/pixel out; the 1.6 MB mip chain and the 512 KB LUT stay
 // in L2.  Texel gradients are accumulated with fp32 atomics (mirror directions of neighbouring pixels hit the same texels).
 #include "mrgs_internal.h"
+#include "mrgs_model_math.h"
+#include "mrgs_wave.h"
 
 struct EnvMips {   // by-value kernel argument
     int n;
@@ -214,16 +216,8 @@ __device__ __forceinline__ void env_fetch(const EnvMips& m, const FaceUV& fu, fl
     }
 }
 
-__device__ __forceinline__ float sigmoidf(float x) { return shade_rcp(1.0f + __expf(-x)); }
-
-// wave64 sum (DPP), result valid in every lane after the final readlane
-__device__ __forceinline__ float wave_sum_all(float v)
-{
-#define DPP_ADD(CTRL, RM) v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, RM, 0xf, false))
-    DPP_ADD(0xb1, 0xf); DPP_ADD(0x4e, 0xf); DPP_ADD(0x124, 0xf); DPP_ADD(0x128, 0xf); DPP_ADD(0x142, 0xa); DPP_ADD(0x143, 0xc);
-#undef DPP_ADD
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
-}
+// v_rcp / v_exp form, a few ulp from the IEEE sigmoidf of mrgs_model_math.h (which the per-gaussian kernels use)
+__device__ __forceinline__ float sigmoid_fast(float x) { return shade_rcp(1.0f + __expf(-x)); }
 
 // Add v[0..2] to the texel at `addr` (nullptr / all-zero v = nothing to add).  Neighbouring pixels mirror into the same few
 // texels (every lane of a wave into ONE texel of the coarse mip levels), and same-address atomics of one instruction
@@ -240,7 +234,7 @@ __device__ __forceinline__ void texel_scatter(float* addr, const float v[3])
         const int leader = __builtin_ctzll(pm);
         const unsigned klo = __builtin_amdgcn_readlane(lo, leader), khi = __builtin_amdgcn_readlane(hi, leader);
         const bool match = pending && lo == klo && hi == khi;
-        const float s0 = wave_sum_all(match ? v[0] : 0.f), s1 = wave_sum_all(match ? v[1] : 0.f), s2 = wave_sum_all(match ? v[2] : 0.f);
+        const float s0 = wave_dpp_sum(match ? v[0] : 0.f), s1 = wave_dpp_sum(match ? v[1] : 0.f), s2 = wave_dpp_sum(match ? v[2] : 0.f);
         if ((int)(threadIdx.x & 63) == leader) {
             atomicAdd(addr + 0, s0);
             atomicAdd(addr + 1, s1);
@@ -439,7 +433,7 @@ __global__ void __launch_bounds__(256) envmap_lookup_fwd_kernel(EnvMips m, long 
     Taps tp[2];
     env_fetch(m, fu, level, use_mips, s, tp);
 #pragma unroll
-    for (int c = 0; c < 3; c++) out[3 * i + c] = sigmoidf(s.L[c]);
+    for (int c = 0; c < 3; c++) out[3 * i + c] = sigmoid_fast(s.L[c]);
 }
 
 __global__ void __launch_bounds__(256) envmap_lookup_bwd_kernel(EnvMips m, long long N, const float* __restrict__ dirs,
@@ -460,7 +454,7 @@ __global__ void __launch_bounds__(256) envmap_lookup_bwd_kernel(EnvMips m, long 
     float gL[3];
 #pragma unroll
     for (int c = 0; c < 3; c++) {
-        const float y = sigmoidf(s.L[c]);
+        const float y = sigmoid_fast(s.L[c]);
         gL[c] = valid ? g_out[3 * i + c] * y * (1.f - y) : 0.f;
     }
     f3 gd;
@@ -576,19 +570,6 @@ __device__ __forceinline__ void shade_setup(const ShadeCamS& cam, int x, int y, 
     lut_fetch(lut, lres, p.u, p.v, p.fg, p.dfg_du, p.dfg_dv);
 }
 
-__device__ __forceinline__ float shade_lin2srgb(float x)        // linear_to_srgb (utils/general_utils / mrgs_maps.hip: the same expression)
-{
-    const float eps = 1.1920928955078125e-07f;
-    return x <= 0.0031308f ? (323.0f / 25.0f) * x : (211.0f * powf(fmaxf(x, eps), 5.0f / 12.0f) - 11.0f) / 200.0f;
-}
-
-__device__ __forceinline__ float shade_lin2srgb_grad(float x)   // d linear_to_srgb / dx (mrgs_maps.hip: lin2srgb_grad, the same expression)
-{
-    const float eps = 1.1920928955078125e-07f;
-    if (x <= 0.0031308f) return 323.0f / 25.0f;
-    return x >= eps ? (211.0f / 200.0f) * (5.0f / 12.0f) * powf(x, -7.0f / 12.0f) : 0.0f;
-}
-
 __global__ void __launch_bounds__(256) shade_specular_fwd_kernel(EnvMips m, ShadeCam cam, int H, int W, Map albedo, Map normal, Map alpha,
                                                                  Map refl, Map rough, const float* __restrict__ lut, int lres,
                                                                  float* __restrict__ specular /*[3,H,W]*/, float* __restrict__ direct /*[3,H,W]*/,
@@ -618,7 +599,7 @@ __global__ void __launch_bounds__(256) shade_specular_fwd_kernel(EnvMips m, Shad
     const size_t HW = (size_t)H * W, pix = (size_t)y * W + x;
 #pragma unroll
     for (int c = 0; c < 3; c++) {
-        const float light = sigmoidf(s.L[c]);
+        const float light = sigmoid_fast(s.L[c]);
         const float wgt = (0.04f * (1.f - p.refl) + p.albedo[c] * p.refl) * p.fg[0] + p.fg[1];
         direct[c * HW + pix] = light;
         weight[pix * 3 + c] = wgt;
@@ -627,7 +608,7 @@ __global__ void __launch_bounds__(256) shade_specular_fwd_kernel(EnvMips m, Shad
         if (render != nullptr) {     // diffuse = (1 - refl) base, render = [srgb](diffuse + specular) + bg (1 - alpha)  (gaussian_renderer/__init__.py:436-445)
             const float d = (1.0f - p.refl) * base[c * HW + pix];
             float v = d + spec;
-            if (srgb) v = shade_lin2srgb(v);
+            if (srgb) v = lin2srgb(v);
             render[c * HW + pix] = v + bg[c] * (1.0f - p.alpha);
             diffuse[c * HW + pix] = d;
         }
@@ -699,7 +680,7 @@ __global__ void __launch_bounds__(MRGS_SHADE_FUSED_THREADS) shade_fused_bwd_kern
                 const float gR = (valid && g_render != nullptr) ? g_render[c * HW + pix] : 0.0f;
                 g_alpha_c -= bg[c] * gR;
                 float gl = gR;
-                if (srgb) gl *= shade_lin2srgb_grad(k * b + spec_fwd[c * HW + pix]);
+                if (srgb) gl *= lin2srgb_grad(k * b + spec_fwd[c * HW + pix]);
                 const float gd = gl + ((valid && g_diffuse != nullptr) ? g_diffuse[c * HW + pix] : 0.0f);
                 if (valid) g_base[c * HW + pix] = k * gd;
                 g_refl_c -= b * gd;
@@ -720,7 +701,7 @@ __global__ void __launch_bounds__(MRGS_SHADE_FUSED_THREADS) shade_fused_bwd_kern
         float gL[3], ga = 0.f, gm = 0.f, gfg0 = 0.f, gfg1 = 0.f, galb[3];
 #pragma unroll
         for (int c = 0; c < 3; c++) {
-            const float light = sigmoidf(s.L[c]);
+            const float light = sigmoid_fast(s.L[c]);
             const float basec = 0.04f * (1.f - p.refl) + p.albedo[c] * p.refl;
             const float wgt = basec * p.fg[0] + p.fg[1];
             const float gs = gs_[c];

@@ -11,6 +11,7 @@
 // LSD radix passes are stable, so within a tile the pairs stay in (depth bits, gaussian index) order --
 // exactly the reference's order -- while moving ~3.4x fewer bytes than the 64-bit-key sort.
 #include "mrgs_blend_math.h"
+#include "mrgs_wave.h"
 
 #define SORT_THREADS 256
 #define SORT_WAVES (SORT_THREADS / 64)
@@ -44,9 +45,6 @@ __device__ __forceinline__ int64_t mrgs_count(int64_t n_host, const uint32_t* __
 
 __device__ __forceinline__ uint64_t lanemask_lt() { return (1ull << (threadIdx.x & 63)) - 1ull; }
 
-__device__ __forceinline__ uint32_t os_load(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void os_store(uint32_t* p, uint32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
 // sum of the published counts of tiles [0, blk) for the caller's column; false on spin overrun.  The status words of
 // OS_WINDOW predecessors are fetched together (independent loads in flight) and consumed nearest-first: a walk that had
 // to take one dependent memory round trip per predecessor made the passes latency-bound.
@@ -59,7 +57,7 @@ __device__ __forceinline__ bool os_look_back(const uint32_t* __restrict__ status
     while (p >= 0) {
         uint32_t s[OS_WINDOW];
 #pragma unroll
-        for (int k = 0; k < OS_WINDOW; k++) s[k] = os_load(status + (size_t)max(p - k, 0) * stride + column);
+        for (int k = 0; k < OS_WINDOW; k++) s[k] = ld_agent(status + (size_t)max(p - k, 0) * stride + column);
         bool stalled = false;
 #pragma unroll
         for (int k = 0; k < OS_WINDOW; k++) {
@@ -79,31 +77,6 @@ __device__ __forceinline__ bool os_look_back(const uint32_t* __restrict__ status
         }
     }
     return true;
-}
-
-// ---- block-wide exclusive scan helper (wave64 shuffles + one LDS hop) ----------------------------------
-template <int THREADS>
-__device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v, uint32_t* lds_wave_sums /*[THREADS/64]*/, uint32_t& total)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        uint32_t t = __shfl_up(inc, d, 64);
-        if (lane >= d) inc += t;
-    }
-    if (lane == 63) lds_wave_sums[wave] = inc;
-    __syncthreads();
-    uint32_t wave_off = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < THREADS / 64; w++) {
-        uint32_t s = lds_wave_sums[w];
-        if (w < wave) wave_off += s;
-        tot += s;
-    }
-    __syncthreads();
-    total = tot;
-    return wave_off + inc - v;
 }
 
 // ---- digit totals of every pass in one sweep over the keys ----------------------------------------------
@@ -213,11 +186,11 @@ __global__ void __launch_bounds__(SORT_THREADS) radix_onesweep_kernel(const uint
     uint32_t excl = 0;
     bool ok = true;
     if (blk == 0) {
-        os_store(mine, (OS_STATE_INC << 30) | cnt);
+        st_agent(mine, (OS_STATE_INC << 30) | cnt);
     } else {
-        os_store(mine, (OS_STATE_AGG << 30) | cnt);
+        st_agent(mine, (OS_STATE_AGG << 30) | cnt);
         ok = os_look_back(status, 256, tid, blk, excl);
-        if (ok) os_store(mine, (OS_STATE_INC << 30) | (excl + cnt));
+        if (ok) st_agent(mine, (OS_STATE_INC << 30) | (excl + cnt));
     }
     uint32_t all;
     const uint32_t digit_base = block_exclusive_scan<SORT_THREADS>(totals[tid], scan_tmp, all);

@@ -14,129 +14,12 @@
 // One gaussian per lane.  The 15x3 "rest" coefficients of a wave's 64 gaussians are one contiguous 11.5 KB run: it is
 // moved with 16-byte loads/stores through a per-wave LDS tile (odd row stride, conflict-free), in both directions.
 #include "mrgs_internal.h"
+#include "mrgs_model_math.h"
 
 namespace {
 
-__device__ __constant__ float cSH_C0 = 0.28209479177387814f;
-__device__ __constant__ float cSH_C1 = 0.4886025119029199f;
-__device__ __constant__ float cSH_C2[5] = {1.0925484305920792f, -1.0925484305920792f, 0.31539156525252005f, -1.0925484305920792f,
-                                           0.5462742152960396f};
-__device__ __constant__ float cSH_C3[7] = {-0.5900435899266435f, 2.890611442640554f, -0.4570457994644658f, 0.3731763325901154f,
-                                           -0.4570457994644658f, 1.445305721320277f, -0.5900435899266435f};
-
 #define REST_L 45            // 15 coefficients x 3 channels
 #define REST_STRIDE 45       // odd: lane-private rows are bank-conflict free
-
-// 64 consecutive rows of L floats <-> LDS tile, 16 bytes per lane and instruction (the run starts 16-byte aligned because
-// the first row index is a multiple of 64); partial waves take the scalar path
-template <int L, int STRIDE = REST_STRIDE>
-__device__ __forceinline__ void tile_load(float* __restrict__ tile, const float* __restrict__ src, int nrows, int lane)
-{
-    if (nrows == 64) {
-        constexpr int NF4 = 16 * L;
-        const float4* s4 = reinterpret_cast<const float4*>(src);
-#pragma unroll
-        for (int k = 0; k * 64 < NF4; k++) {
-            const int t = k * 64 + lane;
-            if (t < NF4) {
-                const float4 v = s4[t];
-                const float a[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-                for (int i = 0; i < 4; i++) {
-                    const int e = 4 * t + i;
-                    tile[(e / L) * STRIDE + (e % L)] = a[i];
-                }
-            }
-        }
-    } else {
-        for (int e = lane; e < nrows * L; e += 64) tile[(e / L) * STRIDE + (e % L)] = src[e];
-    }
-}
-template <int L, int STRIDE = REST_STRIDE>
-__device__ __forceinline__ void tile_store(const float* __restrict__ tile, float* __restrict__ dst, int nrows, int lane)
-{
-    if (nrows == 64) {
-        constexpr int NF4 = 16 * L;
-        float4* d4 = reinterpret_cast<float4*>(dst);
-#pragma unroll
-        for (int k = 0; k * 64 < NF4; k++) {
-            const int t = k * 64 + lane;
-            if (t < NF4) {
-                float a[4];
-#pragma unroll
-                for (int i = 0; i < 4; i++) {
-                    const int e = 4 * t + i;
-                    a[i] = tile[(e / L) * STRIDE + (e % L)];
-                }
-                d4[t] = make_float4(a[0], a[1], a[2], a[3]);
-            }
-        }
-    } else {
-        for (int e = lane; e < nrows * L; e += 64) dst[e] = tile[(e / L) * STRIDE + (e % L)];
-    }
-}
-
-__device__ __forceinline__ float sigmoidf(float x) { return 1.0f / (1.0f + expf(-x)); }
-
-// real SH basis, degree 3, the 3DGS sign convention (utils/sh_utils.py:57-112)
-__device__ __forceinline__ void sh_basis16(float x, float y, float z, float (&B)[16])
-{
-    const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
-    B[0] = cSH_C0;
-    B[1] = -cSH_C1 * y; B[2] = cSH_C1 * z; B[3] = -cSH_C1 * x;
-    B[4] = cSH_C2[0] * xy; B[5] = cSH_C2[1] * yz; B[6] = cSH_C2[2] * (2.0f * zz - xx - yy); B[7] = cSH_C2[3] * xz;
-    B[8] = cSH_C2[4] * (xx - yy);
-    B[9] = cSH_C3[0] * y * (3.0f * xx - yy); B[10] = cSH_C3[1] * xy * z; B[11] = cSH_C3[2] * y * (4.0f * zz - xx - yy);
-    B[12] = cSH_C3[3] * z * (2.0f * zz - 3.0f * xx - 3.0f * yy); B[13] = cSH_C3[4] * x * (4.0f * zz - xx - yy);
-    B[14] = cSH_C3[5] * z * (xx - yy); B[15] = cSH_C3[6] * x * (xx - 3.0f * yy);
-}
-
-struct Frame {               // everything the forward derives from (xyz, q, campos) and the backward needs again
-    float qlen, qn[4];       // |q|, q / |q| (w, x, y, z)
-    float nr[3];             // third column of R(q)
-    float flip, nflen, nn[3];// facing sign, |nf|, unit normal
-    float dlen, v[3];        // |xyz - campos|, unit view direction
-    float c, r[3];           // n . w_o, mirror direction
-};
-
-__device__ __forceinline__ Frame make_frame(const float p[3], const float4 q, const float* __restrict__ campos)
-{
-    Frame f;
-    f.qlen = sqrtf(q.x * q.x + q.y * q.y + q.z * q.z + q.w * q.w);
-    f.qn[0] = q.x / f.qlen; f.qn[1] = q.y / f.qlen; f.qn[2] = q.z / f.qlen; f.qn[3] = q.w / f.qlen;
-    const float w = f.qn[0], x = f.qn[1], y = f.qn[2], z = f.qn[3];
-    f.nr[0] = 2.0f * (x * z + w * y);
-    f.nr[1] = 2.0f * (y * z - w * x);
-    f.nr[2] = 1.0f - 2.0f * (x * x + y * y);
-    const float d[3] = {p[0] - campos[0], p[1] - campos[1], p[2] - campos[2]};
-    f.dlen = sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-    f.v[0] = d[0] / f.dlen; f.v[1] = d[1] / f.dlen; f.v[2] = d[2] / f.dlen;
-    const float dotp = -(f.nr[0] * f.v[0] + f.nr[1] * f.v[1] + f.nr[2] * f.v[2]);
-    f.flip = dotp >= 0.0f ? 1.0f : -1.0f;
-    const float nf[3] = {f.nr[0] * f.flip, f.nr[1] * f.flip, f.nr[2] * f.flip};
-    f.nflen = fmaxf(sqrtf(nf[0] * nf[0] + nf[1] * nf[1] + nf[2] * nf[2]), 1e-20f);
-    f.nn[0] = nf[0] / f.nflen; f.nn[1] = nf[1] / f.nflen; f.nn[2] = nf[2] / f.nflen;
-    f.c = -(f.nn[0] * f.v[0] + f.nn[1] * f.v[1] + f.nn[2] * f.v[2]);       // n . w_o, w_o = -v
-    f.r[0] = 2.0f * f.c * f.nn[0] + f.v[0];
-    f.r[1] = 2.0f * f.c * f.nn[1] + f.v[1];
-    f.r[2] = 2.0f * f.c * f.nn[2] + f.v[2];
-    return f;
-}
-
-// get_distance (gaussian_renderer/envgs_renderer.py:30-38): normal_cam = n @ Wv[:3,:3], centre_cam = p @ Wv[:3,:3] + Wv[3,:3] with the
-// world_view_transform as stored; the distance is |normal_cam . centre_cam|.
-struct PlaneDist { float nc[3], cc[3], s; };
-__device__ __forceinline__ PlaneDist plane_distance(const float* __restrict__ Wv, const float (&n)[3], const float (&p)[3])
-{
-    PlaneDist d;
-#pragma unroll
-    for (int j = 0; j < 3; j++) {
-        d.nc[j] = n[0] * Wv[j] + n[1] * Wv[4 + j] + n[2] * Wv[8 + j];
-        d.cc[j] = p[0] * Wv[j] + p[1] * Wv[4 + j] + p[2] * Wv[8 + j] + Wv[12 + j];
-    }
-    d.s = d.nc[0] * d.cc[0] + d.nc[1] * d.cc[1] + d.nc[2] * d.cc[2];
-    return d;
-}
 
 __global__ void __launch_bounds__(256) surfel_features_fwd_kernel(MrgsSurfelParams prm, float* __restrict__ opacity, float* __restrict__ scales,
                                                                   float* __restrict__ rotations, float* __restrict__ features)
@@ -258,19 +141,19 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MRGS_F
 #pragma unroll
             for (int k = 1; k < 16; k++) row[(k - 1) * 3 + ch] = g * B[k];   // in place: coefficients of this channel were read above
             // d(sum_k sh_k B_k)/d(x,y,z)
-            float dx = -cSH_C1 * sh[3] + cSH_C2[0] * y * sh[4] + cSH_C2[2] * -2.0f * x * sh[6] + cSH_C2[3] * z * sh[7] +
-                       cSH_C2[4] * 2.0f * x * sh[8];
-            float dy = -cSH_C1 * sh[1] + cSH_C2[0] * x * sh[4] + cSH_C2[1] * z * sh[5] + cSH_C2[2] * -2.0f * y * sh[6] +
-                       cSH_C2[4] * -2.0f * y * sh[8];
-            float dz = cSH_C1 * sh[2] + cSH_C2[1] * y * sh[5] + cSH_C2[2] * 4.0f * z * sh[6] + cSH_C2[3] * x * sh[7];
-            dx += cSH_C3[0] * sh[9] * 6.0f * xy + cSH_C3[1] * sh[10] * yz + cSH_C3[2] * sh[11] * -2.0f * xy +
-                  cSH_C3[3] * sh[12] * -6.0f * xz + cSH_C3[4] * sh[13] * (4.0f * zz - 3.0f * xx - yy) + cSH_C3[5] * sh[14] * 2.0f * xz +
-                  cSH_C3[6] * sh[15] * 3.0f * (xx - yy);
-            dy += cSH_C3[0] * sh[9] * 3.0f * (xx - yy) + cSH_C3[1] * sh[10] * xz + cSH_C3[2] * sh[11] * (4.0f * zz - xx - 3.0f * yy) +
-                  cSH_C3[3] * sh[12] * -6.0f * yz + cSH_C3[4] * sh[13] * -2.0f * xy + cSH_C3[5] * sh[14] * -2.0f * yz +
-                  cSH_C3[6] * sh[15] * -6.0f * xy;
-            dz += cSH_C3[1] * sh[10] * xy + cSH_C3[2] * sh[11] * 8.0f * yz + cSH_C3[3] * sh[12] * (6.0f * zz - 3.0f * xx - 3.0f * yy) +
-                  cSH_C3[4] * sh[13] * 8.0f * xz + cSH_C3[5] * sh[14] * (xx - yy);
+            float dx = -SH_C1 * sh[3] + SH_C2[0] * y * sh[4] + SH_C2[2] * -2.0f * x * sh[6] + SH_C2[3] * z * sh[7] +
+                       SH_C2[4] * 2.0f * x * sh[8];
+            float dy = -SH_C1 * sh[1] + SH_C2[0] * x * sh[4] + SH_C2[1] * z * sh[5] + SH_C2[2] * -2.0f * y * sh[6] +
+                       SH_C2[4] * -2.0f * y * sh[8];
+            float dz = SH_C1 * sh[2] + SH_C2[1] * y * sh[5] + SH_C2[2] * 4.0f * z * sh[6] + SH_C2[3] * x * sh[7];
+            dx += SH_C3[0] * sh[9] * 6.0f * xy + SH_C3[1] * sh[10] * yz + SH_C3[2] * sh[11] * -2.0f * xy +
+                  SH_C3[3] * sh[12] * -6.0f * xz + SH_C3[4] * sh[13] * (4.0f * zz - 3.0f * xx - yy) + SH_C3[5] * sh[14] * 2.0f * xz +
+                  SH_C3[6] * sh[15] * 3.0f * (xx - yy);
+            dy += SH_C3[0] * sh[9] * 3.0f * (xx - yy) + SH_C3[1] * sh[10] * xz + SH_C3[2] * sh[11] * (4.0f * zz - xx - 3.0f * yy) +
+                  SH_C3[3] * sh[12] * -6.0f * yz + SH_C3[4] * sh[13] * -2.0f * xy + SH_C3[5] * sh[14] * -2.0f * yz +
+                  SH_C3[6] * sh[15] * -6.0f * xy;
+            dz += SH_C3[1] * sh[10] * xy + SH_C3[2] * sh[11] * 8.0f * yz + SH_C3[3] * sh[12] * (6.0f * zz - 3.0f * xx - 3.0f * yy) +
+                  SH_C3[4] * sh[13] * 8.0f * xz + SH_C3[5] * sh[14] * (xx - yy);
             d_r[0] += g * dx; d_r[1] += g * dy; d_r[2] += g * dz;
         }
     }
@@ -306,13 +189,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MRGS_F
     float a[3];
 #pragma unroll
     for (int i = 0; i < 3; i++) a[i] = (d_nn[i] - f.nn[i] * nn_dot) / f.nflen * f.flip;
-    // nr(qn): nr0 = 2 (x z + w y), nr1 = 2 (y z - w x), nr2 = 1 - 2 (x^2 + y^2)
-    const float w = f.qn[0], qx = f.qn[1], qy = f.qn[2], qz = f.qn[3];
     float d_qn[4];
-    d_qn[0] = 2.0f * qy * a[0] - 2.0f * qx * a[1];
-    d_qn[1] = 2.0f * qz * a[0] - 2.0f * w * a[1] - 4.0f * qx * a[2];
-    d_qn[2] = 2.0f * w * a[0] + 2.0f * qz * a[1] - 4.0f * qy * a[2];
-    d_qn[3] = 2.0f * qx * a[0] + 2.0f * qy * a[1];
+    frame_nr_bwd(f, a, d_qn);
     // qn = q / |q| (build_rotation), plus the `rotations` output = normalize(q) with upstream g_rotations
     const float4 gr = g_rotations ? reinterpret_cast<const float4*>(g_rotations)[idx] : make_float4(0, 0, 0, 0);
     const float grv[4] = {gr.x, gr.y, gr.z, gr.w};

@@ -47,6 +47,7 @@
 #include <cstring>
 
 #include "mrgs_internal.h"
+#include "mrgs_wave.h"
 
 namespace {
 
@@ -121,33 +122,11 @@ BuildWs st_build_ws(int64_t P)
     return w;
 }
 
-__device__ __forceinline__ uint32_t ord_f(float f)          // order-preserving float -> uint
-{
-    const uint32_t u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float unord_f(uint32_t u)
-{
-    return __uint_as_float((u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u);
-}
-
-__device__ __forceinline__ uint32_t ld_agent_u(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void st_agent_u(uint32_t* p, uint32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-__device__ __forceinline__ uint32_t wave_max_u(uint32_t v)
-{
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, s));
-    return v;
-}
-
 // quad boxes + scene bounds.  bounds[k] = max ord(hi_k), bounds[3 + k] = max ~ord(lo_k).  Same-address atomics serialise at L2
 // (one per wave cost 0.32 ms at 300 k surfels): every block leaves one partial row instead and the last block to finish folds them.
 __global__ __launch_bounds__(256) void st_aabb_kernel(int P, const float* __restrict__ verts, float* __restrict__ aabb, uint32_t* __restrict__ partial,
                                                       uint32_t* __restrict__ ticket, uint32_t* __restrict__ bounds)
 {
-    __shared__ uint32_t red[4][6];
-    __shared__ bool last;
     uint32_t ext[6] = {0, 0, 0, 0, 0, 0};
     for (int p = blockIdx.x * 256 + threadIdx.x; p < P; p += gridDim.x * 256) {
         const float4* q = reinterpret_cast<const float4*>(verts + (size_t)p * 12);
@@ -170,34 +149,7 @@ __global__ __launch_bounds__(256) void st_aabb_kernel(int P, const float* __rest
             o[0] = NAN; o[1] = o[2] = o[3] = o[4] = o[5] = 0.f;          // never hit, sorted to key 0
         }
     }
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-        const uint32_t m = wave_max_u(ext[k]);
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][k] = m;
-    }
-    __syncthreads();
-    if (threadIdx.x < 6) {
-        const int k = threadIdx.x;
-        st_agent_u(partial + blockIdx.x * 6 + k, max(max(red[0][k], red[1][k]), max(red[2][k], red[3][k])));
-    }
-    __threadfence();
-    __syncthreads();
-    if (threadIdx.x == 0) last = atomicAdd(ticket, 1u) == gridDim.x - 1;
-    __syncthreads();
-    if (!last) return;
-    __threadfence();
-    // thread b folds block b's row (gridDim.x <= 256 = blockDim.x); six dependent loops over 256 agent-scope loads cost 50 us
-    uint32_t mine[6];
-#pragma unroll
-    for (int k = 0; k < 6; ++k) mine[k] = threadIdx.x < gridDim.x ? ld_agent_u(partial + threadIdx.x * 6 + k) : 0u;
-    __syncthreads();                       // `red` is reused
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-        const uint32_t m = wave_max_u(mine[k]);
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][k] = m;
-    }
-    __syncthreads();
-    if (threadIdx.x < 6) bounds[threadIdx.x] = max(max(red[0][threadIdx.x], red[1][threadIdx.x]), max(red[2][threadIdx.x], red[3][threadIdx.x]));
+    grid_max6_last_block_folds(ext, partial, ticket, bounds);
 }
 
 // Bits of the Morton key per axis.  8: a 24-bit key = THREE 8-bit radix passes instead of four (13 us per traced view); 16.7 M cells for
@@ -205,14 +157,6 @@ __global__ __launch_bounds__(256) void st_aabb_kernel(int P, const float* __rest
 #ifndef ST_MORTON_AXIS_BITS
 #define ST_MORTON_AXIS_BITS 8
 #endif
-__device__ __forceinline__ uint32_t spread10(uint32_t v)      // 10 bits -> every third bit
-{
-    v = (v | (v << 16)) & 0x030000FFu;
-    v = (v | (v << 8)) & 0x0300F00Fu;
-    v = (v | (v << 4)) & 0x030C30C3u;
-    v = (v | (v << 2)) & 0x09249249u;
-    return v;
-}
 
 __global__ __launch_bounds__(256) void st_morton_kernel(int P, const float* __restrict__ aabb, const uint32_t* __restrict__ bounds,
                                                         uint32_t* __restrict__ key, uint32_t* __restrict__ val)
@@ -299,30 +243,6 @@ struct StProf { int nodes, tests, lanes; unsigned t_fetch, t_cand; };     // dev
 // wave-wide reductions; the result is handed back through v_readfirstlane so that the compiler keeps it in a scalar register
 // (after the butterfly every lane holds the same value, which it cannot know: the beam's ~40 numbers would sit in vector registers)
 __device__ __forceinline__ float st_uniform(float v) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v))); }
-// DPP butterflies: xor 1, xor 2 inside the quads, rotations by 4 and 8 inside the 16-lane rows, then lane 15 / lane 31 of the rows before
-// into the rows behind (row_bcast) -- lane 63 ends up with the result of all 64.  Six dependent VALU instructions; the __shfl_xor
-// butterfly these replace goes through ds_bpermute, six dependent ~120-cycle LDS round trips (measured: a packet wave spends 500 of these
-// reductions a view -- nearest child, far bound, beams, packet tests -- i.e. ~40 % of its 470 us in them).  Masked-out rows take `old`.
-#define ST_DPP(OLD, V, CTRL, RM) __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(OLD), __float_as_int(V), CTRL, RM, 0xf, false))
-__device__ __forceinline__ float st_lane63(float v) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63)); }
-__device__ __forceinline__ float wave_sum_f(float v)
-{
-    v += ST_DPP(0.0f, v, 0xb1, 0xf); v += ST_DPP(0.0f, v, 0x4e, 0xf); v += ST_DPP(0.0f, v, 0x124, 0xf); v += ST_DPP(0.0f, v, 0x128, 0xf);
-    v += ST_DPP(0.0f, v, 0x142, 0xa); v += ST_DPP(0.0f, v, 0x143, 0xc);
-    return st_lane63(v);
-}
-__device__ __forceinline__ float wave_max_f(float v)
-{
-    v = fmaxf(v, ST_DPP(v, v, 0xb1, 0xf)); v = fmaxf(v, ST_DPP(v, v, 0x4e, 0xf)); v = fmaxf(v, ST_DPP(v, v, 0x124, 0xf)); v = fmaxf(v, ST_DPP(v, v, 0x128, 0xf));
-    v = fmaxf(v, ST_DPP(v, v, 0x142, 0xa)); v = fmaxf(v, ST_DPP(v, v, 0x143, 0xc));
-    return st_lane63(v);
-}
-__device__ __forceinline__ float wave_min_f(float v)
-{
-    v = fminf(v, ST_DPP(v, v, 0xb1, 0xf)); v = fminf(v, ST_DPP(v, v, 0x4e, 0xf)); v = fminf(v, ST_DPP(v, v, 0x124, 0xf)); v = fminf(v, ST_DPP(v, v, 0x128, 0xf));
-    v = fminf(v, ST_DPP(v, v, 0x142, 0xa)); v = fminf(v, ST_DPP(v, v, 0x143, 0xc));
-    return st_lane63(v);
-}
 
 // ---- the wave-wide hierarchy -------------------------------------------------------------------------------------------------
 // A second tree over the same Morton order for waves whose 64 rays run close together (an 8x8 block of mirror rays off a smooth
@@ -371,7 +291,7 @@ __global__ __launch_bounds__(64) void st_wide_level_kernel(int level, int n_chil
         float* up = boxes + (size_t)(w.off[level + 1] + (node >> 6)) * 384;
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
-            const float lo = wave_min_f(ok ? b[k] : INFINITY), hi = wave_max_f(ok ? b[3 + k] : -INFINITY);
+            const float lo = wave_dpp_min(ok ? b[k] : INFINITY), hi = wave_dpp_max(ok ? b[3 + k] : -INFINITY);
             if (c == 0) { up[k * 64 + (node & 63)] = lo; up[(3 + k) * 64 + (node & 63)] = hi; }
         }
     }
@@ -390,12 +310,12 @@ struct StBeam {
 __device__ __forceinline__ StBeam st_make_beam(bool on, float ox, float oy, float oz, float dx, float dy, float dz, float& s0, float& dm)
 {
     StBeam B;
-    const float cnt = wave_sum_f(on ? 1.0f : 0.0f);
+    const float cnt = wave_dpp_sum(on ? 1.0f : 0.0f);
     const float il = on ? 1.0f / sqrtf(dx * dx + dy * dy + dz * dz) : 0.0f;
-    float mx = wave_sum_f(dx * il), my = wave_sum_f(dy * il), mz = wave_sum_f(dz * il);
+    float mx = wave_dpp_sum(dx * il), my = wave_dpp_sum(dy * il), mz = wave_dpp_sum(dz * il);
     const float ml = 1.0f / sqrtf(mx * mx + my * my + mz * mz);
     mx *= ml; my *= ml; mz *= ml;
-    B.oc[0] = wave_sum_f(on ? ox : 0.0f) / cnt; B.oc[1] = wave_sum_f(on ? oy : 0.0f) / cnt; B.oc[2] = wave_sum_f(on ? oz : 0.0f) / cnt;
+    B.oc[0] = wave_dpp_sum(on ? ox : 0.0f) / cnt; B.oc[1] = wave_dpp_sum(on ? oy : 0.0f) / cnt; B.oc[2] = wave_dpp_sum(on ? oz : 0.0f) / cnt;
     // e1 = m x (the axis m is least aligned with), e2 = m x e1
     const float ax = fabsf(mx), ay = fabsf(my), az = fabsf(mz);
     float qx = 0.f, qy = 0.f, qz = 0.f;
@@ -414,10 +334,10 @@ __device__ __forceinline__ StBeam st_make_beam(bool on, float ox, float oy, floa
     const float px = rx + tau * dx, py = ry + tau * dy, pz = rz + tau * dz;
     const float u0 = px * e1x + py * e1y + pz * e1z, v0 = px * e2x + py * e2y + pz * e2z;
     const float k1 = (dx * e1x + dy * e1y + dz * e1z) / dm, k2 = (dx * e2x + dy * e2y + dz * e2z) / dm;
-    B.u0min = wave_min_f(on ? u0 : INFINITY); B.u0max = wave_max_f(on ? u0 : -INFINITY);
-    B.v0min = wave_min_f(on ? v0 : INFINITY); B.v0max = wave_max_f(on ? v0 : -INFINITY);
-    B.k1min = wave_min_f(on ? k1 : INFINITY); B.k1max = wave_max_f(on ? k1 : -INFINITY);
-    B.k2min = wave_min_f(on ? k2 : INFINITY); B.k2max = wave_max_f(on ? k2 : -INFINITY);
+    B.u0min = wave_dpp_min(on ? u0 : INFINITY); B.u0max = wave_dpp_max(on ? u0 : -INFINITY);
+    B.v0min = wave_dpp_min(on ? v0 : INFINITY); B.v0max = wave_dpp_max(on ? v0 : -INFINITY);
+    B.k1min = wave_dpp_min(on ? k1 : INFINITY); B.k1max = wave_dpp_max(on ? k1 : -INFINITY);
+    B.k2min = wave_dpp_min(on ? k2 : INFINITY); B.k2max = wave_dpp_max(on ? k2 : -INFINITY);
     return B;
 }
 
@@ -479,7 +399,7 @@ __device__ __forceinline__ int st_gather_wide(const StWide& W, const float* __re
     const int lane = tid & 63;
     float s0, dm;
     const StBeam B = st_make_beam(on, ox, oy, oz, dx, dy, dz, s0, dm);
-    const float s_prev = wave_min_f(on ? s0 + prev_t * dm : INFINITY);      // nothing in front of every lane's last blended hit is needed
+    const float s_prev = wave_dpp_min(on ? s0 + prev_t * dm : INFINITY);      // nothing in front of every lane's last blended hit is needed
     // behind s_far no lane needs anything: every active lane's buffer is full and its last entry lies in front (depth = s0 + t dm)
     float s_far = INFINITY;
     unsigned long long mask[SW_MAX_LEVELS] = {0, 0, 0, 0};
@@ -515,7 +435,7 @@ __device__ __forceinline__ int st_gather_wide(const StWide& W, const float* __re
         if (l > 0) {                                                          // nearest remaining child first
             const float mine = l == 1 ? near1 : l == 2 ? near2 : near3;
             const float key = ((mask[l] >> lane) & 1ull) ? mine : INFINITY;
-            const float nearest = wave_min_f(key);
+            const float nearest = wave_dpp_min(key);
             if (nearest > s_far) { mask[l] = 0; continue; }                   // and everything else at this node lies behind it
             const int c = __builtin_ctzll(__ballot(key == nearest));
             mask[l] &= ~(1ull << c);
@@ -564,7 +484,7 @@ __device__ __forceinline__ int st_gather_wide(const StWide& W, const float* __re
                 }
             }
         }
-        s_far = wave_max_f(on ? (n == ST_K ? s0 + kb_t[ST_K - 1][tid] * dm : INFINITY) : -INFINITY) * (1.0f + 1e-5f) + 1e-30f;
+        s_far = wave_dpp_max(on ? (n == ST_K ? s0 + kb_t[ST_K - 1][tid] * dm : INFINITY) : -INFINITY) * (1.0f + 1e-5f) + 1e-30f;
     }
     return n;
 }
@@ -587,7 +507,7 @@ __device__ __forceinline__ int st_gather_group(const StWide& W, const float* __r
     const int lane = tid & 63, wbase = tid & ~63;
     float s0, dm;
     const StBeam B = st_make_beam(on, ox, oy, oz, dx, dy, dz, s0, dm);
-    const float s_prev = wave_min_f(on ? s0 + prev_t * dm : INFINITY);
+    const float s_prev = wave_dpp_min(on ? s0 + prev_t * dm : INFINITY);
     float s_far = INFINITY;
     // the gather layout: lane = grp * R + i; `own` = the lane that owns ray i of packet pk (st_assign_packets' numbering)
     const bool quad_pk = pk <= 4;
@@ -652,7 +572,7 @@ __device__ __forceinline__ int st_gather_group(const StWide& W, const float* __r
         if (l > 0) {                                                          // nearest remaining child first
             const float mine = l == 1 ? near1 : l == 2 ? near2 : near3;
             const float key = ((mask[l] >> lane) & 1ull) ? mine : INFINITY;
-            const float nearest = wave_min_f(key);
+            const float nearest = wave_dpp_min(key);
             if (nearest > s_far) { mask[l] = 0; continue; }
             const int c = __builtin_ctzll(__ballot(key == nearest));
             mask[l] &= ~(1ull << c);
@@ -722,7 +642,7 @@ __device__ __forceinline__ int st_gather_group(const StWide& W, const float* __r
 #ifdef ST_PROFILE
         prof.t_cand += (unsigned)(wall_clock64() - tc0);
 #endif
-        s_far = wave_max_f(on ? (kb_n[tid] == ST_K ? s0 + kb_t[ST_K - 1][tid] * dm : INFINITY) : -INFINITY) * (1.0f + 1e-5f) + 1e-30f;
+        s_far = wave_dpp_max(on ? (kb_n[tid] == ST_K ? s0 + kb_t[ST_K - 1][tid] * dm : INFINITY) : -INFINITY) * (1.0f + 1e-5f) + 1e-30f;
     }
     return on ? (int)kb_n[tid] : 0;
 }
@@ -731,17 +651,17 @@ __device__ __forceinline__ int st_gather_group(const StWide& W, const float* __r
 // scene's extent of their centre.  `on` selects the rays asked about; the answer is wave-uniform.
 __device__ __forceinline__ bool st_run_together(float extent, float cone, bool on, float ox, float oy, float oz, float dx, float dy, float dz)
 {
-    const float cnt = wave_sum_f(on ? 1.0f : 0.0f);
+    const float cnt = wave_dpp_sum(on ? 1.0f : 0.0f);
     if (cnt < 1.0f) return false;
     const float il = on ? 1.0f / sqrtf(dx * dx + dy * dy + dz * dz) : 0.0f;
     const float ux = dx * il, uy = dy * il, uz = dz * il;
-    float mx = wave_sum_f(ux), my = wave_sum_f(uy), mz = wave_sum_f(uz);
+    float mx = wave_dpp_sum(ux), my = wave_dpp_sum(uy), mz = wave_dpp_sum(uz);
     const float ml = sqrtf(mx * mx + my * my + mz * mz);
     if (!(ml > 0.5f * cnt)) return false;
     mx /= ml; my /= ml; mz /= ml;
-    const float worst = wave_max_f(on ? 1.0f - (ux * mx + uy * my + uz * mz) : 0.0f);
-    const float cx = wave_sum_f(on ? ox : 0.0f) / cnt, cy = wave_sum_f(on ? oy : 0.0f) / cnt, cz = wave_sum_f(on ? oz : 0.0f) / cnt;
-    const float spread = wave_max_f(on ? fmaxf(fabsf(ox - cx), fmaxf(fabsf(oy - cy), fabsf(oz - cz))) : 0.0f);
+    const float worst = wave_dpp_max(on ? 1.0f - (ux * mx + uy * my + uz * mz) : 0.0f);
+    const float cx = wave_dpp_sum(on ? ox : 0.0f) / cnt, cy = wave_dpp_sum(on ? oy : 0.0f) / cnt, cz = wave_dpp_sum(on ? oz : 0.0f) / cnt;
+    const float spread = wave_dpp_max(on ? fmaxf(fabsf(ox - cx), fmaxf(fabsf(oy - cy), fabsf(oz - cz))) : 0.0f);
     return worst <= cone && spread <= 0.02f * extent;
 }
 
@@ -759,7 +679,7 @@ __device__ __forceinline__ int st_assign_packets(const StArgs& A, const float* _
         const bool there = (vmask[root] >> lane) & 1ull;
         const float* bx = boxes + (size_t)root * 384 + lane;
         for (int k = 0; k < 3; ++k)
-            extent = fmaxf(extent, wave_max_f(there ? bx[(3 + k) * 64] : -INFINITY) - wave_min_f(there ? bx[k * 64] : INFINITY));
+            extent = fmaxf(extent, wave_dpp_max(there ? bx[(3 + k) * 64] : -INFINITY) - wave_dpp_min(there ? bx[k * 64] : INFINITY));
     } else {
         extent = INFINITY;                                                    // <= 64 surfels: no scale to compare origins with
     }
@@ -1244,14 +1164,14 @@ __global__ __launch_bounds__(ST_THREADS) __attribute__((amdgpu_waves_per_eu(MODE
 __device__ __forceinline__ float scan16_mul_excl(float v, int lane)          // exclusive prefix product over lanes 0..15 (others: don't care)
 {
     float inc = v;
-    inc *= ST_DPP(1.0f, inc, 0x111, 0xf); inc *= ST_DPP(1.0f, inc, 0x112, 0xf); inc *= ST_DPP(1.0f, inc, 0x114, 0xf); inc *= ST_DPP(1.0f, inc, 0x118, 0xf);
-    return ST_DPP(1.0f, inc, 0x111, 0xf);
+    inc *= MRGS_DPP(1.0f, inc, 0x111, 0xf); inc *= MRGS_DPP(1.0f, inc, 0x112, 0xf); inc *= MRGS_DPP(1.0f, inc, 0x114, 0xf); inc *= MRGS_DPP(1.0f, inc, 0x118, 0xf);
+    return MRGS_DPP(1.0f, inc, 0x111, 0xf);
 }
 __device__ __forceinline__ float scan16_add_excl(float v, int lane)
 {
     float inc = v;
-    inc += ST_DPP(0.0f, inc, 0x111, 0xf); inc += ST_DPP(0.0f, inc, 0x112, 0xf); inc += ST_DPP(0.0f, inc, 0x114, 0xf); inc += ST_DPP(0.0f, inc, 0x118, 0xf);
-    return ST_DPP(0.0f, inc, 0x111, 0xf);
+    inc += MRGS_DPP(0.0f, inc, 0x111, 0xf); inc += MRGS_DPP(0.0f, inc, 0x112, 0xf); inc += MRGS_DPP(0.0f, inc, 0x114, 0xf); inc += MRGS_DPP(0.0f, inc, 0x118, 0xf);
+    return MRGS_DPP(0.0f, inc, 0x111, 0xf);
 }
 __device__ __forceinline__ unsigned long long readlane_u64(unsigned long long v, int l)
 {
@@ -1371,7 +1291,7 @@ __device__ __forceinline__ void st_trace_lone_rays(const StArgs& A, const float4
                 }
                 const float my_near = l == 1 ? near1 : l == 2 ? near2 : near3;
                 const float key = ((mask[l] >> lane) & 1ull) ? my_near : INFINITY;
-                const float nearest = wave_min_f(key);
+                const float nearest = wave_dpp_min(key);
                 if (nearest * 0.99999f > t_far) { mask[l] = 0; continue; }
                 const int c = __builtin_ctzll(__ballot(key == nearest));
                 mask[l] &= ~(1ull << c);
@@ -1406,10 +1326,10 @@ __device__ __forceinline__ void st_trace_lone_rays(const StArgs& A, const float4
             const float nfx = sgn * g2.y, nfy = sgn * g2.z, nfz = sgn * g2.w;
             const float Ab = Aw + scan16_add_excl(w, lane), M1b = M1 + scan16_add_excl(w * t, lane), M2b = M2 + scan16_add_excl(w * t * t, lane);
             if (!BWD) {
-                C0 += wave_sum_f(w * a0.x); C1 += wave_sum_f(w * a0.y); C2 += wave_sum_f(w * a0.z);
-                N0 += wave_sum_f(w * nfx); N1 += wave_sum_f(w * nfy); N2 += wave_sum_f(w * nfz);
-                X0 += wave_sum_f(w * a0.w); X1 += wave_sum_f(w * a1.x);
-                dist += wave_sum_f(w * (t * t * Ab + M2b - 2.0f * t * M1b));
+                C0 += wave_dpp_sum(w * a0.x); C1 += wave_dpp_sum(w * a0.y); C2 += wave_dpp_sum(w * a0.z);
+                N0 += wave_dpp_sum(w * nfx); N1 += wave_dpp_sum(w * nfy); N2 += wave_dpp_sum(w * nfz);
+                X0 += wave_dpp_sum(w * a0.w); X1 += wave_dpp_sum(w * a1.x);
+                dist += wave_dpp_sum(w * (t * t * Ab + M2b - 2.0f * t * M1b));
                 if (bl) atomicAdd(A.wet + id, w);
             } else {
                 const float q = gc0 * a0.x + gc1 * a0.y + gc2 * a0.z + gd * t + ga + gn0 * nfx + gn1 * nfy + gn2 * nfz + gx0 * a0.w + gx1 * a1.x
@@ -1440,15 +1360,15 @@ __device__ __forceinline__ void st_trace_lone_rays(const StArgs& A, const float4
                     go0 += dpx - dnum * nx; go1 += dpy - dnum * ny; go2 += dpz - dnum * nz;
                     gv0 += t * dpx + dden * nx; gv1 += t * dpy + dden * ny; gv2 += t * dpz + dden * nz;
                 }
-                Qpre += wave_sum_f(wq);
+                Qpre += wave_dpp_sum(wq);
             }
-            D += wave_sum_f(w * t);
-            const float sw = wave_sum_f(w);
-            Aw += sw; M1 += wave_sum_f(w * t); M2 += wave_sum_f(w * t * t);
+            D += wave_dpp_sum(w * t);
+            const float sw = wave_dpp_sum(w);
+            Aw += sw; M1 += wave_dpp_sum(w * t); M2 += wave_dpp_sum(w * t * t);
             // transmittance behind the blended hits
             const float keep = bl ? 1.0f - alpha : 1.0f;
             float prod = keep;          // product over the row's 16 lanes: inside the quads, then the neighbouring quads by rotation
-            prod *= ST_DPP(1.0f, prod, 0xb1, 0xf); prod *= ST_DPP(1.0f, prod, 0x4e, 0xf); prod *= ST_DPP(1.0f, prod, 0x124, 0xf); prod *= ST_DPP(1.0f, prod, 0x128, 0xf);
+            prod *= MRGS_DPP(1.0f, prod, 0xb1, 0xf); prod *= MRGS_DPP(1.0f, prod, 0x4e, 0xf); prod *= MRGS_DPP(1.0f, prod, 0x124, 0xf); prod *= MRGS_DPP(1.0f, prod, 0x128, 0xf);
             T *= st_uniform(prod);
             blended += n_bl;
             if (stop || nb < ST_K) done = true;
@@ -1463,7 +1383,7 @@ __device__ __forceinline__ void st_trace_lone_rays(const StArgs& A, const float4
                 reinterpret_cast<float4*>(A.state)[r] = make_float4(M2, T, (float)blended, (float)passes);
             }
         } else {
-            const float s0 = wave_sum_f(go0), s1 = wave_sum_f(go1), s2 = wave_sum_f(go2), v0 = wave_sum_f(gv0), v1 = wave_sum_f(gv1), v2 = wave_sum_f(gv2);
+            const float s0 = wave_dpp_sum(go0), s1 = wave_dpp_sum(go1), s2 = wave_dpp_sum(go2), v0 = wave_dpp_sum(gv0), v1 = wave_dpp_sum(gv1), v2 = wave_dpp_sum(gv2);
             if (lane == 0) {
                 A.g_ray_o[3 * r] = s0; A.g_ray_o[3 * r + 1] = s1; A.g_ray_o[3 * r + 2] = s2;
                 A.g_ray_d[3 * r] = v0; A.g_ray_d[3 * r + 1] = v1; A.g_ray_d[3 * r + 2] = v2;

@@ -12,15 +12,9 @@
 // Backward: g_geom / g_attr (the tracer's outputs) -> gradients of means, scales, rotations (through the normalisation), opacities,
 // SH coefficients or colours, others.  The quads carry no gradient (the reference detaches them, optix_utils.py:76).
 #include "mrgs_internal.h"
+#include "mrgs_model_math.h"
 
 namespace {
-
-__device__ __constant__ float pSH_C0 = 0.28209479177387814f;
-__device__ __constant__ float pSH_C1 = 0.4886025119029199f;
-__device__ __constant__ float pSH_C2[5] = {1.0925484305920792f, -1.0925484305920792f, 0.31539156525252005f, -1.0925484305920792f,
-                                           0.5462742152960396f};
-__device__ __constant__ float pSH_C3[7] = {-0.5900435899266435f, 2.890611442640554f, -0.4570457994644658f, 0.3731763325901154f,
-                                           -0.4570457994644658f, 1.445305721320277f, -0.5900435899266435f};
 
 struct PrepArgs {
     int P, M, degree;                     // M coefficients per channel in `shs` (layout [P,M,3]), active degree
@@ -38,71 +32,10 @@ struct PrepArgs {
 };
 
 #define PREST_L 45           // 15 coefficients x 3 channels of _features_rest
-// 64 consecutive rows of 45 floats <-> a per-wave LDS tile with 16-byte global accesses (the run starts 16-byte aligned: the first row
-// index is a multiple of 64; row stride 45 floats is odd, so lane-private rows are bank-conflict free); partial waves go scalar
-__device__ __forceinline__ void prest_load(float* __restrict__ tile, const float* __restrict__ src, int nrows, int lane)
-{
-    if (nrows == 64) {
-        constexpr int NF4 = 16 * PREST_L;
-        const float4* s4 = reinterpret_cast<const float4*>(src);
-#pragma unroll
-        for (int k = 0; k * 64 < NF4; k++) {
-            const int t = k * 64 + lane;
-            if (t < NF4) {
-                const float4 v = s4[t];
-                tile[4 * t] = v.x; tile[4 * t + 1] = v.y; tile[4 * t + 2] = v.z; tile[4 * t + 3] = v.w;
-            }
-        }
-    } else {
-        for (int e = lane; e < nrows * PREST_L; e += 64) tile[e] = src[e];
-    }
-}
-__device__ __forceinline__ void prest_store(const float* __restrict__ tile, float* __restrict__ dst, int nrows, int lane)
-{
-    if (nrows == 64) {
-        constexpr int NF4 = 16 * PREST_L;
-        float4* d4 = reinterpret_cast<float4*>(dst);
-#pragma unroll
-        for (int k = 0; k * 64 < NF4; k++) {
-            const int t = k * 64 + lane;
-            if (t < NF4) d4[t] = make_float4(tile[4 * t], tile[4 * t + 1], tile[4 * t + 2], tile[4 * t + 3]);
-        }
-    } else {
-        for (int e = lane; e < nrows * PREST_L; e += 64) dst[e] = tile[e];
-    }
-}
-__device__ __forceinline__ float psigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
-
-// basis values B[0..n) and their derivatives with respect to the unit direction (x, y, z)
-__device__ __forceinline__ void sh_basis_and_grad(int degree, float x, float y, float z, float (&B)[16], float (&Bx)[16], float (&By)[16], float (&Bz)[16])
-{
-#pragma unroll
-    for (int i = 0; i < 16; ++i) { B[i] = 0.f; Bx[i] = 0.f; By[i] = 0.f; Bz[i] = 0.f; }
-    B[0] = pSH_C0;
-    if (degree < 1) return;
-    B[1] = -pSH_C1 * y; By[1] = -pSH_C1;
-    B[2] = pSH_C1 * z; Bz[2] = pSH_C1;
-    B[3] = -pSH_C1 * x; Bx[3] = -pSH_C1;
-    if (degree < 2) return;
-    const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
-    B[4] = pSH_C2[0] * xy; Bx[4] = pSH_C2[0] * y; By[4] = pSH_C2[0] * x;
-    B[5] = pSH_C2[1] * yz; By[5] = pSH_C2[1] * z; Bz[5] = pSH_C2[1] * y;
-    B[6] = pSH_C2[2] * (2.0f * zz - xx - yy); Bx[6] = -2.0f * pSH_C2[2] * x; By[6] = -2.0f * pSH_C2[2] * y; Bz[6] = 4.0f * pSH_C2[2] * z;
-    B[7] = pSH_C2[3] * xz; Bx[7] = pSH_C2[3] * z; Bz[7] = pSH_C2[3] * x;
-    B[8] = pSH_C2[4] * (xx - yy); Bx[8] = 2.0f * pSH_C2[4] * x; By[8] = -2.0f * pSH_C2[4] * y;
-    if (degree < 3) return;
-    B[9] = pSH_C3[0] * y * (3.0f * xx - yy); Bx[9] = pSH_C3[0] * 6.0f * xy; By[9] = pSH_C3[0] * 3.0f * (xx - yy);
-    B[10] = pSH_C3[1] * xy * z; Bx[10] = pSH_C3[1] * yz; By[10] = pSH_C3[1] * xz; Bz[10] = pSH_C3[1] * xy;
-    B[11] = pSH_C3[2] * y * (4.0f * zz - xx - yy); Bx[11] = -2.0f * pSH_C3[2] * xy; By[11] = pSH_C3[2] * (4.0f * zz - xx - 3.0f * yy); Bz[11] = 8.0f * pSH_C3[2] * yz;
-    B[12] = pSH_C3[3] * z * (2.0f * zz - 3.0f * xx - 3.0f * yy); Bx[12] = -6.0f * pSH_C3[3] * xz; By[12] = -6.0f * pSH_C3[3] * yz;
-    Bz[12] = pSH_C3[3] * (6.0f * zz - 3.0f * xx - 3.0f * yy);
-    B[13] = pSH_C3[4] * x * (4.0f * zz - xx - yy); Bx[13] = pSH_C3[4] * (4.0f * zz - 3.0f * xx - yy); By[13] = -2.0f * pSH_C3[4] * xy; Bz[13] = 8.0f * pSH_C3[4] * xz;
-    B[14] = pSH_C3[5] * z * (xx - yy); Bx[14] = 2.0f * pSH_C3[5] * xz; By[14] = -2.0f * pSH_C3[5] * yz; Bz[14] = pSH_C3[5] * (xx - yy);
-    B[15] = pSH_C3[6] * x * (xx - 3.0f * yy); Bx[15] = pSH_C3[6] * 3.0f * (xx - yy); By[15] = -6.0f * pSH_C3[6] * xy;
-}
 
 struct Rot { float qn[4], len, R[3][3]; };
 
+// build_rotation (utils/general_utils.py:80-99): divides by |q|, row-major R[r][c]; not mrgs_preprocess.hip's quat_to_rotmat (1 / sqrt, then products)
 __device__ __forceinline__ Rot make_rot(const float4 q)
 {
     Rot r;
@@ -127,7 +60,7 @@ __global__ __launch_bounds__(256) void trace_prep_kernel(PrepArgs A)
     const int p = valid ? wave_base + lane : A.P - 1;
     float* rest = s_rest[SPLIT ? wave : 0];
     if (SPLIT) {
-        prest_load(rest, A.shs_rest + (size_t)wave_base * PREST_L, nrows, lane);
+        tile_load<PREST_L>(rest, A.shs_rest + (size_t)wave_base * PREST_L, nrows, lane);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");      // lanes read rows other lanes wrote
         __builtin_amdgcn_wave_barrier();
     }
@@ -177,7 +110,7 @@ __global__ __launch_bounds__(256) void trace_prep_kernel(PrepArgs A)
         g[0] = make_float4(mx, my, mz, ru[0] / su);
         g[1] = make_float4(ru[1] / su, ru[2] / su, rv[0] / sv, rv[1] / sv);
         g[2] = make_float4(rv[2] / sv, rw[0], rw[1], rw[2]);
-        g[3] = make_float4(A.raw ? psigmoid(A.opacities[p]) : A.opacities[p], 0.f, 0.f, 0.f);
+        g[3] = make_float4(A.raw ? sigmoidf(A.opacities[p]) : A.opacities[p], 0.f, 0.f, 0.f);
         float4* a = reinterpret_cast<float4*>(A.attr) + (size_t)p * 2;
         a[0] = make_float4(rgb[0], rgb[1], rgb[2], A.others ? A.others[2 * p] : 0.f);
         a[1] = make_float4(A.others ? A.others[2 * p + 1] : 0.f, 0.f, 0.f, 0.f);
@@ -219,7 +152,7 @@ __global__ __launch_bounds__(256) void trace_prep_kernel(PrepArgs A)
     const float dot = w * dw + x * dx + y * dy + z * dz;
     if (valid) {
         reinterpret_cast<float4*>(A.g_rotations)[p] = make_float4((dw - w * dot) / r.len, (dx - x * dot) / r.len, (dy - y * dot) / r.len, (dz - z * dot) / r.len);
-        if (A.raw) { const float o = psigmoid(A.opacities[p]); A.g_opacities[p] = g3.x * o * (1.0f - o); }
+        if (A.raw) { const float o = sigmoidf(A.opacities[p]); A.g_opacities[p] = g3.x * o * (1.0f - o); }
         else A.g_opacities[p] = g3.x;
         if (A.g_others) { A.g_others[2 * p] = a0.w; A.g_others[2 * p + 1] = a1.x; }
     }
@@ -256,7 +189,7 @@ __global__ __launch_bounds__(256) void trace_prep_kernel(PrepArgs A)
                 for (int i = 0; i < PREST_L; ++i) rest[lane * PREST_L + i] = out[3 + i];
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                 __builtin_amdgcn_wave_barrier();
-                prest_store(rest, A.g_shs_rest + (size_t)wave_base * PREST_L, nrows, lane);
+                tile_store<PREST_L>(rest, A.g_shs_rest + (size_t)wave_base * PREST_L, nrows, lane);
             } else if (valid) {
                 float4* g4 = reinterpret_cast<float4*>(gsh);
 #pragma unroll

@@ -1,0 +1,176 @@
+// mrgs_wave.h -- wave64 and workgroup primitives shared by the kernel files: each exists here once.
+//
+// Two families of wave-wide reductions, told apart by name:
+//   wave_shfl_*   __shfl_xor butterfly: six ds_bpermute round trips through the LDS crossbar, the result in EVERY lane (a vector register)
+//   wave_dpp_*    six DPP steps on the VALU, the result read from lane 63 and therefore wave-uniform (a scalar register)
+// The values are the same up to the order of a float sum; the cost and the register class of the result are not.
+#pragma once
+#include "mrgs_internal.h"
+
+// ---- relaxed agent-scope word access (tickets, look-back status words, partial rows another workgroup reads) ----------------------
+__device__ __forceinline__ uint32_t ld_agent(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ void st_agent(uint32_t* p, uint32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// ---- ordered float keys, Morton codes --------------------------------------------------------------------------------------------
+__device__ __forceinline__ uint32_t ord_f(float f)          // order-preserving float -> uint
+{
+    const uint32_t u = __float_as_uint(f);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float unord_f(uint32_t u)
+{
+    return __uint_as_float((u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u);
+}
+__device__ __forceinline__ uint32_t spread10(uint32_t v)      // 10 bits -> every third bit
+{
+    v = (v | (v << 16)) & 0x030000FFu;
+    v = (v | (v << 8)) & 0x0300F00Fu;
+    v = (v | (v << 4)) & 0x030C30C3u;
+    v = (v | (v << 2)) & 0x09249249u;
+    return v;
+}
+
+// ---- shuffle butterflies: result in every lane, via LDS permute --------------------------------------------------------------------
+template <typename T>
+__device__ __forceinline__ T wave_shfl_sum(T v)               // float or double
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+__device__ __forceinline__ float wave_shfl_min(float v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o, 64));
+    return v;
+}
+__device__ __forceinline__ float wave_shfl_max(float v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+    return v;
+}
+__device__ __forceinline__ uint32_t wave_shfl_max(uint32_t v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, o, 64));
+    return v;
+}
+
+// ---- DPP reductions: result uniform, six DPP steps -----------------------------------------------------------------------------------
+// xor 1, xor 2 inside the quads, rotations by 4 and 8 inside the 16-lane rows, then lane 15 / lane 31 of the rows before into the rows
+// behind (row_bcast) -- lane 63 ends up with the result of all 64.  Six dependent VALU instructions; a __shfl_xor butterfly goes through
+// ds_bpermute, six dependent ~120-cycle LDS round trips (measured in the tracer: a packet wave spends 500 of these reductions a view --
+// nearest child, far bound, beams, packet tests -- i.e. ~40 % of its 470 us in them).  Masked-out rows take `old`.  Every lane of the
+// wave must be active.
+#define MRGS_DPP(OLD, V, CTRL, RM) __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(OLD), __float_as_int(V), CTRL, RM, 0xf, false))
+__device__ __forceinline__ float wave_lane63(float v) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63)); }
+// one step of a DPP sum: v + (v moved by CTRL, 0 where no lane is the source or the row is masked out)
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ float dpp_add(float v)
+{
+    return v + MRGS_DPP(0.0f, v, CTRL, ROW_MASK);
+}
+__device__ __forceinline__ float wave_dpp_sum(float v)
+{
+    v = dpp_add<0xb1, 0xf>(v); v = dpp_add<0x4e, 0xf>(v); v = dpp_add<0x124, 0xf>(v); v = dpp_add<0x128, 0xf>(v);
+    v = dpp_add<0x142, 0xa>(v); v = dpp_add<0x143, 0xc>(v);
+    return wave_lane63(v);
+}
+__device__ __forceinline__ float wave_dpp_max(float v)
+{
+    v = fmaxf(v, MRGS_DPP(v, v, 0xb1, 0xf)); v = fmaxf(v, MRGS_DPP(v, v, 0x4e, 0xf)); v = fmaxf(v, MRGS_DPP(v, v, 0x124, 0xf)); v = fmaxf(v, MRGS_DPP(v, v, 0x128, 0xf));
+    v = fmaxf(v, MRGS_DPP(v, v, 0x142, 0xa)); v = fmaxf(v, MRGS_DPP(v, v, 0x143, 0xc));
+    return wave_lane63(v);
+}
+__device__ __forceinline__ float wave_dpp_min(float v)
+{
+    v = fminf(v, MRGS_DPP(v, v, 0xb1, 0xf)); v = fminf(v, MRGS_DPP(v, v, 0x4e, 0xf)); v = fminf(v, MRGS_DPP(v, v, 0x124, 0xf)); v = fminf(v, MRGS_DPP(v, v, 0x128, 0xf));
+    v = fminf(v, MRGS_DPP(v, v, 0x142, 0xa)); v = fminf(v, MRGS_DPP(v, v, 0x143, 0xc));
+    return wave_lane63(v);
+}
+
+// ---- workgroup scans ---------------------------------------------------------------------------------------------------------------
+// v = this thread's count; returns the exclusive prefix over the 256 threads of the workgroup.  One barrier: s_wave must not be written
+// again before every wave has read it (the callers scan once per launch).
+template <typename T>
+__device__ __forceinline__ T block_exclusive_scan_256(T v, T* s_wave /*[4]*/, T& total)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    T inc = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const T n = __shfl_up(inc, o, 64);
+        if (lane >= o) inc += n;
+    }
+    if (lane == 63) s_wave[wave] = inc;
+    __syncthreads();
+    T base = 0;
+    for (int w = 0; w < wave; ++w) base += s_wave[w];
+    total = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+    return base + inc - v;
+}
+// The same for THREADS threads, with a second barrier behind the reads so that the caller may scan again through the same lds_wave_sums
+// (the radix passes do), and every wave sums all THREADS / 64 entries instead of its own predecessors.
+template <int THREADS>
+__device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v, uint32_t* lds_wave_sums /*[THREADS/64]*/, uint32_t& total)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t inc = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        uint32_t t = __shfl_up(inc, d, 64);
+        if (lane >= d) inc += t;
+    }
+    if (lane == 63) lds_wave_sums[wave] = inc;
+    __syncthreads();
+    uint32_t wave_off = 0, tot = 0;
+#pragma unroll
+    for (int w = 0; w < THREADS / 64; w++) {
+        uint32_t s = lds_wave_sums[w];
+        if (w < wave) wave_off += s;
+        tot += s;
+    }
+    __syncthreads();
+    total = tot;
+    return wave_off + inc - v;
+}
+
+// ---- six maxima over a whole grid without same-address atomics -----------------------------------------------------------------------
+// Tail of a 256-thread kernel whose threads each hold six ordered-uint maxima (ext): every block leaves one partial row, takes a ticket,
+// and the last block to finish folds the rows into bounds[0..6).  Same-address atomics serialise at L2 (one per wave cost 0.32 ms at
+// 300 k surfels).  gridDim.x <= 256; *ticket starts at 0; partial holds gridDim.x * 6 words.
+__device__ __forceinline__ void grid_max6_last_block_folds(const uint32_t (&ext)[6], uint32_t* __restrict__ partial, uint32_t* __restrict__ ticket,
+                                                           uint32_t* __restrict__ bounds)
+{
+    __shared__ uint32_t red[4][6];
+    __shared__ bool last;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        const uint32_t m = wave_shfl_max(ext[k]);
+        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][k] = m;
+    }
+    __syncthreads();
+    if (threadIdx.x < 6) {
+        const int k = threadIdx.x;
+        st_agent(partial + blockIdx.x * 6 + k, max(max(red[0][k], red[1][k]), max(red[2][k], red[3][k])));
+    }
+    __threadfence();
+    __syncthreads();
+    if (threadIdx.x == 0) last = atomicAdd(ticket, 1u) == gridDim.x - 1;
+    __syncthreads();
+    if (!last) return;
+    __threadfence();
+    // thread b folds block b's row (gridDim.x <= 256 = blockDim.x); six dependent loops over 256 agent-scope loads cost 50 us
+    uint32_t mine[6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) mine[k] = threadIdx.x < gridDim.x ? ld_agent(partial + threadIdx.x * 6 + k) : 0u;
+    __syncthreads();                       // `red` is reused
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        const uint32_t m = wave_shfl_max(mine[k]);
+        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][k] = m;
+    }
+    __syncthreads();
+    if (threadIdx.x < 6) bounds[threadIdx.x] = max(max(red[0][threadIdx.x], red[1][threadIdx.x]), max(red[2][threadIdx.x], red[3][threadIdx.x]));
+}
