@@ -848,6 +848,9 @@ int mrgs_set_profiling(int32_t level);   /* 0 off, 1 every stage, 2 only the two
 int mrgs_get_kernel_times(MrgsKernelTimes* out);
 
 const char* mrgs_strerror(int code);
+/* "<hipGetErrorString> at <file>:<line>" of the most recent MRGS_E_HIP returned to the CALLING thread, by whichever entry point: every
+ * such return records its reason first.  Valid until that thread's next failing call (a success does not clear it); "" if the thread
+ * has had none. */
 const char* mrgs_last_hip_error(void);
 const char* mrgs_version(void);
 

@@ -301,7 +301,9 @@ def lib():
     return _lib
 
 
-MRGS_E_WORKSPACE = 5
+# the status codes of include/mrgs.h
+(MRGS_OK, MRGS_E_BAD_ARG, MRGS_E_TOO_MANY_FEATURES, MRGS_E_NEED_COLORS, MRGS_E_HIP, MRGS_E_WORKSPACE, MRGS_E_UNSUPPORTED,
+ MRGS_E_INTERNAL) = range(8)
 
 
 # ---- launch plumbing (host time per call matters: a full render is ~30 native calls a view) -----------------------------------------
@@ -348,6 +350,6 @@ def check(rc):
     if rc != 0:
         L = lib()
         msg = L.mrgs_strerror(rc).decode()
-        if rc == 4:
+        if rc == MRGS_E_HIP:
             msg += ": " + L.mrgs_last_hip_error().decode()
         raise RuntimeError(f"libmrgs: {msg}")

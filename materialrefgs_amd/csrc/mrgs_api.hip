@@ -10,20 +10,18 @@
 static thread_local char g_hip_err[256] = "";
 static int g_profiling = 0;
 
-#define HIP_TRY(expr)                                                                                       \
-    do {                                                                                                    \
-        hipError_t e_ = (expr);                                                                             \
-        if (e_ != hipSuccess) {                                                                             \
-            snprintf(g_hip_err, sizeof(g_hip_err), "%s at %s:%d", hipGetErrorString(e_), __FILE__, __LINE__); \
-            return MRGS_E_HIP;                                                                              \
-        }                                                                                                   \
-    } while (0)
+int mrgs_hip_status(hipError_t e, const char* file, int line)
+{
+    if (e == hipSuccess) return MRGS_OK;
+    snprintf(g_hip_err, sizeof(g_hip_err), "%s at %s:%d", hipGetErrorString(e), file, line);
+    return MRGS_E_HIP;
+}
 
 // CHECK_CUDA(A, debug) of the reference (auxiliary.h:303-310): with cfg.debug every stage is synchronised.
-#define STAGE_CHECK(cfg, stream)                                 \
-    do {                                                         \
-        HIP_TRY(hipGetLastError());                              \
-        if ((cfg)->debug) HIP_TRY(hipStreamSynchronize(stream)); \
+#define STAGE_CHECK(cfg, stream)                                      \
+    do {                                                              \
+        if (int rc_ = MRGS_LAUNCH_STATUS()) return rc_;               \
+        if ((cfg)->debug) MRGS_HIP_TRY(hipStreamSynchronize(stream)); \
     } while (0)
 
 namespace {
@@ -248,7 +246,7 @@ static int enqueue_geom(const MrgsRasterConfig* cfg, const MrgsRasterInputs* in,
     if (g.tile_mat != nullptr) {
         // per-tile pair counts of fixed surfel slices, column prefixes, tile offsets, num_rendered (mrgs_binning.hip)
         mrgs_launch_tile_count_scan(*cfg, g, host_slot, stream);
-        if (slot_event != nullptr) HIP_TRY(hipEventRecord(slot_event, stream));   // the host slot is written when this completes
+        if (slot_event != nullptr) MRGS_HIP_TRY(hipEventRecord(slot_event, stream));   // the host slot is written when this completes
     } else {
         // images with more tiles than the slice histograms hold: global radix path of round 1 (mrgs_sort.hip).
         // depth sort of the gaussians (32 key bits, 4 passes -> result back in buffer 0)
@@ -280,14 +278,14 @@ static int enqueue_render(const MrgsRasterConfig* cfg, const MrgsRasterInputs* i
         // ordering launch did besides ordering moves into the tile sort
         reuse_order = R > 0 && in->work_hint != nullptr && (in->hint_flags & MRGS_HINT_REUSE_ORDER) != 0u;
         if (R > 0) mrgs_launch_tile_emit_sort(*cfg, g, b, img, R, reuse_order, in->bwd_grad_ws, in->bwd_grad_ws ? mrgs_grad_bytes(cfg->P, cfg->S) : 0, stream);
-        else HIP_TRY(hipMemsetAsync(img.ranges, 0, img.ranges_est_bytes, stream));   // nothing visible: the ranges read as empty
+        else MRGS_HIP_TRY(hipMemsetAsync(img.ranges, 0, img.ranges_est_bytes, stream));   // nothing visible: the ranges read as empty
         STAGE_CHECK(cfg, stream);
     } else {
         if (R > 0) {
             mrgs_launch_duplicate(*cfg, g, g.order[dcur], b.tile_key[0], b.plist[0], R, R_dev, b, img, host_slot, stream);
-            if (slot_event != nullptr) HIP_TRY(hipEventRecord(slot_event, stream));   // the host slot is written when this completes
+            if (slot_event != nullptr) MRGS_HIP_TRY(hipEventRecord(slot_event, stream));   // the host slot is written when this completes
         } else {   // nothing visible: no kernel touches the pair buffers, only the ranges have to read as empty
-            HIP_TRY(hipMemsetAsync(img.ranges, 0, img.ranges_est_bytes, stream));
+            MRGS_HIP_TRY(hipMemsetAsync(img.ranges, 0, img.ranges_est_bytes, stream));
         }
         STAGE_CHECK(cfg, stream);
         const int bits = tile_bits(ntiles);
@@ -313,9 +311,9 @@ static int zero_outputs(const MrgsRasterConfig* cfg, float* out_color, float* ou
 {
     // the reference returns zero-filled outputs without touching the kernels (rasterize_points.cu:89-93,106)
     const size_t hw = (size_t)cfg->H * cfg->W;
-    HIP_TRY(hipMemsetAsync(out_color, 0, sizeof(float) * 3 * hw, stream));
-    if (cfg->S > 0) HIP_TRY(hipMemsetAsync(out_feature, 0, sizeof(float) * cfg->S * hw, stream));
-    HIP_TRY(hipMemsetAsync(out_others, 0, sizeof(float) * MRGS_NUM_OTHERS * hw, stream));
+    MRGS_HIP_TRY(hipMemsetAsync(out_color, 0, sizeof(float) * 3 * hw, stream));
+    if (cfg->S > 0) MRGS_HIP_TRY(hipMemsetAsync(out_feature, 0, sizeof(float) * cfg->S * hw, stream));
+    MRGS_HIP_TRY(hipMemsetAsync(out_others, 0, sizeof(float) * MRGS_NUM_OTHERS * hw, stream));
     return MRGS_OK;
 }
 
@@ -343,8 +341,8 @@ int mrgs_rasterize_forward_geom(const MrgsRasterConfig* cfg, const MrgsRasterInp
     if (rc) return rc;
     // blocking read-back of num_rendered, as rasterizer_impl.cu:287 (plus the error flag of the look-back kernels)
     uint32_t host[2] = {0, 0};
-    HIP_TRY(hipMemcpyAsync(host, g.counters, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
+    MRGS_HIP_TRY(hipMemcpyAsync(host, g.counters, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    MRGS_HIP_TRY(hipStreamSynchronize(stream));
     return check_counters(host, num_rendered_host);
 }
 
@@ -400,13 +398,13 @@ int mrgs_rasterize_forward_begin(const MrgsRasterConfig* cfg, const MrgsRasterIn
     MrgsBinWs b = mrgs_carve_bin(binning_ws, capacity_pairs);
     if (binning_bytes < b.total) return MRGS_E_WORKSPACE;
     int device = 0;
-    HIP_TRY(hipGetDevice(&device));
+    MRGS_HIP_TRY(hipGetDevice(&device));
     if (device < 0 || device >= MRGS_MAX_DEVICES) return MRGS_E_UNSUPPORTED;
     ReadbackRing& ring = g_rings[device];
     if (!ring.host) {
-        HIP_TRY(hipHostMalloc((void**)&ring.host, MRGS_TICKET_RING * 64, hipHostMallocMapped | hipHostMallocPortable));
-        HIP_TRY(hipHostGetDevicePointer((void**)&ring.dev, ring.host, 0));
-        for (int i = 0; i < MRGS_TICKET_RING; ++i) HIP_TRY(hipEventCreateWithFlags(&ring.ev[i], hipEventDisableTiming));
+        MRGS_HIP_TRY(hipHostMalloc((void**)&ring.host, MRGS_TICKET_RING * 64, hipHostMallocMapped | hipHostMallocPortable));
+        MRGS_HIP_TRY(hipHostGetDevicePointer((void**)&ring.dev, ring.host, 0));
+        for (int i = 0; i < MRGS_TICKET_RING; ++i) MRGS_HIP_TRY(hipEventCreateWithFlags(&ring.ev[i], hipEventDisableTiming));
     }
     const int slot = (int)(ring.next % MRGS_TICKET_RING);
     ring.seq[slot] = ring.next;
@@ -428,7 +426,7 @@ int mrgs_rasterize_forward_finish(const MrgsRasterTicket* ticket, int64_t* num_r
     if (ticket->device >= MRGS_MAX_DEVICES || ticket->slot < 0 || ticket->slot >= MRGS_TICKET_RING) return MRGS_E_BAD_ARG;
     ReadbackRing& ring = g_rings[ticket->device];
     if (!ring.host || ring.seq[ticket->slot] != ticket->seq) return MRGS_E_BAD_ARG;      // another thread's ticket, or the slot was reused
-    HIP_TRY(hipEventSynchronize(ring.ev[ticket->slot]));
+    MRGS_HIP_TRY(hipEventSynchronize(ring.ev[ticket->slot]));
     int rc = check_counters(ring.host + 16 * ticket->slot, num_rendered_host);
     if (rc) return rc;
     return *num_rendered_host > ticket->capacity_pairs ? MRGS_E_WORKSPACE : MRGS_OK;
@@ -495,7 +493,7 @@ int mrgs_rasterize_backward_blend(const MrgsRasterConfig* cfg, const MrgsRasterI
         if (!prepared) mrgs_launch_blend_order(img, g.counters + 16, tiles_x * tiles_y, 1, grad_rec, mrgs_grad_bytes(cfg->P, cfg->S), nullptr, stream);
         mrgs_launch_render_bwd(*cfg, *in, g, b.plist[cur], b.cflag, img, dL_dout_color, dL_dout_feature, dL_dout_others, grad_rec, prepared, stream);
     } else if (!prepared) {
-        HIP_TRY(hipMemsetAsync(grad_rec, 0, mrgs_grad_bytes(cfg->P, cfg->S), stream));
+        MRGS_HIP_TRY(hipMemsetAsync(grad_rec, 0, mrgs_grad_bytes(cfg->P, cfg->S), stream));
     }
     t0.stop();
     if (dL_dRGB_masked) mrgs_launch_color_grad_extract(*cfg, g, radii, grad_rec, in->shs != nullptr, dL_dRGB_masked, stream);
@@ -550,8 +548,7 @@ int mrgs_mark_visible(int32_t P, const float* means3D, const float* viewmatrix, 
     if (P == 0) return MRGS_OK;
     if (!means3D || !viewmatrix || !present) return MRGS_E_BAD_ARG;
     mrgs_launch_mark_visible(P, means3D, viewmatrix, present, (hipStream_t)stream_);
-    HIP_TRY(hipGetLastError());
-    return MRGS_OK;
+    return MRGS_LAUNCH_STATUS();
 }
 
 // ---- introspection for the parity tests --------------------------------------------------------------
@@ -594,26 +591,25 @@ int mrgs_debug_export(const MrgsRasterConfig* cfg, const void* geom_ws, const vo
     case 0: case 1: case 2: case 3: case 4: case 6:
         if (P > 0) hipLaunchKernelGGL(export_rec_kernel, dim3((P + 255) / 256), dim3(256), 0, stream, P, which, g.rec, g.clamped, dst);
         break;
-    case 5: HIP_TRY(hipMemcpyAsync(dst, g.tiles_touched, sizeof(uint32_t) * P, hipMemcpyDeviceToDevice, stream)); break;
+    case 5: MRGS_HIP_TRY(hipMemcpyAsync(dst, g.tiles_touched, sizeof(uint32_t) * P, hipMemcpyDeviceToDevice, stream)); break;
     case 7: {
         MrgsBinWs b = mrgs_carve_bin(const_cast<void*>(binning_ws), R);
         const int cur = plist_buf(g, tiles_x * tiles_y);
-        if (R > 0) HIP_TRY(hipMemcpyAsync(dst, b.plist[cur], sizeof(uint32_t) * R, hipMemcpyDeviceToDevice, stream));
+        if (R > 0) MRGS_HIP_TRY(hipMemcpyAsync(dst, b.plist[cur], sizeof(uint32_t) * R, hipMemcpyDeviceToDevice, stream));
     } break;
-    case 8: HIP_TRY(hipMemcpyAsync(dst, img.ranges, sizeof(uint2) * tiles_x * tiles_y, hipMemcpyDeviceToDevice, stream)); break;
-    case 9: HIP_TRY(hipMemcpyAsync(dst, img.final_T, sizeof(float) * 3 * hw, hipMemcpyDeviceToDevice, stream)); break;
-    case 10: HIP_TRY(hipMemcpyAsync(dst, img.n_contrib, sizeof(uint32_t) * 2 * hw, hipMemcpyDeviceToDevice, stream)); break;
-    case 11: HIP_TRY(hipMemcpyAsync(dst, g.order[sorted_buf(32)], sizeof(uint32_t) * P, hipMemcpyDeviceToDevice, stream)); break;
-    case 12: HIP_TRY(hipMemcpyAsync(dst, img.redo_list, sizeof(uint32_t) * (2 + hw), hipMemcpyDeviceToDevice, stream)); break;   // [0] count, [2..] marked pixels
+    case 8: MRGS_HIP_TRY(hipMemcpyAsync(dst, img.ranges, sizeof(uint2) * tiles_x * tiles_y, hipMemcpyDeviceToDevice, stream)); break;
+    case 9: MRGS_HIP_TRY(hipMemcpyAsync(dst, img.final_T, sizeof(float) * 3 * hw, hipMemcpyDeviceToDevice, stream)); break;
+    case 10: MRGS_HIP_TRY(hipMemcpyAsync(dst, img.n_contrib, sizeof(uint32_t) * 2 * hw, hipMemcpyDeviceToDevice, stream)); break;
+    case 11: MRGS_HIP_TRY(hipMemcpyAsync(dst, g.order[sorted_buf(32)], sizeof(uint32_t) * P, hipMemcpyDeviceToDevice, stream)); break;
+    case 12: MRGS_HIP_TRY(hipMemcpyAsync(dst, img.redo_list, sizeof(uint32_t) * (2 + hw), hipMemcpyDeviceToDevice, stream)); break;   // [0] count, [2..] marked pixels
     case 13: {      // the quadrant masks of the tile lists (one byte per list entry: which 8x8 blocks of its tile the surfel's box touches)
         MrgsBinWs b = mrgs_carve_bin(const_cast<void*>(binning_ws), R);
-        if (R > 0) HIP_TRY(hipMemcpyAsync(dst, b.qmask, sizeof(uint8_t) * R, hipMemcpyDeviceToDevice, stream));
+        if (R > 0) MRGS_HIP_TRY(hipMemcpyAsync(dst, b.qmask, sizeof(uint8_t) * R, hipMemcpyDeviceToDevice, stream));
     } break;
-    case 14: if (P > 0) HIP_TRY(hipMemcpyAsync(dst, g.cull, sizeof(float4) * MRGS_CULL_F4 * (size_t)P, hipMemcpyDeviceToDevice, stream)); break;
+    case 14: if (P > 0) MRGS_HIP_TRY(hipMemcpyAsync(dst, g.cull, sizeof(float4) * MRGS_CULL_F4 * (size_t)P, hipMemcpyDeviceToDevice, stream)); break;
     default: return MRGS_E_BAD_ARG;
     }
-    HIP_TRY(hipGetLastError());
-    return MRGS_OK;
+    return MRGS_LAUNCH_STATUS();
 }
 
 int mrgs_set_profiling(int32_t enabled)

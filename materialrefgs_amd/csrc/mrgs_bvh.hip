@@ -340,7 +340,7 @@ extern "C" int mrgs_bvh_trace(const void* blob_dev, int64_t n_triangles, int64_t
     bvh_trace_kernel<<<dim3((unsigned)nblk), 256, 0, (hipStream_t)stream>>>(
         reinterpret_cast<const BvhNode*>(base + l.nodes_off), reinterpret_cast<const float4*>(base + l.tris_off),
         reinterpret_cast<const int32_t*>(base + l.perm_off), n_rays, rays_o, rays_d, positions, normals, depth, face_ids);
-    return hipGetLastError() == hipSuccess ? MRGS_OK : MRGS_E_HIP;
+    return MRGS_LAUNCH_STATUS();
 }
 
 extern "C" int mrgs_bvh_visibility(const void* blob_dev, int64_t n_triangles, int32_t H, int32_t W, const float* Kinv, const float* R,
@@ -360,5 +360,5 @@ extern "C" int mrgs_bvh_visibility(const void* blob_dev, int64_t n_triangles, in
     bvh_visibility_kernel<<<dim3((W + 31) / 32, (H + 7) / 8), 256, 0, (hipStream_t)stream>>>(
         reinterpret_cast<const BvhNode*>(base + l.nodes_off), reinterpret_cast<const float4*>(base + l.tris_off), cam, H, W, nm, am, surf_depth,
         visibility);
-    return hipGetLastError() == hipSuccess ? MRGS_OK : MRGS_E_HIP;
+    return MRGS_LAUNCH_STATUS();
 }

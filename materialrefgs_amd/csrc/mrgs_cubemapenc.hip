@@ -214,7 +214,7 @@ int mrgs_cubemap_encode_forward(const float* inputs, const float* cubemap, const
     if (!inputs || !cubemap || !fail_value || !outputs) return MRGS_E_BAD_ARG;
     hipLaunchKernelGGL(cubemap_encode_fwd_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, (hipStream_t)stream, inputs, cubemap, fail_value,
                        outputs, interp, seamless, (long long)B, C, L);
-    return hipGetLastError() == hipSuccess ? MRGS_OK : MRGS_E_HIP;
+    return MRGS_LAUNCH_STATUS();
 }
 
 int mrgs_cubemap_encode_backward(const float* grad_outputs, const float* inputs, const float* cubemap, float* grad_cubemap, float* grad_inputs,
@@ -225,7 +225,7 @@ int mrgs_cubemap_encode_backward(const float* grad_outputs, const float* inputs,
     if (!grad_outputs || !inputs || !cubemap || !grad_cubemap || !grad_inputs || !grad_fail) return MRGS_E_BAD_ARG;
     hipLaunchKernelGGL(cubemap_encode_bwd_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, (hipStream_t)stream, grad_outputs, inputs, cubemap,
                        grad_cubemap, grad_inputs, grad_fail, interp, seamless, (long long)B, C, L);
-    return hipGetLastError() == hipSuccess ? MRGS_OK : MRGS_E_HIP;
+    return MRGS_LAUNCH_STATUS();
 }
 
 }   // extern "C"

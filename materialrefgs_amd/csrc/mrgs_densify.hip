@@ -254,8 +254,7 @@ extern "C" size_t mrgs_densify_ws_bytes(int64_t P)
 extern "C" int mrgs_densify_classify(const MrgsDensifyConfig* cfg, const float* accum, const float* denom, const float* scaling_raw,
                                      const float* opacity_raw, void* ws, size_t ws_bytes, int64_t* counts_dev, void* stream)
 {
-    const int rc = densify_check_cfg(cfg);
-    if (rc != MRGS_OK) return rc;
+    if (int rc = densify_check_cfg(cfg)) return rc;
     if (cfg->P == 0) return MRGS_OK;
     if (!ws || ((uintptr_t)ws & 3) || !counts_dev || ws_bytes < mrgs_densify_ws_bytes(cfg->P)) return MRGS_E_BAD_ARG;
     hipStream_t st = (hipStream_t)stream;
@@ -269,14 +268,13 @@ extern "C" int mrgs_densify_classify(const MrgsDensifyConfig* cfg, const float* 
     a.world_limit = cfg->world_size_limit; a.child_div = (float)(0.8 * (double)cfg->N);
     densify_classify_kernel<<<dim3((unsigned)nb), 256, 0, st>>>(a, accum, denom, scaling_raw, opacity_raw, cls, counts, (int)nb);
     densify_scan_kernel<<<1, 1024, 0, st>>>((int)nb, counts, offs, (long long*)counts_dev);
-    return hipGetLastError() == hipSuccess ? MRGS_OK : MRGS_E_HIP;
+    return MRGS_LAUNCH_STATUS();
 }
 
 extern "C" int mrgs_densify_emit(const MrgsDensifyConfig* cfg, const void* ws, const int64_t* counts_host, const MrgsDensifyTensor* tensors,
                                  int32_t n_tensors, uint64_t seed, const float* noise, void* stream)
 {
-    const int rc = densify_check_cfg(cfg);
-    if (rc != MRGS_OK) return rc;
+    if (int rc = densify_check_cfg(cfg)) return rc;
     if (n_tensors < 0 || (n_tensors > 0 && !tensors)) return MRGS_E_BAD_ARG;
     if (cfg->P == 0 || n_tensors == 0) return MRGS_OK;
     if (!ws || ((uintptr_t)ws & 3) || !counts_host) return MRGS_E_BAD_ARG;
@@ -313,7 +311,7 @@ extern "C" int mrgs_densify_emit(const MrgsDensifyConfig* cfg, const void* ws, c
         if (m == 0) continue;
         densify_emit_kernel<<<dim3((unsigned)nb, (unsigned)m), 256, 0, (hipStream_t)stream>>>(a, cls, offs, t);
     }
-    return hipGetLastError() == hipSuccess ? MRGS_OK : MRGS_E_HIP;
+    return MRGS_LAUNCH_STATUS();
 }
 
 extern "C" int mrgs_densify_stats(int64_t P, const float* grad, const uint8_t* visible, const int32_t* radii, float* accum, float* denom,
@@ -323,5 +321,5 @@ extern "C" int mrgs_densify_stats(int64_t P, const float* grad, const uint8_t* v
     if (P == 0) return MRGS_OK;
     if (!grad || !visible || !accum || !denom) return MRGS_E_BAD_ARG;
     densify_stats_kernel<<<dim3((unsigned)((P + 255) / 256)), 256, 0, (hipStream_t)stream>>>(P, grad, visible, radii, accum, denom, max_radii);
-    return hipGetLastError() == hipSuccess ? MRGS_OK : MRGS_E_HIP;
+    return MRGS_LAUNCH_STATUS();
 }

@@ -36,6 +36,14 @@
 #define MRGS_G_M2(SMAX) (16 + (SMAX))
 #define MRGS_GRAD_STRIDE(S) ((18 + MRGS_SMAX(S) + 3) & ~3)
 
+// The one way an entry point reports a HIP failure (mrgs_api.hip, beside the thread-local text mrgs_last_hip_error() returns): MRGS_OK for
+// hipSuccess, otherwise records "<hipGetErrorString(e)> at <file>:<line>" for the calling thread and returns the HIP-failure code.
+int mrgs_hip_status(hipError_t e, const char* file, int line);
+// a HIP runtime call inside an entry point: a failure returns its status from the enclosing function
+#define MRGS_HIP_TRY(expr) do { if (int rc_ = mrgs_hip_status((expr), __FILE__, __LINE__)) return rc_; } while (0)
+// the launches so far: `return MRGS_LAUNCH_STATUS();` ends an entry point, `if (int rc = MRGS_LAUNCH_STATUS()) return rc;` goes inside one
+#define MRGS_LAUNCH_STATUS() mrgs_hip_status(hipGetLastError(), __FILE__, __LINE__)
+
 static inline size_t mrgs_align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 struct MrgsGeomWs {   // carved from geom_ws (all offsets 256-B aligned)

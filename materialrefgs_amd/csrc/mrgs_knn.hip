@@ -264,7 +264,7 @@ int mrgs_knn_mean_dist2(const float* points, int64_t P, float* out, void* ws, si
     hipStream_t st = (hipStream_t)stream;
     char* base = (char*)ws;
     const int n = (int)P, L = (int)w.L, T = (int)w.T;
-    if (hipMemsetAsync(base + w.zero_from, 0, w.zero_bytes, st) != hipSuccess) return MRGS_E_HIP;
+    MRGS_HIP_TRY(hipMemsetAsync(base + w.zero_from, 0, w.zero_bytes, st));
     uint32_t* bounds = (uint32_t*)(base + w.bounds);
     uint32_t* key[2] = {(uint32_t*)(base + w.key0), (uint32_t*)(base + w.key1)};
     uint32_t* val[2] = {(uint32_t*)(base + w.val0), (uint32_t*)(base + w.val1)};
@@ -280,5 +280,5 @@ int mrgs_knn_mean_dist2(const float* points, int64_t P, float* out, void* ws, si
     hipLaunchKernelGGL(knn_gather_kernel, dim3(lb), dim3(64 * KNN_WAVES), 0, st, n, L, points, val[cur], sorted, leafbox);
     hipLaunchKernelGGL(knn_top_kernel, dim3((unsigned)T), dim3(64), 0, st, L, leafbox, topbox);
     hipLaunchKernelGGL(knn_search_kernel, dim3(lb), dim3(64 * KNN_WAVES), 0, st, n, L, T, sorted, leafbox, topbox, out);
-    return hipGetLastError() == hipSuccess ? MRGS_OK : MRGS_E_HIP;
+    return MRGS_LAUNCH_STATUS();
 }

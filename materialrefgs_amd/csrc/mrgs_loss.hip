@@ -349,8 +349,7 @@ extern "C" int mrgs_loss_forward(const MrgsLossConfig* cfg, const float* image, 
                                  size_t ws_bytes, float* out_terms, float* out_loss, void* stream)
 {
     LossArgs a;
-    const int rc = make_args(cfg, image_weight != nullptr, a);
-    if (rc) return rc;
+    if (int rc = make_args(cfg, image_weight != nullptr, a)) return rc;
     if (!image || !gt || !ws || !out_terms) return MRGS_E_BAD_ARG;
     if (a.normal_mode && (!rend_normal || !surf_normal)) return MRGS_E_BAD_ARG;
     if (a.lambda_dist > 0.f && !rend_dist) return MRGS_E_BAD_ARG;
@@ -361,7 +360,7 @@ extern "C" int mrgs_loss_forward(const MrgsLossConfig* cfg, const float* image, 
     hipStream_t st = (hipStream_t)stream;
     loss_fwd_kernel<<<grid, 256, 0, st>>>(a, image, gt, rend_normal, surf_normal, rend_dist, image_weight, dmaps, partials);
     loss_finalize_kernel<<<1, 256, 0, st>>>(a, partials, (int)(grid.x * grid.y), out_terms, out_loss);
-    return hipGetLastError() == hipSuccess ? MRGS_OK : MRGS_E_HIP;
+    return MRGS_LAUNCH_STATUS();
 }
 
 extern "C" int mrgs_loss_backward(const MrgsLossConfig* cfg, const float* image, const float* gt, const float* rend_normal,
@@ -369,12 +368,11 @@ extern "C" int mrgs_loss_backward(const MrgsLossConfig* cfg, const float* image,
                                   float* g_image, float* g_rend_normal, float* g_surf_normal, float* g_rend_dist, void* stream)
 {
     LossArgs a;
-    const int rc = make_args(cfg, image_weight != nullptr, a);
-    if (rc) return rc;
+    if (int rc = make_args(cfg, image_weight != nullptr, a)) return rc;
     if (!image || !gt || !ws || !g_image) return MRGS_E_BAD_ARG;
     if (a.normal_mode && (!rend_normal || !surf_normal || !g_rend_normal || !g_surf_normal)) return MRGS_E_BAD_ARG;
     if (a.lambda_dist > 0.f && !g_rend_dist) return MRGS_E_BAD_ARG;
     loss_bwd_kernel<<<loss_grid(a), 256, 0, (hipStream_t)stream>>>(a, image, gt, rend_normal, surf_normal, image_weight, (const float*)ws,
                                                                   g_loss, g_image, g_rend_normal, g_surf_normal, g_rend_dist);
-    return hipGetLastError() == hipSuccess ? MRGS_OK : MRGS_E_HIP;
+    return MRGS_LAUNCH_STATUS();
 }

@@ -422,7 +422,7 @@ int mrgs_surfel_maps_forward(const MrgsMapsFrame* fr, const float* allmap, float
     const int HW = fr->H * fr->W;
     hipLaunchKernelGGL(surfel_maps_fwd_kernel, dim3((HW + 255) / 256), dim3(256), 0, (hipStream_t)stream, to_dev(fr), allmap, rend_normal,
                        surf_depth, surf_normal, normal_map, rend_alpha, rend_dist, rend_alpha2);
-    return hipGetLastError() == hipSuccess ? MRGS_OK : MRGS_E_HIP;
+    return MRGS_LAUNCH_STATUS();
 }
 
 int mrgs_surfel_maps_backward(const MrgsMapsFrame* fr, const float* allmap, const float* g_rend_normal, const float* g_surf_depth,
@@ -432,7 +432,7 @@ int mrgs_surfel_maps_backward(const MrgsMapsFrame* fr, const float* allmap, cons
     if (!fr || fr->H <= 0 || fr->W <= 0 || !allmap || !g_allmap) return MRGS_E_BAD_ARG;
     hipLaunchKernelGGL(surfel_maps_bwd_kernel, dim3((fr->W + MB_TX - 1) / MB_TX, (fr->H + MB_TY - 1) / MB_TY), dim3(256), 0, (hipStream_t)stream,
                        to_dev(fr), allmap, g_rend_normal, g_surf_depth, g_surf_normal, g_normal_map, g_rend_alpha, g_rend_dist, g_rend_alpha2, g_allmap);
-    return hipGetLastError() == hipSuccess ? MRGS_OK : MRGS_E_HIP;
+    return MRGS_LAUNCH_STATUS();
 }
 
 int mrgs_surfel_composite_forward(int32_t H, int32_t W, int32_t srgb, const float* base_color, const float* refl_strength, const float* specular,
@@ -442,7 +442,7 @@ int mrgs_surfel_composite_forward(int32_t H, int32_t W, int32_t srgb, const floa
     const int HW = H * W;
     hipLaunchKernelGGL(surfel_composite_fwd_kernel, dim3((HW + 255) / 256), dim3(256), 0, (hipStream_t)stream, HW, srgb, base_color,
                        refl_strength, specular, alpha, bg, render, diffuse);
-    return hipGetLastError() == hipSuccess ? MRGS_OK : MRGS_E_HIP;
+    return MRGS_LAUNCH_STATUS();
 }
 
 int mrgs_surfel_composite_backward(int32_t H, int32_t W, int32_t srgb, const float* base_color, const float* refl_strength,
@@ -455,7 +455,7 @@ int mrgs_surfel_composite_backward(int32_t H, int32_t W, int32_t srgb, const flo
     const int HW = H * W;
     hipLaunchKernelGGL(surfel_composite_bwd_kernel, dim3((HW + 255) / 256), dim3(256), 0, (hipStream_t)stream, HW, srgb, base_color,
                        refl_strength, specular, bg, g_render, g_diffuse, g_base, g_refl, g_specular, g_alpha, zero_fill, (long long)zero_floats);
-    return hipGetLastError() == hipSuccess ? MRGS_OK : MRGS_E_HIP;
+    return MRGS_LAUNCH_STATUS();
 }
 
 int mrgs_indirect_blend_forward(int32_t H, int32_t W, const float* direct, const float* weight, const MrgsStridedMap* indirect,
@@ -467,7 +467,7 @@ int mrgs_indirect_blend_forward(int32_t H, int32_t W, const float* direct, const
     const BlendMap ma = {alpha->ptr, (long long)alpha->stride_h, (long long)alpha->stride_w, (long long)alpha->stride_c};
     hipLaunchKernelGGL(indirect_blend_fwd_kernel, dim3((H * W + 255) / 256), dim3(256), 0, (hipStream_t)stream, H, W, direct, weight, mi, ma,
                        visibility, specular, indirect_color);
-    return hipGetLastError() == hipSuccess ? MRGS_OK : MRGS_E_HIP;
+    return MRGS_LAUNCH_STATUS();
 }
 
 int mrgs_indirect_blend_backward(int32_t H, int32_t W, const float* direct, const float* weight, const MrgsStridedMap* indirect,
@@ -481,7 +481,7 @@ int mrgs_indirect_blend_backward(int32_t H, int32_t W, const float* direct, cons
     const BlendMap ma = {alpha->ptr, (long long)alpha->stride_h, (long long)alpha->stride_w, (long long)alpha->stride_c};
     hipLaunchKernelGGL(indirect_blend_bwd_kernel, dim3((H * W + 255) / 256), dim3(256), 0, (hipStream_t)stream, H, W, direct, weight, mi, ma,
                        visibility, g_specular, g_indirect_color, g_direct, g_weight, g_indirect, g_alpha);
-    return hipGetLastError() == hipSuccess ? MRGS_OK : MRGS_E_HIP;
+    return MRGS_LAUNCH_STATUS();
 }
 
 int mrgs_surfel_feature_grads(int32_t H, int32_t W, const float* g_refl_composite, const float* g_refl_shade, const float* g_roughness,
@@ -492,7 +492,7 @@ int mrgs_surfel_feature_grads(int32_t H, int32_t W, const float* g_refl_composit
     const int HW = H * W;
     hipLaunchKernelGGL(surfel_feature_grads_kernel, dim3((HW + 255) / 256), dim3(256), 0, (hipStream_t)stream, HW, g_refl_composite, g_refl_shade,
                        g_roughness, g_albedo_hwc, g_indirect_hwc, g_features, g_alpha_a, g_alpha_b, g_alpha_c, g_alpha);
-    return hipGetLastError() == hipSuccess ? MRGS_OK : MRGS_E_HIP;
+    return MRGS_LAUNCH_STATUS();
 }
 
 }   // extern "C"

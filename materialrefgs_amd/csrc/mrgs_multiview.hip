@@ -727,10 +727,10 @@ int draw_samples(const WarpArgs& a, const WarpWs& w, int32_t* samples, hipStream
 {
     const int HW = a.H * a.W, nbg = (HW + WB - 1) / WB;
     if (a.n_given >= 0) {
-        if (hipMemsetAsync(w.slot, 0xFF, (size_t)HW * 4, st) != hipSuccess) return MRGS_E_HIP;
+        MRGS_HIP_TRY(hipMemsetAsync(w.slot, 0xFF, (size_t)HW * 4, st));
         if (a.n_given > 0) warp_given_samples<<<(a.n_given + WB - 1) / WB, WB, 0, st>>>(a, w, samples);
     } else {
-        if (hipMemsetAsync(w.hist, 0, 2 * (size_t)NBINS * 4, st) != hipSuccess) return MRGS_E_HIP;
+        MRGS_HIP_TRY(hipMemsetAsync(w.hist, 0, 2 * (size_t)NBINS * 4, st));
         warp_sel_hist<<<nbg, WB, 0, st>>>(a, w, 0);
         warp_sel_scan<<<1, FIN, 0, st>>>(w, 0);
         warp_sel_hist<<<nbg, WB, 0, st>>>(a, w, 1);
@@ -738,7 +738,7 @@ int draw_samples(const WarpArgs& a, const WarpWs& w, int32_t* samples, hipStream
         warp_compact_count<<<nbg, WB, 0, st>>>(a, w);
         warp_compact_scan<<<1, FIN, 0, st>>>(w, nbg);
         warp_compact_write<<<nbg, WB, 0, st>>>(a, w);
-        if (samples && hipMemcpyAsync(samples, w.samples, (size_t)a.k * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return MRGS_E_HIP;
+        if (samples) MRGS_HIP_TRY(hipMemcpyAsync(samples, w.samples, (size_t)a.k * 4, hipMemcpyDeviceToDevice, st));
     }
     return MRGS_OK;
 }
@@ -767,13 +767,13 @@ extern "C" int mrgs_warp_loss_forward(const MrgsWarpConfig* cfg, const MrgsWarpM
     const int HW = a.H * a.W, nbg = (HW + WB - 1) / WB;
     warp_geo_fwd<<<nbg, WB, 0, st>>>(a, maps->depth_v, maps->depth_n, maps->cam_v, maps->cam_n, w, weight_map);
     warp_geo_finalize<<<1, FIN, 0, st>>>(a, w, nbg, out_terms, out_counts);
-    if (!(a.flags & MRGS_WARP_MATERIAL)) return hipGetLastError() == hipSuccess ? MRGS_OK : MRGS_E_HIP;
+    if (!(a.flags & MRGS_WARP_MATERIAL)) return MRGS_LAUNCH_STATUS();
     if ((rc = draw_samples(a, w, samples, st))) return rc;
     const Maps m = make_maps(maps);
     const int ns_max = a.n_given >= 0 ? a.n_given : a.k;
     if (ns_max > 0) warp_patch_fwd<<<(ns_max + WB / 64 - 1) / (WB / 64), WB, 0, st>>>(a, w, m, maps->cam_v, maps->cam_n, weight_map);
     warp_patch_finalize<<<1, FIN, 0, st>>>(a, w, out_terms, out_counts);
-    return hipGetLastError() == hipSuccess ? MRGS_OK : MRGS_E_HIP;
+    return MRGS_LAUNCH_STATUS();
 }
 
 extern "C" int mrgs_warp_loss_backward(const MrgsWarpConfig* cfg, const MrgsWarpMaps* maps, const void* ws, const float* weight_map,
@@ -790,11 +790,11 @@ extern "C" int mrgs_warp_loss_backward(const MrgsWarpConfig* cfg, const MrgsWarp
     hipStream_t st = (hipStream_t)stream;
     const size_t HW = (size_t)a.H * a.W;
     const int nbg = (int)((HW + WB - 1) / WB);
-    if (g_depth_n && hipMemsetAsync(g_depth_n, 0, HW * 4, st) != hipSuccess) return MRGS_E_HIP;
+    if (g_depth_n) MRGS_HIP_TRY(hipMemsetAsync(g_depth_n, 0, HW * 4, st));
     if ((g_depth_v || g_depth_n) && (a.flags & MRGS_WARP_GEO))
         warp_geo_bwd<<<nbg, WB, 0, st>>>(a, maps->depth_v, maps->depth_n, maps->cam_v, maps->cam_n, w, weight_map, g_terms, g_depth_v, g_depth_n);
-    else if (g_depth_v && hipMemsetAsync(g_depth_v, 0, HW * 4, st) != hipSuccess)
-        return MRGS_E_HIP;
+    else if (g_depth_v)
+        MRGS_HIP_TRY(hipMemsetAsync(g_depth_v, 0, HW * 4, st));
     GradMaps g{g_base_v, (a.flags & MRGS_WARP_METALLIC) ? g_metal_v : nullptr, (a.flags & MRGS_WARP_ROUGHNESS) ? g_rough_v : nullptr,
                g_base_n, (a.flags & MRGS_WARP_METALLIC) ? g_metal_n : nullptr, (a.flags & MRGS_WARP_ROUGHNESS) ? g_rough_n : nullptr};
     float* outs[6] = {g_base_v, g_metal_v, g_rough_v, g_base_n, g_metal_n, g_rough_n};
@@ -804,7 +804,7 @@ extern "C" int mrgs_warp_loss_backward(const MrgsWarpConfig* cfg, const MrgsWarp
     // view maps the gather does not write, and every neighbour map (the scatter accumulates): cleared
     for (int i = 0; i < 6; ++i)
         if (outs[i] && (!material || i >= 3 || !used[i]))
-            if (hipMemsetAsync(outs[i], 0, chans[i] * HW * 4, st) != hipSuccess) return MRGS_E_HIP;
+            MRGS_HIP_TRY(hipMemsetAsync(outs[i], 0, chans[i] * HW * 4, st));
     if (material) {
         const Maps m = make_maps(maps);
         if (g.base_v || g.metal_v || g.rough_v) warp_view_gather<<<nbg, WB, 0, st>>>(a, w, m, g_terms, g);
@@ -812,7 +812,7 @@ extern "C" int mrgs_warp_loss_backward(const MrgsWarpConfig* cfg, const MrgsWarp
         if ((g.base_n || g.metal_n || g.rough_n) && ns_max > 0)
             warp_nbr_scatter<<<(ns_max + WB / 64 - 1) / (WB / 64), WB, 0, st>>>(a, w, m, g_terms, g);
     }
-    return hipGetLastError() == hipSuccess ? MRGS_OK : MRGS_E_HIP;
+    return MRGS_LAUNCH_STATUS();
 }
 
 // ---- grey-image patch NCC (get_consistency_loss2 over lncc; train_refreal.py:358-395, utils/loss_utils.py:230-265) -----------------
@@ -1006,8 +1006,7 @@ __global__ __launch_bounds__(WB) void warp_ncc_bwd(int HW, const int32_t* __rest
 // the NCC calls accept the configuration of the material call they follow
 int ncc_args(const MrgsWarpConfig* cfg, const MrgsWarpMaps* mp, float ncc_w, WarpArgs& a)
 {
-    const int rc = make_args(cfg, a);
-    if (rc) return rc;
+    if (int rc = make_args(cfg, a)) return rc;
     if (!(ncc_w == ncc_w)) return MRGS_E_BAD_ARG;
     if (mp && (!mp->cam_v || !mp->cam_n || !mp->normal_v || !mp->distance_v || !mp->metal_v || !mp->metal_n)) return MRGS_E_BAD_ARG;
     return MRGS_OK;
@@ -1028,8 +1027,7 @@ extern "C" int mrgs_warp_ncc_forward(const MrgsWarpConfig* cfg, const MrgsWarpMa
 {
     WarpArgs a;
     if (!maps) return MRGS_E_BAD_ARG;
-    const int rc = ncc_args(cfg, maps, ncc_weight, a);
-    if (rc) return rc;
+    if (int rc = ncc_args(cfg, maps, ncc_weight, a)) return rc;
     if (!grey_v || !grey_n || !weight_map || !warp_ws || !ws || !out_term || !out_counts || !ref_weight_map) return MRGS_E_BAD_ARG;
     if (a.n_given > 0 && !(a.flags & MRGS_WARP_MATERIAL) && !samples) return MRGS_E_BAD_ARG;
     if (warp_ws_bytes < ws_layout(a.H, a.W, a.k, nullptr, nullptr) || ws_bytes < ncc_layout(a.H, a.W, a.k, nullptr, nullptr))
@@ -1040,8 +1038,8 @@ extern "C" int mrgs_warp_ncc_forward(const MrgsWarpConfig* cfg, const MrgsWarpMa
     ncc_layout(a.H, a.W, a.k, &n, (char*)ws);
     hipStream_t st = (hipStream_t)stream;
     const int HW = a.H * a.W;
-    if (hipMemcpyAsync(n.st, w.st, ST_WORDS * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return MRGS_E_HIP;
-    if (hipMemsetAsync(ref_weight_map, 0, (size_t)HW * 4, st) != hipSuccess) return MRGS_E_HIP;
+    MRGS_HIP_TRY(hipMemcpyAsync(n.st, w.st, ST_WORDS * 4, hipMemcpyDeviceToDevice, st));
+    MRGS_HIP_TRY(hipMemsetAsync(ref_weight_map, 0, (size_t)HW * 4, st));
     NccIn in{maps->normal_v, maps->distance_v, maps->metal_v, maps->metal_n, grey_v, grey_n, maps->cam_v, maps->cam_n, weight_map,
              w.samples, w.homog};
     if (!(a.flags & MRGS_WARP_MATERIAL)) {
@@ -1056,15 +1054,14 @@ extern "C" int mrgs_warp_ncc_forward(const MrgsWarpConfig* cfg, const MrgsWarpMa
     const int ns_max = a.n_given >= 0 ? a.n_given : a.k;
     if (ns_max > 0) warp_ncc_fwd<<<(ns_max + WB / 64 - 1) / (WB / 64), WB, 0, st>>>(a, in, n, ref_weight_map, out_ncc, out_use);
     warp_ncc_finalize<<<1, FIN, 0, st>>>(n, ncc_weight, out_term, out_counts);
-    return hipGetLastError() == hipSuccess ? MRGS_OK : MRGS_E_HIP;
+    return MRGS_LAUNCH_STATUS();
 }
 
 extern "C" int mrgs_warp_ncc_backward(const MrgsWarpConfig* cfg, const void* warp_ws, const void* ws, float ncc_weight, const float* g_term,
                                       float* g_normal_v, float* g_distance_v, void* stream)
 {
     WarpArgs a;
-    const int rc = ncc_args(cfg, nullptr, ncc_weight, a);
-    if (rc) return rc;
+    if (int rc = ncc_args(cfg, nullptr, ncc_weight, a)) return rc;
     if (!warp_ws || !ws || !g_term) return MRGS_E_BAD_ARG;
     if (!g_normal_v && !g_distance_v) return MRGS_OK;
     WarpWs w;
@@ -1074,5 +1071,5 @@ extern "C" int mrgs_warp_ncc_backward(const MrgsWarpConfig* cfg, const void* war
     const int HW = a.H * a.W;
     const int32_t* slot = (a.flags & MRGS_WARP_MATERIAL) ? w.slot : n.slot;
     warp_ncc_bwd<<<(HW + WB - 1) / WB, WB, 0, (hipStream_t)stream>>>(HW, slot, n, ncc_weight, g_term, g_normal_v, g_distance_v);
-    return hipGetLastError() == hipSuccess ? MRGS_OK : MRGS_E_HIP;
+    return MRGS_LAUNCH_STATUS();
 }

@@ -113,7 +113,7 @@ extern "C" int mrgs_adam_step(const MrgsAdamTensor* tensors, int32_t n_tensors, 
         if (vec) adam_kernel<true><<<dim3(chunks), 256, 0, st>>>(t);
         else adam_kernel<false><<<dim3(chunks), 256, 0, st>>>(t);
     }
-    return hipGetLastError() == hipSuccess ? MRGS_OK : MRGS_E_HIP;
+    return MRGS_LAUNCH_STATUS();
 }
 
 // ---- densify / prune compaction (scene/gaussian_model.py:856-905: _prune_optimizer + prune_points) -------------------------------
@@ -202,7 +202,7 @@ extern "C" int mrgs_compact_count(int64_t n_rows, const uint8_t* keep, void* ws,
 {
     if (n_rows < 0 || !ws || !count_dev || ws_bytes < mrgs_compact_ws_bytes(n_rows)) return MRGS_E_BAD_ARG;
     hipStream_t st = (hipStream_t)stream;
-    if (n_rows == 0) return hipMemsetAsync(count_dev, 0, sizeof(int64_t), st) == hipSuccess ? MRGS_OK : MRGS_E_HIP;
+    if (n_rows == 0) { MRGS_HIP_TRY(hipMemsetAsync(count_dev, 0, sizeof(int64_t), st)); return MRGS_OK; }
     if (!keep) return MRGS_E_BAD_ARG;
     const long long nb = (n_rows + COMPACT_ROWS - 1) / COMPACT_ROWS;
     if (nb > (1 << 22)) return MRGS_E_UNSUPPORTED;
@@ -210,7 +210,7 @@ extern "C" int mrgs_compact_count(int64_t n_rows, const uint8_t* keep, void* ws,
     unsigned* offs = counts + nb;
     compact_count_kernel<<<dim3((unsigned)nb), 256, 0, st>>>(n_rows, keep, counts);
     compact_scan_kernel<<<1, 1024, 0, st>>>((int)nb, counts, offs, (long long*)count_dev);
-    return hipGetLastError() == hipSuccess ? MRGS_OK : MRGS_E_HIP;
+    return MRGS_LAUNCH_STATUS();
 }
 
 extern "C" int mrgs_compact_rows(int64_t n_rows, const uint8_t* keep, const void* ws, const MrgsCompactTensor* tensors, int32_t n_tensors,
@@ -234,5 +234,5 @@ extern "C" int mrgs_compact_rows(int64_t n_rows, const uint8_t* keep, const void
         if (m == 0) continue;
         compact_gather_kernel<<<dim3((unsigned)nb, (unsigned)m), 256, 0, (hipStream_t)stream>>>(n_rows, keep, offs, t);
     }
-    return hipGetLastError() == hipSuccess ? MRGS_OK : MRGS_E_HIP;
+    return MRGS_LAUNCH_STATUS();
 }

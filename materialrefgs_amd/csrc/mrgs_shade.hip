@@ -1310,26 +1310,24 @@ extern "C" {
 int mrgs_envmap_lookup_forward(const MrgsEnvMips* mips, int64_t N, const float* dirs, const float* roughness, float* out, void* stream)
 {
     EnvMips m;
-    int rc = make_mips(mips, m);
-    if (rc) return rc;
+    if (int rc = make_mips(mips, m)) return rc;
     if (N < 0 || (N > 0 && (!dirs || !out))) return MRGS_E_BAD_ARG;
     if (N == 0) return MRGS_OK;
     hipLaunchKernelGGL(envmap_lookup_fwd_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, (hipStream_t)stream, m, (long long)N, dirs,
                        roughness, out);
-    return hipGetLastError() == hipSuccess ? MRGS_OK : MRGS_E_HIP;
+    return MRGS_LAUNCH_STATUS();
 }
 
 int mrgs_envmap_lookup_backward(const MrgsEnvMips* mips, int64_t N, const float* dirs, const float* roughness, const float* g_out,
                                 float* g_dirs, float* g_roughness, void* stream)
 {
     EnvMips m;
-    int rc = make_mips(mips, m);
-    if (rc) return rc;
+    if (int rc = make_mips(mips, m)) return rc;
     if (N < 0 || (N > 0 && (!dirs || !g_out))) return MRGS_E_BAD_ARG;
     if (N == 0) return MRGS_OK;
     hipLaunchKernelGGL(envmap_lookup_bwd_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, (hipStream_t)stream, m, (long long)N, dirs,
                        roughness, g_out, g_dirs, g_roughness);
-    return hipGetLastError() == hipSuccess ? MRGS_OK : MRGS_E_HIP;
+    return MRGS_LAUNCH_STATUS();
 }
 
 static int shade_specular_forward_impl(const MrgsEnvMips* mips, const MrgsShadeFrame* fr, float* specular, float* direct_light, float* specular_weight,
@@ -1337,8 +1335,7 @@ static int shade_specular_forward_impl(const MrgsEnvMips* mips, const MrgsShadeF
                                        int64_t zero_floats, void* stream)
 {
     EnvMips m;
-    int rc = make_mips(mips, m);
-    if (rc) return rc;
+    if (int rc = make_mips(mips, m)) return rc;
     if (!fr || fr->H <= 0 || fr->W <= 0 || !fr->R || !fr->T || !fr->lut || fr->lut_res < 1 || !specular || !direct_light || !specular_weight)
         return MRGS_E_BAD_ARG;
     if (zero_floats < 0 || (zero_floats > 0 && !zero_fill)) return MRGS_E_BAD_ARG;
@@ -1349,7 +1346,7 @@ static int shade_specular_forward_impl(const MrgsEnvMips* mips, const MrgsShadeF
     hipLaunchKernelGGL(shade_specular_fwd_kernel, grid, block, 0, (hipStream_t)stream, m, cam, fr->H, fr->W, to_map(fr->albedo), to_map(fr->normal),
                        to_map(fr->alpha), to_map(fr->refl), to_map(fr->roughness), fr->lut, fr->lut_res, specular, direct_light, specular_weight,
                        base_color, bg, srgb, render, diffuse, zero_fill, (long long)zero_floats);
-    return hipGetLastError() == hipSuccess ? MRGS_OK : MRGS_E_HIP;
+    return MRGS_LAUNCH_STATUS();
 }
 
 int mrgs_shade_specular_forward(const MrgsEnvMips* mips, const MrgsShadeFrame* fr, float* specular, float* direct_light, float* specular_weight,
@@ -1375,8 +1372,7 @@ static int shade_specular_backward_impl(const MrgsEnvMips* mips, const MrgsShade
                                         float* g_roughness, float* g_features, const ShadeCompositeArgs* composite, void* stream)
 {
     EnvMips m;
-    int rc = make_mips(mips, m);
-    if (rc) return rc;
+    if (int rc = make_mips(mips, m)) return rc;
     if (!fr || fr->H <= 0 || fr->W <= 0 || !fr->R || !fr->T || !fr->lut || !g_normal || !g_alpha) return MRGS_E_BAD_ARG;
     if (composite ? (!g_features || !composite->base || !composite->spec_fwd || !composite->bg || !composite->g_base)
                   : (!g_albedo || !g_refl || !g_roughness)) return MRGS_E_BAD_ARG;
@@ -1413,7 +1409,7 @@ static int shade_specular_backward_impl(const MrgsEnvMips* mips, const MrgsShade
                            to_map(fr->alpha), to_map(fr->refl), to_map(fr->roughness), fr->lut, fr->lut_res, g_specular, g_direct_light, g_specular_weight,
                            g_albedo, g_normal, g_alpha, g_refl, g_roughness, tiles_x, ntiles, lds_floats, g_features, (const float*)nullptr, (const float*)nullptr,
                            0, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (float*)nullptr);
-    return hipGetLastError() == hipSuccess ? MRGS_OK : MRGS_E_HIP;
+    return MRGS_LAUNCH_STATUS();
 }
 
 int mrgs_shade_specular_backward(const MrgsEnvMips* mips, const MrgsShadeFrame* fr, const float* g_specular, const float* g_direct_light,
@@ -1441,7 +1437,7 @@ int mrgs_cubemap_filter_count(int32_t res, int32_t kind, float roughness, float 
     const int NT = 6 * res * res;
     hipLaunchKernelGGL(cubemap_filter_build_kernel<0>, dim3((NT + 255) / 256), dim3(256), 0, (hipStream_t)stream, res, kind, roughness, cos_cutoff,
                        row_count, row_wsum, (const uint32_t*)nullptr, (uint32_t*)nullptr, (float*)nullptr);
-    return hipGetLastError() == hipSuccess ? MRGS_OK : MRGS_E_HIP;
+    return MRGS_LAUNCH_STATUS();
 }
 
 int mrgs_cubemap_filter_fill(int32_t res, int32_t kind, float roughness, float cos_cutoff, const uint32_t* row_ptr, const float* row_wsum,
@@ -1451,7 +1447,7 @@ int mrgs_cubemap_filter_fill(int32_t res, int32_t kind, float roughness, float c
     const int NT = 6 * res * res;
     hipLaunchKernelGGL(cubemap_filter_build_kernel<1>, dim3((NT + 255) / 256), dim3(256), 0, (hipStream_t)stream, res, kind, roughness, cos_cutoff,
                        (uint32_t*)nullptr, const_cast<float*>(row_wsum), row_ptr, col, val);
-    return hipGetLastError() == hipSuccess ? MRGS_OK : MRGS_E_HIP;
+    return MRGS_LAUNCH_STATUS();
 }
 
 int mrgs_csr_spmv3(int32_t nrows, const uint32_t* row_ptr, const void* col, int32_t col_bytes, const void* val, int32_t val_bytes,
@@ -1464,7 +1460,7 @@ int mrgs_csr_spmv3(int32_t nrows, const uint32_t* row_ptr, const void* col, int3
         if (col_bytes != 2 || lanes_per_row < 64 || (nrows & 3) || ((uintptr_t)x & 15u) || ((uintptr_t)val & 7u)) return MRGS_E_BAD_ARG;
         hipLaunchKernelGGL(csr_spmv3_blk4_kernel, dim3((unsigned)(((size_t)nrows * 64 + 255) / 256)), dim3(256), 0, st, nrows, row_ptr, (const uint16_t*)col,
                            (const uint2*)val, row_scale, x, y);
-        return hipGetLastError() == hipSuccess ? MRGS_OK : MRGS_E_HIP;
+        return MRGS_LAUNCH_STATUS();
     }
     const bool wide = lanes_per_row >= 64;
     const dim3 g(wide ? (unsigned)(((size_t)nrows * 64 + 255) / 256) : (unsigned)(((size_t)nrows * 4 + 255) / 256)), b(256);
@@ -1477,7 +1473,7 @@ int mrgs_csr_spmv3(int32_t nrows, const uint32_t* row_ptr, const void* col, int3
         else { if (val_bytes == 2) SPMV(4, uint32_t, uint16_t); else SPMV(4, uint32_t, float); }
     }
 #undef SPMV
-    return hipGetLastError() == hipSuccess ? MRGS_OK : MRGS_E_HIP;
+    return MRGS_LAUNCH_STATUS();
 }
 
 int mrgs_cube_symmetry_rows(int32_t res, int32_t* rows)
@@ -1539,7 +1535,7 @@ int mrgs_csr_spmv3_batched(const MrgsSpmvDesc* descs, int32_t n, void* stream)
     if (const char* tp = getenv("MRGS_SPMV_TRACE_BUF")) B.trace = (unsigned long long*)strtoull(tp, nullptr, 16);     // developer build: per-wave timestamps
 #endif
     hipLaunchKernelGGL(csr_spmv3_batched_kernel, dim3((unsigned)blocks), dim3(MRGS_SPMV_BATCH_THREADS), lds, (hipStream_t)stream, B);
-    return hipGetLastError() == hipSuccess ? MRGS_OK : MRGS_E_HIP;
+    return MRGS_LAUNCH_STATUS();
 }
 
 int mrgs_cubemap_mip_chain_forward(int32_t res_in, int32_t n_steps, const float* in, float* const* outs, void* stream)
@@ -1562,7 +1558,7 @@ int mrgs_cubemap_mip_chain_forward(int32_t res_in, int32_t n_steps, const float*
         res = Nc;
         done += steps;
     }
-    return hipGetLastError() == hipSuccess ? MRGS_OK : MRGS_E_HIP;
+    return MRGS_LAUNCH_STATUS();
 }
 
 int mrgs_cubemap_mip_chain_backward(int32_t res0, int32_t n_levels, float* const* g, void* stream)
@@ -1580,7 +1576,7 @@ int mrgs_cubemap_mip_chain_backward(int32_t res0, int32_t n_levels, float* const
         const int N = res0 >> k, n = 6 * N * N;
         hipLaunchKernelGGL(cubemap_mip_bwd_kernel, dim3((n + 255) / 256), dim3(256), 0, st, N, g[k + 1], g[k]);
     }
-    return hipGetLastError() == hipSuccess ? MRGS_OK : MRGS_E_HIP;
+    return MRGS_LAUNCH_STATUS();
 }
 
 int mrgs_cubemap_mip_forward(int32_t res_out, const float* in, float* out, void* stream)
@@ -1588,7 +1584,7 @@ int mrgs_cubemap_mip_forward(int32_t res_out, const float* in, float* out, void*
     if (res_out < 1 || !in || !out) return MRGS_E_BAD_ARG;
     const int n = 6 * res_out * res_out * 3;
     hipLaunchKernelGGL(cubemap_mip_fwd_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, res_out, in, out);
-    return hipGetLastError() == hipSuccess ? MRGS_OK : MRGS_E_HIP;
+    return MRGS_LAUNCH_STATUS();
 }
 
 int mrgs_cubemap_mip_backward(int32_t res_fine, const float* dout, float* g_fine, void* stream)
@@ -1596,7 +1592,7 @@ int mrgs_cubemap_mip_backward(int32_t res_fine, const float* dout, float* g_fine
     if (res_fine < 2 || (res_fine & 1) || !dout || !g_fine) return MRGS_E_BAD_ARG;
     const int n = 6 * res_fine * res_fine;
     hipLaunchKernelGGL(cubemap_mip_bwd_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, res_fine, dout, g_fine);
-    return hipGetLastError() == hipSuccess ? MRGS_OK : MRGS_E_HIP;
+    return MRGS_LAUNCH_STATUS();
 }
 
 }   // extern "C"

@@ -389,7 +389,7 @@ int mrgs_sh_grad_expand_surfel(int32_t P, int32_t D, int32_t V, const float* xyz
     hipLaunchKernelGGL(sh_grad_expand_surfel_kernel, dim3((P + 255) / 256), dim3(256), 0, (hipStream_t)stream, P, D, V, xyz, rotation_raw, gathered,
                        (long long)row_stride, gathered + 3 * (size_t)P, (long long)row_stride, gathered + 6 * (size_t)P, (long long)row_stride,
                        g_features_dc, g_features_rest, g_indirect_dc, g_indirect_rest);
-    return hipGetLastError() == hipSuccess ? MRGS_OK : MRGS_E_HIP;
+    return MRGS_LAUNCH_STATUS();
 }
 
 int mrgs_sh_grad_expand_surfel_rows(int32_t P, int32_t D, int32_t V, const float* xyz, const float* rotation_raw, const float* rgb_rows,
@@ -404,7 +404,7 @@ int mrgs_sh_grad_expand_surfel_rows(int32_t P, int32_t D, int32_t V, const float
     hipLaunchKernelGGL(sh_grad_expand_surfel_kernel, dim3((P + 255) / 256), dim3(256), 0, (hipStream_t)stream, P, D, V, xyz, rotation_raw, rgb_rows,
                        (long long)rgb_stride, ind_rows, (long long)ind_stride, campos_rows, (long long)campos_stride, g_features_dc, g_features_rest,
                        g_indirect_dc, g_indirect_rest);
-    return hipGetLastError() == hipSuccess ? MRGS_OK : MRGS_E_HIP;
+    return MRGS_LAUNCH_STATUS();
 }
 
 int mrgs_sh_grad_expand(int32_t P, int32_t M, int32_t D, int32_t V, const float* means3D, const float* gathered, int64_t row_stride,
@@ -420,7 +420,7 @@ int mrgs_sh_grad_expand(int32_t P, int32_t M, int32_t D, int32_t V, const float*
     else
         hipLaunchKernelGGL(sh_grad_expand_kernel<false>, dim3((P + 255) / 256), dim3(256), 0, (hipStream_t)stream, P, M, D, V, means3D, gathered,
                            (long long)row_stride, dL_dsh);
-    return hipGetLastError() == hipSuccess ? MRGS_OK : MRGS_E_HIP;
+    return MRGS_LAUNCH_STATUS();
 }
 
 
@@ -433,7 +433,7 @@ int mrgs_surfel_features_forward(const MrgsSurfelParams* p, float* opacity, floa
         return MRGS_E_BAD_ARG;
     hipLaunchKernelGGL(surfel_features_fwd_kernel, dim3((p->P + 255) / 256), dim3(256), 0, (hipStream_t)stream, *p, opacity, scales,
                        rotations, features);
-    return hipGetLastError() == hipSuccess ? MRGS_OK : MRGS_E_HIP;
+    return MRGS_LAUNCH_STATUS();
 }
 
 int mrgs_surfel_features_backward(const MrgsSurfelParams* p, const float* g_opacity, const float* g_scales, const float* g_rotations,
@@ -449,7 +449,7 @@ int mrgs_surfel_features_backward(const MrgsSurfelParams* p, const float* g_opac
         return MRGS_E_BAD_ARG;
     hipLaunchKernelGGL(surfel_features_bwd_kernel, dim3((p->P + 255) / 256), dim3(256), 0, (hipStream_t)stream, *p, g_opacity, g_scales,
                        g_rotations, g_features, *grads, g_xyz_upstream);
-    return hipGetLastError() == hipSuccess ? MRGS_OK : MRGS_E_HIP;
+    return MRGS_LAUNCH_STATUS();
 }
 
 }   // extern "C"

@@ -1567,7 +1567,7 @@ int mrgs_surfel_bvh_build(const float* quad_vertices, int64_t n_surfels, void* b
     hipStream_t st = (hipStream_t)stream;
     char* base = (char*)ws;
     const int P = (int)n_surfels;
-    if (hipMemsetAsync(base + w.zero_from, 0, w.zero_bytes, st) != hipSuccess) return MRGS_E_HIP;
+    MRGS_HIP_TRY(hipMemsetAsync(base + w.zero_from, 0, w.zero_bytes, st));
     float* aabb = (float*)(base + w.aabb);
     uint32_t* bounds = (uint32_t*)(base + w.bounds);
     uint32_t* key[2] = {(uint32_t*)(base + w.key0), (uint32_t*)(base + w.key1)};
@@ -1577,13 +1577,13 @@ int mrgs_surfel_bvh_build(const float* quad_vertices, int64_t n_surfels, void* b
                        bounds + 9, bounds);
     hipLaunchKernelGGL(st_morton_kernel, dim3(nb), dim3(256), 0, st, P, aabb, bounds, key[0], val[0]);
     const int cur = mrgs_radix_sort_pairs(key, val, (uint32_t*)(base + w.sortws), bounds + 8, n_surfels, nullptr, 0, 3 * ST_MORTON_AXIS_BITS <= 24 ? 24 : 32, st);
-    if (hipMemcpyAsync(blob, val[cur], (size_t)P * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return MRGS_E_HIP;      // the sorted order
+    MRGS_HIP_TRY(hipMemcpyAsync(blob, val[cur], (size_t)P * 4, hipMemcpyDeviceToDevice, st));      // the sorted order
     const StWide wd = st_wide(n_surfels);
     const BlobLayout bl = st_blob(n_surfels);
     for (int l = 0; l < wd.n; ++l)
         hipLaunchKernelGGL(st_wide_level_kernel, dim3(wd.cnt[l]), dim3(64), 0, st, l, l == 0 ? P : wd.cnt[l - 1], wd, val[cur], aabb,
                            (float*)((char*)blob + bl.wide_boxes), (unsigned long long*)((char*)blob + bl.wide_vmask));
-    return hipGetLastError() == hipSuccess ? MRGS_OK : MRGS_E_HIP;
+    return MRGS_LAUNCH_STATUS();
 }
 
 // start-of-trace initialisation in one launch (see st_launch): `defer` = header (16 words) + list, directly followed by the record header
@@ -1674,7 +1674,7 @@ static int st_launch(bool bwd, void* blob, int64_t n_surfels, int64_t n_rays, in
         hipLaunchKernelGGL(st_trace_kernel<1>, grid, dim3(ST_THREADS), 0, st, a, a.geom_leaf, wide_boxes, wide_vmask);
         hipLaunchKernelGGL(st_trace_rest_kernel<1>, rgrid, dim3(ST_THREADS), 0, st, a, a.geom_leaf, wide_boxes, wide_vmask, a.lone_list);
     }
-    return hipGetLastError() == hipSuccess ? MRGS_OK : MRGS_E_HIP;
+    return MRGS_LAUNCH_STATUS();
 }
 
 int mrgs_surfel_trace_forward(void* blob, int64_t n_surfels, int64_t n_rays, int32_t ray_width, const float* ray_o, const float* ray_d, const float* geom,
@@ -1684,18 +1684,19 @@ int mrgs_surfel_trace_forward(void* blob, int64_t n_surfels, int64_t n_rays, int
     if (n_rays < 0 || n_surfels < 0 || n_surfels > (int64_t)1 << 24 || !st_ray_count_supported(n_rays, ray_width)) return MRGS_E_UNSUPPORTED;
     hipStream_t st = (hipStream_t)stream;
     if (n_rays == 0) {                                                     // nothing traced: every surfel's weight sum is zero
-        if (n_surfels > 0 && wet && hipMemsetAsync(wet, 0, (size_t)n_surfels * 4, st) != hipSuccess) return MRGS_E_HIP;
+        if (n_surfels > 0 && wet) MRGS_HIP_TRY(hipMemsetAsync(wet, 0, (size_t)n_surfels * 4, st));
         return MRGS_OK;
     }
     if (!bg_host || !rgb || !dpt || !acc || !norm || !dist || !aux) return MRGS_E_BAD_ARG;
     if (n_surfels > 0 && (!ray_o || !ray_d || !state || !blob || !geom || !attr || !wet)) return MRGS_E_BAD_ARG;
     if (n_surfels == 0) {                                                  // nothing to hit: background everywhere
-        if (hipMemsetAsync(dpt, 0, n_rays * 4, st) != hipSuccess || hipMemsetAsync(acc, 0, n_rays * 4, st) != hipSuccess ||
-            hipMemsetAsync(norm, 0, n_rays * 12, st) != hipSuccess || hipMemsetAsync(dist, 0, n_rays * 4, st) != hipSuccess ||
-            hipMemsetAsync(aux, 0, n_rays * 8, st) != hipSuccess)
-            return MRGS_E_HIP;
+        MRGS_HIP_TRY(hipMemsetAsync(dpt, 0, n_rays * 4, st));
+        MRGS_HIP_TRY(hipMemsetAsync(acc, 0, n_rays * 4, st));
+        MRGS_HIP_TRY(hipMemsetAsync(norm, 0, n_rays * 12, st));
+        MRGS_HIP_TRY(hipMemsetAsync(dist, 0, n_rays * 4, st));
+        MRGS_HIP_TRY(hipMemsetAsync(aux, 0, n_rays * 8, st));
         hipLaunchKernelGGL(st_fill_bg_kernel, dim3((unsigned)((n_rays + 255) / 256)), dim3(256), 0, st, n_rays, bg_host[0], bg_host[1], bg_host[2], rgb);
-        return hipGetLastError() == hipSuccess ? MRGS_OK : MRGS_E_HIP;    // (an empty model, e.g. after pruning everything; `state` is not touched)
+        return MRGS_LAUNCH_STATUS();    // (an empty model, e.g. after pruning everything; `state` is not touched)
     }
     StArgs a;
     std::memset(&a, 0, sizeof(a));
@@ -1717,9 +1718,10 @@ int mrgs_surfel_trace_backward(void* blob, int64_t n_surfels, int64_t n_rays, in
     if ((((uintptr_t)g_geom | (uintptr_t)g_attr) & 15u) == 0) {                                             // one launch, not two memsets
         hipLaunchKernelGGL(st_zero2_kernel, dim3((unsigned)(((size_t)n_surfels * 4 + 255) / 256)), dim3(256), 0, st, reinterpret_cast<float4*>(g_geom),
                            (size_t)n_surfels * 4, reinterpret_cast<float4*>(g_attr), (size_t)n_surfels * 2);
-        if (hipGetLastError() != hipSuccess) return MRGS_E_HIP;
-    } else if (hipMemsetAsync(g_geom, 0, (size_t)n_surfels * 64, st) != hipSuccess || hipMemsetAsync(g_attr, 0, (size_t)n_surfels * 32, st) != hipSuccess) {
-        return MRGS_E_HIP;
+        if (int rc = MRGS_LAUNCH_STATUS()) return rc;
+    } else {
+        MRGS_HIP_TRY(hipMemsetAsync(g_geom, 0, (size_t)n_surfels * 64, st));
+        MRGS_HIP_TRY(hipMemsetAsync(g_attr, 0, (size_t)n_surfels * 32, st));
     }
     if (n_rays == 0) return MRGS_OK;
     if (!blob || !ray_o || !ray_d || !geom || !attr || !bg_host || !rgb || !dpt || !acc || !norm || !aux || !state || !g_ray_o || !g_ray_d)

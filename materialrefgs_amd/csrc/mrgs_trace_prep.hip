@@ -351,7 +351,7 @@ int mrgs_surfel_trace_prep_forward(int64_t P, const float* means3D, const float*
     a.means = means3D; a.scales = scales; a.rotations = rotations; a.opacities = opacities; a.shs = shs; a.colors = colors_precomp; a.others = others;
     a.campos = campos; a.geom = geom; a.attr = attr; a.quads = quad_vertices;
     hipLaunchKernelGGL((trace_prep_kernel<false, false>), dim3((unsigned)((P + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
-    return hipGetLastError() == hipSuccess ? MRGS_OK : MRGS_E_HIP;
+    return MRGS_LAUNCH_STATUS();
 }
 
 int mrgs_surfel_trace_prep_backward(int64_t P, const float* means3D, const float* scales, const float* rotations, const float* shs, int32_t M,
@@ -369,7 +369,7 @@ int mrgs_surfel_trace_prep_backward(int64_t P, const float* means3D, const float
     a.g_geom = g_geom; a.g_attr = g_attr; a.g_means = g_means3D; a.g_scales = g_scales; a.g_rotations = g_rotations; a.g_opacities = g_opacities;
     a.g_shs = g_shs; a.g_colors = g_colors_precomp; a.g_others = g_others;
     hipLaunchKernelGGL((trace_prep_kernel<true, false>), dim3((unsigned)((P + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
-    return hipGetLastError() == hipSuccess ? MRGS_OK : MRGS_E_HIP;
+    return MRGS_LAUNCH_STATUS();
 }
 
 int mrgs_surfel_trace_prep_raw_forward(int64_t P, const float* xyz, const float* scaling_raw, const float* rotation_raw, const float* opacity_raw,
@@ -385,7 +385,7 @@ int mrgs_surfel_trace_prep_raw_forward(int64_t P, const float* xyz, const float*
     a.means = xyz; a.scales = scaling_raw; a.rotations = rotation_raw; a.opacities = opacity_raw; a.shs = features_dc; a.shs_rest = features_rest;
     a.others = others; a.campos = campos; a.geom = geom; a.attr = attr; a.quads = quad_vertices;
     hipLaunchKernelGGL((trace_prep_kernel<false, true>), dim3((unsigned)((P + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
-    return hipGetLastError() == hipSuccess ? MRGS_OK : MRGS_E_HIP;
+    return MRGS_LAUNCH_STATUS();
 }
 
 int mrgs_surfel_trace_prep_raw_backward(int64_t P, const float* xyz, const float* scaling_raw, const float* rotation_raw, const float* opacity_raw,
@@ -406,7 +406,7 @@ int mrgs_surfel_trace_prep_raw_backward(int64_t P, const float* xyz, const float
     a.campos = campos; a.g_geom = g_geom; a.g_attr = g_attr; a.g_means = g_xyz; a.g_scales = g_scaling_raw; a.g_rotations = g_rotation_raw;
     a.g_opacities = g_opacity_raw; a.g_shs = g_features_dc; a.g_shs_rest = g_features_rest; a.g_others = g_others;
     hipLaunchKernelGGL((trace_prep_kernel<true, true>), dim3((unsigned)((P + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
-    return hipGetLastError() == hipSuccess ? MRGS_OK : MRGS_E_HIP;
+    return MRGS_LAUNCH_STATUS();
 }
 
 static void mirror_fill(MirrorArgs& a, int32_t H, int32_t W, const float* Kinv_host, const float* R, const float* T, const MrgsStridedMap* normal)
@@ -425,7 +425,7 @@ int mrgs_traced_blend_forward(int32_t H, int32_t W, const float* a, const float*
     const int HW = H * W;
     hipLaunchKernelGGL(traced_blend_fwd_kernel, dim3((HW + 255) / 256), dim3(256), 0, (hipStream_t)stream, HW, a, b, (long long)b_channel_stride,
                        (long long)b_pixel_stride, s, (long long)s_pixel_stride, out);
-    return hipGetLastError() == hipSuccess ? MRGS_OK : MRGS_E_HIP;
+    return MRGS_LAUNCH_STATUS();
 }
 
 int mrgs_traced_blend_backward(int32_t H, int32_t W, const float* a, const float* b, int64_t b_channel_stride, int64_t b_pixel_stride, const float* s,
@@ -436,7 +436,7 @@ int mrgs_traced_blend_backward(int32_t H, int32_t W, const float* a, const float
     const int HW = H * W;
     hipLaunchKernelGGL(traced_blend_bwd_kernel, dim3((HW + 255) / 256), dim3(256), 0, (hipStream_t)stream, HW, a, b, (long long)b_channel_stride,
                        (long long)b_pixel_stride, s, (long long)s_pixel_stride, g_out, g_a, g_b, g_s);
-    return hipGetLastError() == hipSuccess ? MRGS_OK : MRGS_E_HIP;
+    return MRGS_LAUNCH_STATUS();
 }
 
 int mrgs_mirror_rays_blended_forward(int32_t H, int32_t W, const float* Kinv_host, const float* R, const float* T, const MrgsStridedMap* rend_normal,
@@ -448,7 +448,7 @@ int mrgs_mirror_rays_blended_forward(int32_t H, int32_t W, const float* Kinv_hos
     mirror_fill(a, H, W, Kinv_host, R, T, rend_normal);
     a.alpha = alpha; a.depth = surf_depth; a.ray_o = ray_o; a.ray_d = ray_d;
     hipLaunchKernelGGL(mirror_rays_kernel<false>, dim3((W + 31) / 32, (H + 7) / 8), dim3(256), 0, (hipStream_t)stream, a);
-    return hipGetLastError() == hipSuccess ? MRGS_OK : MRGS_E_HIP;
+    return MRGS_LAUNCH_STATUS();
 }
 
 int mrgs_mirror_rays_blended_backward(int32_t H, int32_t W, const float* Kinv_host, const float* R, const float* T, const MrgsStridedMap* rend_normal,
@@ -463,7 +463,7 @@ int mrgs_mirror_rays_blended_backward(int32_t H, int32_t W, const float* Kinv_ho
     a.alpha = alpha; a.g_alpha = g_alpha;
     a.g_ray_o = g_ray_o; a.g_ray_d = g_ray_d; a.g_normal = g_rend_normal; a.g_depth = g_surf_depth;
     hipLaunchKernelGGL(mirror_rays_kernel<true>, dim3((W + 31) / 32, (H + 7) / 8), dim3(256), 0, (hipStream_t)stream, a);
-    return hipGetLastError() == hipSuccess ? MRGS_OK : MRGS_E_HIP;
+    return MRGS_LAUNCH_STATUS();
 }
 
 int mrgs_mirror_rays_forward(int32_t H, int32_t W, const float* Kinv_host, const float* R, const float* T, const MrgsStridedMap* normal,
@@ -475,7 +475,7 @@ int mrgs_mirror_rays_forward(int32_t H, int32_t W, const float* Kinv_host, const
     mirror_fill(a, H, W, Kinv_host, R, T, normal);
     a.depth = surf_depth; a.ray_o = ray_o; a.ray_d = ray_d;
     hipLaunchKernelGGL(mirror_rays_kernel<false>, dim3((W + 31) / 32, (H + 7) / 8), dim3(256), 0, (hipStream_t)stream, a);
-    return hipGetLastError() == hipSuccess ? MRGS_OK : MRGS_E_HIP;
+    return MRGS_LAUNCH_STATUS();
 }
 
 int mrgs_mirror_rays_backward(int32_t H, int32_t W, const float* Kinv_host, const float* R, const float* T, const MrgsStridedMap* normal,
@@ -487,7 +487,7 @@ int mrgs_mirror_rays_backward(int32_t H, int32_t W, const float* Kinv_host, cons
     mirror_fill(a, H, W, Kinv_host, R, T, normal);
     a.g_ray_o = g_ray_o; a.g_ray_d = g_ray_d; a.g_normal = g_normal; a.g_depth = g_surf_depth;
     hipLaunchKernelGGL(mirror_rays_kernel<true>, dim3((W + 31) / 32, (H + 7) / 8), dim3(256), 0, (hipStream_t)stream, a);
-    return hipGetLastError() == hipSuccess ? MRGS_OK : MRGS_E_HIP;
+    return MRGS_LAUNCH_STATUS();
 }
 
 }   // extern "C"
