@@ -828,6 +828,86 @@ int mrgs_sh_grad_expand_surfel_rows(int32_t P, int32_t D, int32_t V, const float
 size_t mrgs_knn_ws_bytes(int64_t P);
 int mrgs_knn_mean_dist2(const float* points, int64_t P, float* out, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- mesh extraction: TSDF fusion, marching tetrahedra, floater removal -----------------------------------------------------
+ * Replaces the in-loop mesh step of the training scripts (utils/mesh_utils.py: extract_mesh_bounded :212-253, extract_mesh_unbounded
+ * :309-404, post_process_mesh :30-51; utils/mcube_utils.py).  Everything is queued on `stream`; nothing is allocated by the library.
+ *
+ * mrgs_tsdf_fuse: the rule of compute_unbounded_tsdf / compute_sdf_perframe (:322-373).  Per sample x: tsdf = 1, w = 1; for each view
+ * in table order: clip = [x, 1] @ proj (proj row-major [4][4], the camera's full_proj_transform), z = clip.w, ndc = clip.xy / z; the
+ * view contributes iff -1 < ndc.x, ndc.y < 1 and z > 0; d = bilinear tap of the view's depth map [H, W] at ndc (align_corners, border
+ * padding); when depth_trunc > 0 the view is skipped unless all four texels lie in (0, depth_trunc]; sdf = d - z, contributes iff
+ * sdf > -trunc; t = clamp(sdf / trunc, -1, 1); tsdf = (tsdf w + t) / (w + 1); w += 1.  ONE launch per call: the view table is a device
+ * array of any length, the view loop runs inside the kernel, the field is written once, w only to weight_debug when that is given.
+ * Samples: MRGS_TSDF_PLAIN the lattice x = origin + spacing * (i0, i1, i2), field index (i0 n1 + i1) n2 + i2; MRGS_TSDF_CONTRACTED the same
+ * lattice read as contracted coordinates s: x = center + radius * uncontract(s), uncontract(s) = s for |s| < 1, else s / ((2 - |s|) |s|),
+ * and trunc times 1 / (2 - min(|s|, 1.9)) where |s| > 1; MRGS_TSDF_POINTS x = points[n_points, 3] as given.
+ * Codes, before any launch: MRGS_E_BAD_ARG for a wrong struct_size, an unknown mode, a lattice axis below 2, trunc not > 0, radius not
+ * > 0 in contracted mode, n_views < 0, n_points < 0, a NULL field / points / (with n_views > 0) view table; MRGS_E_UNSUPPORTED for 2^39
+ * samples or more (the launch's grid); n_points = 0 returns MRGS_OK and launches nothing.  n_views = 0 is served: the field is all 1. */
+#define MRGS_TSDF_CONTRACTED 0
+#define MRGS_TSDF_PLAIN 1
+#define MRGS_TSDF_POINTS 2
+typedef struct MrgsTsdfView {
+    float proj[16];          /* full_proj_transform, row-major */
+    const float* depth;      /* device fp32 [H, W] */
+    int32_t H, W;
+} MrgsTsdfView;
+typedef struct MrgsTsdfConfig {
+    uint32_t struct_size;    /* = sizeof(MrgsTsdfConfig) */
+    int32_t mode;            /* MRGS_TSDF_* */
+    int32_t n0, n1, n2;      /* lattice points per axis (lattice modes) */
+    int32_t n_views;
+    int64_t n_points;        /* MRGS_TSDF_POINTS */
+    float origin[3], spacing[3];
+    float center[3], radius; /* MRGS_TSDF_CONTRACTED */
+    float trunc;             /* contracted mode: the value inside the unit ball, 5 voxels in the reference */
+    float depth_trunc;       /* > 0: texel validity as above; <= 0: off */
+    const float* points;     /* device fp32 [n_points, 3] */
+} MrgsTsdfConfig;
+int mrgs_tsdf_fuse(const MrgsTsdfConfig* cfg, const MrgsTsdfView* views_dev, float* field, float* weight_debug, void* stream);
+
+/* Marching tetrahedra over the lattice of `field` [n0, n1, n2] (index (i0 n1 + i1) n2 + i2, point origin + spacing * (i0, i1, i2)).
+ * Every cube is cut into the six Kuhn tetrahedra (c, c+e_a, c+e_a+e_b, c+e_a+e_b+e_c); a point is inside iff F < level; a vertex sits on
+ * every lattice edge (3 axes, 3 face diagonals, the body diagonal) whose ends differ, at p_a + (level - F_a) / (F_b - F_a) (p_b - p_a) with
+ * a the end of lower lattice index; triangles are wound so that their normal points from inside to outside.  With `contracted` the
+ * vertices are then mapped by center + radius * uncontract(.) and clipped to +-32 (mcube_utils.py:91-93).  Vertices are indexed by their
+ * owning lattice point, so triangles share indices by construction.
+ * The lattice is worked in slabs of `slab_planes` cube layers along axis 0 (ws, mrgs_mesh_ws_bytes, holds one word per point of a slab).
+ * mrgs_mesh_count writes {V, T} to totals_dev (device int64[2]); the caller reads those 16 bytes, allocates vertices fp32 [V,3] and
+ * triangles int32 [T,3] and calls mrgs_mesh_emit with the same cfg / field / ws.  Vertices are ordered by (lattice index of the owning point, direction
+ * code 4 d0 + 2 d1 + d2 of the edge), whatever the slab height; the order of the triangles is unspecified but the same from call to call.
+ * Codes, before any HIP call: MRGS_E_BAD_ARG for a wrong struct_size, an axis below 2, slab_planes < 1, a spacing not > 0, a NaN level,
+ * radius not > 0 with `contracted`, a NULL field / ws / totals, ws not 8-byte aligned, negative totals, a NULL destination with a
+ * non-zero total; MRGS_E_WORKSPACE for ws_bytes too small; MRGS_E_UNSUPPORTED for a slab of more than 2^28 points or a total beyond
+ * 2^31 - 1.  Zero totals: mrgs_mesh_emit returns MRGS_OK, launches nothing, and the destinations may be NULL. */
+typedef struct MrgsMeshConfig {
+    uint32_t struct_size;    /* = sizeof(MrgsMeshConfig) */
+    int32_t n0, n1, n2;
+    int32_t slab_planes;     /* cube layers per slab, >= 1 */
+    int32_t contracted;
+    float level;
+    float origin[3], spacing[3];
+    float center[3], radius;
+} MrgsMeshConfig;
+size_t mrgs_mesh_ws_bytes(const MrgsMeshConfig* cfg);     /* 0 for a configuration the calls below refuse */
+int mrgs_mesh_count(const MrgsMeshConfig* cfg, const float* field, void* ws, size_t ws_bytes, int64_t* totals_dev, void* stream);
+int mrgs_mesh_emit(const MrgsMeshConfig* cfg, const float* field, void* ws, size_t ws_bytes, const int64_t* totals_host, float* vertices,
+                   int32_t* triangles, void* stream);
+
+/* post_process_mesh (:30-51).  mrgs_mesh_clusters: labels[v] (device int32 [V]) = the smallest vertex index of v's connected component,
+ * components through shared vertex indices; counts[l] (device int32 [V]) = triangles of the component whose label is l, 0 elsewhere.
+ * mrgs_mesh_select: keep_vertex[v] = counts[labels[v]] >= threshold, keep_triangle[t] likewise through its first corner -- the masks
+ * for mrgs_compact_count / mrgs_compact_rows, which keep the survivors' order.  mrgs_mesh_reindex: with new_to_old[V_new] (the old
+ * indices of the surviving vertices, e.g. an index column compacted with them) writes remap_ws[old] = new (device int32 [V_old] scratch)
+ * and rewrites triangles [T,3] in place.  A corner outside [0, V) is ignored by all three.
+ * Codes, before any launch: MRGS_E_BAD_ARG for negative sizes, V_new > V_old, a NULL pointer that would be read or written;
+ * MRGS_E_UNSUPPORTED beyond 2^31 - 1; empty inputs return MRGS_OK and launch nothing. */
+int mrgs_mesh_clusters(int64_t V, int64_t T, const int32_t* triangles, int32_t* labels, int32_t* counts, void* stream);
+int mrgs_mesh_select(int64_t V, int64_t T, const int32_t* triangles, const int32_t* labels, const int32_t* counts, int32_t threshold,
+                     uint8_t* keep_vertex, uint8_t* keep_triangle, void* stream);
+int mrgs_mesh_reindex(int64_t V_old, int64_t V_new, const int32_t* new_to_old, int32_t* remap_ws, int64_t T, int32_t* triangles,
+                      void* stream);
+
 /* Introspection used by the parity tests: copies of internal state in the reference's layouts.
  * which: 0 depths f32[P], 1 means2D f32[P,2], 2 transMat f32[P,9], 3 normal_opacity f32[P,4], 4 rgb f32[P,3],
  * 5 tiles_touched u32[P], 6 clamped u8[P,3], 7 point_list u32[R], 8 ranges u32[tiles,2], 9 final_T f32[3,H,W],

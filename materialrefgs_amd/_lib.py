@@ -132,6 +132,25 @@ class MrgsDensifyTensor(ctypes.Structure):
     _fields_ = [("src", c_void_p), ("dst", c_void_p), ("row_floats", c_int32), ("role", c_int32)]
 
 
+MRGS_TSDF_CONTRACTED, MRGS_TSDF_PLAIN, MRGS_TSDF_POINTS = 0, 1, 2
+
+
+class MrgsTsdfView(ctypes.Structure):
+    _fields_ = [("proj", c_float * 16), ("depth", c_void_p), ("H", c_int32), ("W", c_int32)]
+
+
+class MrgsTsdfConfig(_Sized):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("mode", c_int32), ("n0", c_int32), ("n1", c_int32), ("n2", c_int32), ("n_views", c_int32),
+                ("n_points", c_int64), ("origin", c_float * 3), ("spacing", c_float * 3), ("center", c_float * 3), ("radius", c_float),
+                ("trunc", c_float), ("depth_trunc", c_float), ("points", c_void_p)]
+
+
+class MrgsMeshConfig(_Sized):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("n0", c_int32), ("n1", c_int32), ("n2", c_int32), ("slab_planes", c_int32),
+                ("contracted", c_int32), ("level", c_float), ("origin", c_float * 3), ("spacing", c_float * 3), ("center", c_float * 3),
+                ("radius", c_float)]
+
+
 class MrgsKernelTimes(ctypes.Structure):
     _fields_ = [(n, c_float) for n in ("preprocess_ms", "sort_ms", "duplicate_ms", "render_fwd_ms", "render_bwd_ms",
                                        "preprocess_bwd_ms")]
@@ -247,6 +266,14 @@ SYMBOLS = {
     "mrgs_densify_emit": (ctypes.c_int, [ctypes.POINTER(MrgsDensifyConfig), c_void_p, ctypes.POINTER(c_int64),
                                          ctypes.POINTER(MrgsDensifyTensor), c_int32, ctypes.c_uint64, c_void_p, c_void_p]),
     "mrgs_densify_stats": (ctypes.c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mrgs_tsdf_fuse": (ctypes.c_int, [ctypes.POINTER(MrgsTsdfConfig), c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mrgs_mesh_ws_bytes": (c_size_t, [ctypes.POINTER(MrgsMeshConfig)]),
+    "mrgs_mesh_count": (ctypes.c_int, [ctypes.POINTER(MrgsMeshConfig), c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "mrgs_mesh_emit": (ctypes.c_int, [ctypes.POINTER(MrgsMeshConfig), c_void_p, c_void_p, c_size_t, ctypes.POINTER(c_int64), c_void_p, c_void_p,
+                                      c_void_p]),
+    "mrgs_mesh_clusters": (ctypes.c_int, [c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mrgs_mesh_select": (ctypes.c_int, [c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
+    "mrgs_mesh_reindex": (ctypes.c_int, [c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
     "mrgs_knn_ws_bytes": (c_size_t, [c_int64]),
     "mrgs_knn_mean_dist2": (ctypes.c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
     "mrgs_mark_visible": (ctypes.c_int, [c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -551,6 +551,35 @@ int mrgs_mark_visible(int32_t P, const float* means3D, const float* viewmatrix, 
     return MRGS_LAUNCH_STATUS();
 }
 
+// ---- mesh extraction (kernels, checks and launches: mrgs_mesh.hip) ------------------------------------
+#define MRGS_MESH_ENTRY(call) do { bool launched = false; if (int rc = (call)) return rc; return launched ? MRGS_LAUNCH_STATUS() : MRGS_OK; } while (0)
+int mrgs_tsdf_fuse(const MrgsTsdfConfig* cfg, const MrgsTsdfView* views_dev, float* field, float* weight_debug, void* stream_)
+{
+    MRGS_MESH_ENTRY(mrgs_tsdf_fuse_launch(cfg, views_dev, field, weight_debug, stream_, &launched));
+}
+int mrgs_mesh_count(const MrgsMeshConfig* cfg, const float* field, void* ws, size_t ws_bytes, int64_t* totals_dev, void* stream_)
+{
+    MRGS_MESH_ENTRY(mrgs_mesh_count_launch(cfg, field, ws, ws_bytes, totals_dev, stream_, &launched));
+}
+int mrgs_mesh_emit(const MrgsMeshConfig* cfg, const float* field, void* ws, size_t ws_bytes, const int64_t* totals_host, float* vertices,
+                   int32_t* triangles, void* stream_)
+{
+    MRGS_MESH_ENTRY(mrgs_mesh_emit_launch(cfg, field, ws, ws_bytes, totals_host, vertices, triangles, stream_, &launched));
+}
+int mrgs_mesh_clusters(int64_t V, int64_t T, const int32_t* triangles, int32_t* labels, int32_t* counts, void* stream_)
+{
+    MRGS_MESH_ENTRY(mrgs_mesh_clusters_launch(V, T, triangles, labels, counts, stream_, &launched));
+}
+int mrgs_mesh_select(int64_t V, int64_t T, const int32_t* triangles, const int32_t* labels, const int32_t* counts, int32_t threshold,
+                     uint8_t* keep_vertex, uint8_t* keep_triangle, void* stream_)
+{
+    MRGS_MESH_ENTRY(mrgs_mesh_select_launch(V, T, triangles, labels, counts, threshold, keep_vertex, keep_triangle, stream_, &launched));
+}
+int mrgs_mesh_reindex(int64_t V_old, int64_t V_new, const int32_t* new_to_old, int32_t* remap_ws, int64_t T, int32_t* triangles, void* stream_)
+{
+    MRGS_MESH_ENTRY(mrgs_mesh_reindex_launch(V_old, V_new, new_to_old, remap_ws, T, triangles, stream_, &launched));
+}
+
 // ---- introspection for the parity tests --------------------------------------------------------------
 __global__ void export_rec_kernel(int P, int which, const float4* __restrict__ rec, const uint8_t* __restrict__ clamped, void* dst)
 {

@@ -181,6 +181,17 @@ void mrgs_launch_render_bwd(const MrgsRasterConfig& cfg, const MrgsRasterInputs&
                             const uint8_t* cflag, const MrgsImgWs& img, const float* dL_dpix, const float* dL_dpix_f, const float* dL_dothers,
                             float* grad_rec, bool forward_queues, hipStream_t stream);
 
+// mesh extraction (mrgs_mesh.hip): all argument checks, then the launches; *launched = something was queued (mrgs_api.hip reports its status)
+int mrgs_tsdf_fuse_launch(const MrgsTsdfConfig* cfg, const MrgsTsdfView* views, float* field, float* weight_debug, void* stream, bool* launched);
+int mrgs_mesh_count_launch(const MrgsMeshConfig* cfg, const float* field, void* ws, size_t ws_bytes, int64_t* totals_dev, void* stream, bool* launched);
+int mrgs_mesh_emit_launch(const MrgsMeshConfig* cfg, const float* field, void* ws, size_t ws_bytes, const int64_t* totals_host, float* vertices,
+                          int32_t* triangles, void* stream, bool* launched);
+int mrgs_mesh_clusters_launch(int64_t V, int64_t T, const int32_t* triangles, int32_t* labels, int32_t* counts, void* stream, bool* launched);
+int mrgs_mesh_select_launch(int64_t V, int64_t T, const int32_t* triangles, const int32_t* labels, const int32_t* counts, int32_t threshold,
+                            uint8_t* keep_vertex, uint8_t* keep_triangle, void* stream, bool* launched);
+int mrgs_mesh_reindex_launch(int64_t V_old, int64_t V_new, const int32_t* new_to_old, int32_t* remap_ws, int64_t T, int32_t* triangles,
+                             void* stream, bool* launched);
+
 #ifndef MRGS_EXP
 #define MRGS_EXP(x) expf(x)
 #endif

@@ -93,6 +93,67 @@ def read_ply_vertices(path: str):
     return names, np.array(data, dtype=np.float32)
 
 
+def save_mesh_ply(path: str, mesh_or_vertices, triangles=None):
+    """Triangle mesh as a binary little-endian PLY: `vertex` with float x, y, z and `face` with `list uchar int vertex_indices` -- the layout
+    of o3d.io.write_triangle_mesh for a mesh without colours or normals (train_refnerf.py:1468), read back by load_mesh_ply and by the
+    reference's load_mesh_from_ply.  Takes a mesh (`.vertices`, `.triangles`) or the two arrays."""
+    v, t = (mesh_or_vertices.vertices, mesh_or_vertices.triangles) if triangles is None else (mesh_or_vertices, triangles)
+    v = np.ascontiguousarray(np.asarray(v), dtype="<f4").reshape(-1, 3)
+    t = np.ascontiguousarray(np.asarray(t), dtype="<i4").reshape(-1, 3)
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    header = ["ply", "format binary_little_endian 1.0", f"element vertex {v.shape[0]}", "property float x", "property float y", "property float z",
+              f"element face {t.shape[0]}", "property list uchar int vertex_indices", "end_header"]
+    faces = np.empty(t.shape[0], dtype=[("n", "u1"), ("idx", "<i4", (3,))])
+    faces["n"], faces["idx"] = 3, t
+    with open(path, "wb") as f:
+        f.write(("\n".join(header) + "\n").encode("ascii"))
+        f.write(v.tobytes())
+        f.write(faces.tobytes())
+
+
+def load_mesh_ply(path: str):
+    """(vertices float32 [V,3], triangles int32 [T,3]) of a binary little-endian PLY whose vertex element starts with float x, y, z and
+    whose faces are triangles in a `list uchar int` (or uint) property -- what save_mesh_ply writes."""
+    sizes = {"float": 4, "float32": 4, "double": 8, "float64": 8, "uchar": 1, "uint8": 1, "char": 1, "int8": 1, "short": 2, "int16": 2,
+             "ushort": 2, "uint16": 2, "int": 4, "int32": 4, "uint": 4, "uint32": 4}
+    with open(path, "rb") as f:
+        if f.readline().strip() != b"ply":
+            raise ValueError("not a PLY file")
+        fmt, elements = None, []
+        while True:
+            line = f.readline()
+            if not line:
+                raise ValueError("PLY header not terminated")
+            tok = line.decode("ascii").split()
+            if not tok or tok[0] == "comment":
+                continue
+            if tok[0] == "format":
+                fmt = tok[1]
+            elif tok[0] == "element":
+                elements.append((tok[1], int(tok[2]), []))
+            elif tok[0] == "property":
+                elements[-1][2].append(tok[1:])
+            elif tok[0] == "end_header":
+                break
+        if fmt != "binary_little_endian":
+            raise ValueError(f"unsupported PLY format {fmt}")
+        if [e[0] for e in elements[:2]] != ["vertex", "face"]:
+            raise ValueError("expected the elements vertex and face, in that order")
+        (_, nv, vprops), (_, nf, fprops) = elements[:2]
+        if [p[-1] for p in vprops[:3]] != ["x", "y", "z"] or any(p[0] not in ("float", "float32") for p in vprops[:3]) or \
+                any(p[0] == "list" for p in vprops):
+            raise ValueError("the vertex element must start with float x, y, z and hold no lists")
+        row = sum(sizes[p[0]] for p in vprops)
+        raw = np.frombuffer(f.read(nv * row), dtype=np.uint8).reshape(nv, row)
+        vertices = np.ascontiguousarray(raw[:, :12]).view("<f4").reshape(nv, 3).astype(np.float32)
+        if len(fprops) != 1 or fprops[0][0] != "list" or sizes.get(fprops[0][1]) != 1 or fprops[0][2] not in ("int", "int32", "uint", "uint32"):
+            raise ValueError("the face element must be one `list uchar int` property")
+        faces = np.frombuffer(f.read(nf * 13), dtype=[("n", "u1"), ("idx", "<i4", (3,))])
+        if len(faces) != nf or (faces["n"] != 3).any():
+            raise ValueError("only triangle faces are read")
+    return vertices, np.ascontiguousarray(faces["idx"], dtype=np.int32)
+
+
 def load_ply(path: str, max_sh_degree: int = 3, device="cpu") -> Dict[str, torch.Tensor]:
     """load_ply (:725-838): returns the tensors in the GaussianModel layout (see save_ply)."""
     names, data = read_ply_vertices(path)

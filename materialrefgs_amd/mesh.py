@@ -1,0 +1,323 @@
+"""Mesh extraction inside the training loop: the reference's `GaussianExtractor` and `post_process_mesh` (utils/mesh_utils.py:30-51,
+81-404) on the device.  Every `MESH_EXTRACT_INTERVAL` iterations the training scripts render all training cameras, fuse the depth maps
+into a truncated signed distance field, extract a triangle mesh, drop floaters and hand the mesh to `GaussianModel.update_mesh`
+(train_refnerf.py:1459-1472).  The reference does this with Open3D, skimage and trimesh on host copies of every map; here the depth
+maps stay where the renderer wrote them and fusion, extraction and clustering are kernels of libmrgs.so (csrc/mrgs_mesh.hip) on
+torch's current stream.  No CPU path: host tensors raise.
+
+Differences from the reference, all stated in INTEGRATION.md section 4c: the surface is marching tetrahedra (six Kuhn tetrahedra per
+cube), not Lewiner marching cubes; `extract_mesh_bounded` fuses on a plain lattice by this repository's rule (Open3D's is not part of
+the reference tree: parity unpinned); clusters are connected through shared vertices; `cluster_to_keep` is clamped to the number of
+clusters; no vertex colours; `extract_mesh_unbounded` works on one lattice of any resolution."""
+import ctypes
+from functools import partial
+
+import numpy as np
+import torch
+
+from . import _lib
+from .densify import compact_rows
+
+_MAX_LATTICE_POINTS = 2 ** 31 - 1
+_SLAB_POINTS = 1 << 24              # lattice points whose mask / base words the extraction keeps at a time (64 MiB)
+
+
+class TriangleMesh:
+    """`vertices_device` [V,3] fp32 and `triangles_device` [T,3] int32; `.vertices` / `.triangles` are host numpy arrays, copied once
+    and kept (`np.asarray(mesh.vertices)` of GaussianModel.update_mesh works unchanged; the BVH build is a host step)."""
+
+    def __init__(self, vertices_device, triangles_device):
+        self.vertices_device = vertices_device
+        self.triangles_device = triangles_device
+        self._vertices = self._triangles = None
+
+    @property
+    def vertices(self):
+        if self._vertices is None:
+            self._vertices = self.vertices_device.detach().cpu().numpy()
+        return self._vertices
+
+    @property
+    def triangles(self):
+        if self._triangles is None:
+            self._triangles = self.triangles_device.detach().cpu().numpy()
+        return self._triangles
+
+    def __repr__(self):
+        return f"TriangleMesh({self.vertices_device.shape[0]} vertices, {self.triangles_device.shape[0]} triangles)"
+
+
+def _need_device(t, what):
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise RuntimeError(f"materialrefgs_amd.mesh: {what} must be a device tensor (libmrgs.so has no CPU path)")
+
+
+def _vec3(v, what):
+    a = np.asarray(v.detach().cpu().numpy() if torch.is_tensor(v) else v, dtype=np.float32).reshape(-1)
+    if a.size == 1:
+        a = np.repeat(a, 3)
+    if a.size != 3:
+        raise ValueError(f"{what} must have one or three values")
+    return (ctypes.c_float * 3)(*[float(x) for x in a])
+
+
+def _view_table(views, dev):
+    """Device array of MrgsTsdfView, one per (full_proj_transform [4,4], depth [H,W] or [1,H,W]); the depth tensors are returned too so
+    that they outlive the launch."""
+    n = len(views)
+    depths = []
+    for proj, depth in views:
+        _need_device(depth, "a depth map")
+        _need_device(proj, "a projection matrix")
+        if depth.dtype != torch.float32:
+            raise TypeError(f"depth maps must be float32, got {depth.dtype}")
+        if depth.dim() == 3 and depth.shape[0] == 1:
+            depth = depth[0]
+        if depth.dim() != 2 or depth.device != dev or tuple(proj.shape) != (4, 4):
+            raise ValueError("a view is (full_proj_transform [4,4], depth [H,W] or [1,H,W]) on the device of the field")
+        depths.append(depth.detach().contiguous())
+    table = (_lib.MrgsTsdfView * max(n, 1))()
+    if n:
+        projs = torch.stack([p.detach().to(torch.float32) for p, _ in views]).cpu().numpy().reshape(n, 16)      # the call's one host read
+        for i, d in enumerate(depths):
+            table[i].proj[:] = projs[i].tolist()
+            table[i].depth = d.data_ptr()
+            table[i].H, table[i].W = int(d.shape[0]), int(d.shape[1])
+    host = torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8)
+    return host.to(dev), depths
+
+
+def tsdf_fuse(views, trunc, *, shape=None, origin=None, spacing=None, contraction=None, points=None, depth_trunc=0.0, return_weight=False,
+              device=None):
+    """Fuse depth maps into a truncated signed distance field by the rule of compute_unbounded_tsdf (utils/mesh_utils.py:322-373; the
+    contract is written out at mrgs_tsdf_fuse in include/mrgs.h).
+
+    views: sequence of (full_proj_transform [4,4], depth [H,W] or [1,H,W]) device tensors, visited in order; sizes may differ.
+    Samples: `points` [n,3] as given, or the lattice origin + spacing * (i,j,k) of `shape`; with contraction=(center, radius) that lattice
+    is read as contracted coordinates and `trunc` is the value inside the unit ball.  depth_trunc > 0 switches on the bounded mode's
+    texel validity.  Returns the field ([n] or `shape`), with return_weight also the update count + 1."""
+    lib = _lib.lib()
+    cfg = _lib.MrgsTsdfConfig()
+    if points is not None:
+        _need_device(points, "points")
+        if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 3:
+            raise TypeError("points must be float32 [n,3]")
+        points = points.detach().contiguous()
+        dev = points.device
+        cfg.mode, cfg.n_points, cfg.points = _lib.MRGS_TSDF_POINTS, points.shape[0], points.data_ptr()
+        out_shape = (points.shape[0],)
+    else:
+        if shape is None or origin is None or spacing is None:
+            raise ValueError("tsdf_fuse needs `points` or a lattice (shape, origin, spacing)")
+        n0, n1, n2 = (int(s) for s in shape)
+        if n0 * n1 * n2 > _MAX_LATTICE_POINTS:
+            raise ValueError(f"a lattice of {n0} x {n1} x {n2} points exceeds 2^31 - 1")
+        dev = torch.device(device) if device is not None else (views[0][1].device if len(views) else torch.device("cuda"))
+        if dev.type != "cuda":
+            raise RuntimeError("materialrefgs_amd.mesh: the field lives on a GPU (libmrgs.so has no CPU path)")
+        if dev.index is None:                                        # "cuda": the current device, named like the tensors on it
+            dev = torch.device("cuda", torch.cuda.current_device())
+        cfg.mode = _lib.MRGS_TSDF_PLAIN if contraction is None else _lib.MRGS_TSDF_CONTRACTED
+        cfg.n0, cfg.n1, cfg.n2 = n0, n1, n2
+        cfg.origin, cfg.spacing = _vec3(origin, "origin"), _vec3(spacing, "spacing")
+        if contraction is not None:
+            cfg.center, cfg.radius = _vec3(contraction[0], "center"), float(contraction[1])
+        out_shape = (n0, n1, n2)
+    cfg.n_views, cfg.trunc, cfg.depth_trunc = len(views), float(trunc), float(depth_trunc)
+    table, keep = _view_table(views, dev)
+    field = torch.empty(out_shape, dtype=torch.float32, device=dev)
+    weight = torch.empty(out_shape, dtype=torch.float32, device=dev) if return_weight else None
+    with _lib.guard(dev):
+        _lib.check(lib.mrgs_tsdf_fuse(ctypes.byref(cfg), _lib.ptr(table) if len(views) else None, _lib.ptr(field) or None, _lib.ptr(weight),
+                                      _lib.stream_ptr(dev)))
+    del keep
+    return (field, weight) if return_weight else field
+
+
+def marching_tetrahedra(field, level, origin, spacing, *, contraction=None, slab_planes=None):
+    """Triangle mesh of the surface F = level of `field` [n0,n1,n2] (device fp32) on the lattice origin + spacing * (i,j,k): marching
+    tetrahedra, indexed vertices without a sort (mrgs_mesh_count / mrgs_mesh_emit, include/mrgs.h).  Triangles are wound so that the
+    normal points towards growing F.  contraction=(center, radius): the lattice is in contracted coordinates; vertices are formed there,
+    then mapped by center + radius * uncontract(.) and clipped to +-32.  slab_planes: cube layers along axis 0 worked at a time."""
+    _need_device(field, "the field")
+    if field.dtype != torch.float32 or field.dim() != 3:
+        raise TypeError("the field must be float32 [n0,n1,n2]")
+    field = field.detach().contiguous()
+    dev = field.device
+    n0, n1, n2 = field.shape
+    if slab_planes is None:
+        slab_planes = max(1, min(n0 - 1, _SLAB_POINTS // max(n1 * n2, 1) - 1))
+    cfg = _lib.MrgsMeshConfig(n0, n1, n2, int(slab_planes), 0 if contraction is None else 1, float(level), _vec3(origin, "origin"),
+                              _vec3(spacing, "spacing"))
+    if contraction is not None:
+        cfg.center, cfg.radius = _vec3(contraction[0], "center"), float(contraction[1])
+    lib = _lib.lib()
+    with _lib.guard(dev):
+        st = _lib.stream_ptr(dev)
+        ws = torch.empty(max(lib.mrgs_mesh_ws_bytes(ctypes.byref(cfg)), 8), dtype=torch.uint8, device=dev)
+        totals = torch.empty(2, dtype=torch.int64, device=dev)
+        _lib.check(lib.mrgs_mesh_count(ctypes.byref(cfg), _lib.ptr(field), _lib.ptr(ws), ws.numel(), _lib.ptr(totals), st))
+        V, T = (int(x) for x in totals.tolist())                  # the one host read: 16 bytes
+        vertices = torch.empty((V, 3), dtype=torch.float32, device=dev)
+        triangles = torch.empty((T, 3), dtype=torch.int32, device=dev)
+        host_totals = (ctypes.c_int64 * 2)(V, T)
+        _lib.check(lib.mrgs_mesh_emit(ctypes.byref(cfg), _lib.ptr(field), _lib.ptr(ws), ws.numel(), host_totals, _lib.ptr(vertices) or None,
+                                      _lib.ptr(triangles) or None, st))
+    return TriangleMesh(vertices, triangles)
+
+
+def _as_mesh(mesh):
+    v, t = mesh.vertices_device, mesh.triangles_device
+    _need_device(v, "mesh vertices")
+    _need_device(t, "mesh triangles")
+    if v.dtype != torch.float32 or t.dtype != torch.int32:
+        raise TypeError("a mesh is float32 vertices [V,3] and int32 triangles [T,3]")
+    return v.contiguous(), t.contiguous()
+
+
+def cluster_triangles(mesh):
+    """(labels [V] int32, counts [V] int32) on the device: labels[v] is the smallest vertex index of v's connected component (through
+    shared vertex indices), counts[l] the triangles of the component labelled l and 0 elsewhere."""
+    v, t = _as_mesh(mesh)
+    dev = v.device
+    labels = torch.empty(v.shape[0], dtype=torch.int32, device=dev)
+    counts = torch.empty(v.shape[0], dtype=torch.int32, device=dev)
+    with _lib.guard(dev):
+        _lib.check(_lib.lib().mrgs_mesh_clusters(v.shape[0], t.shape[0], _lib.ptr(t) or None, _lib.ptr(labels) or None, _lib.ptr(counts) or None,
+                                                 _lib.stream_ptr(dev)))
+    return labels, counts
+
+
+def post_process_mesh(mesh, cluster_to_keep=1000):
+    """post_process_mesh (utils/mesh_utils.py:30-51): keep the triangles of clusters with at least max(n, 50) triangles, n the
+    cluster_to_keep-th largest cluster size, then drop unreferenced vertices; survivors keep their order.  cluster_to_keep beyond the
+    number of clusters is clamped to it (the reference raises IndexError there).  The result may be empty: when the largest cluster has
+    fewer than 50 triangles everything goes."""
+    if cluster_to_keep < 1:
+        raise ValueError("cluster_to_keep must be at least 1")
+    v, t = _as_mesh(mesh)
+    dev = v.device
+    V, T = v.shape[0], t.shape[0]
+    if V == 0 or T == 0:
+        return TriangleMesh(v[:0].clone(), t[:0].clone())
+    labels, counts = cluster_triangles(mesh)
+    sizes = counts.cpu().numpy()                                     # the k-th largest cluster is picked on the host (every 2000 iterations)
+    sizes = np.sort(sizes[sizes > 0])
+    threshold = max(int(sizes[-min(int(cluster_to_keep), len(sizes))]), 50)
+    keep_v = torch.empty(V, dtype=torch.uint8, device=dev)
+    keep_t = torch.empty(T, dtype=torch.uint8, device=dev)
+    lib = _lib.lib()
+    with _lib.guard(dev):
+        st = _lib.stream_ptr(dev)
+        _lib.check(lib.mrgs_mesh_select(V, T, _lib.ptr(t), _lib.ptr(labels), _lib.ptr(counts), threshold, _lib.ptr(keep_v), _lib.ptr(keep_t), st))
+        (new_v, new_to_old), n_v = compact_rows([v, torch.arange(V, dtype=torch.int32, device=dev)], keep_v)
+        (new_t,), n_t = compact_rows([t], keep_t)
+        if n_t > 0:
+            remap = torch.empty(V, dtype=torch.int32, device=dev)
+            _lib.check(lib.mrgs_mesh_reindex(V, n_v, _lib.ptr(new_to_old), _lib.ptr(remap), n_t, _lib.ptr(new_t), st))
+    return TriangleMesh(new_v, new_t)
+
+
+def bounding_sphere(viewpoint_stack):
+    """(center [3] float64, radius) of GaussianExtractor.estimate_bounding_sphere (:197-209): the point nearest to all optical axes
+    (focus_point_fn, utils/render_utils.py:68-74) and the distance of the closest camera to it."""
+    c2ws = np.array([np.linalg.inv(np.asarray(cam.world_view_transform.T.detach().cpu().numpy(), dtype=np.float64)) for cam in viewpoint_stack])
+    poses = c2ws[:, :3, :] @ np.diag([1.0, -1.0, -1.0, 1.0])
+    directions, origins = poses[:, :3, 2:3], poses[:, :3, 3:4]
+    m = np.eye(3) - directions * np.transpose(directions, [0, 2, 1])
+    mt_m = np.transpose(m, [0, 2, 1]) @ m
+    center = np.linalg.inv(mt_m.mean(0)) @ (mt_m @ origins).mean(0)[:, 0]
+    radius = np.linalg.norm(c2ws[:, :3, 3] - center, axis=-1).min()
+    return center, float(radius)
+
+
+def _contract(x):
+    mag = torch.linalg.norm(x, dim=-1, keepdim=True)
+    return torch.where(mag < 1, x, (2 - 1 / mag) * (x / mag))
+
+
+class GaussianExtractor:
+    """GaussianExtractor(gaussians, render, pipe, bg_color=None) of utils/mesh_utils.py:81-404 for the training loop: `reconstruction`
+    renders the cameras and keeps `surf_depth` per view on the device (no rgb, normal or host copies), `extract_mesh_bounded` /
+    `extract_mesh_unbounded` return a TriangleMesh."""
+
+    def __init__(self, gaussians, render, pipe, bg_color=None, device="cuda"):
+        self.device = torch.device(device)
+        self.gaussians = gaussians
+        self._render, self._pipe = render, pipe
+        self._bg_color = [0, 0, 0] if bg_color is None else bg_color
+        self.render = None
+        self.clean()
+
+    @torch.no_grad()
+    def clean(self):
+        self.depthmaps = []
+        self.viewpoint_stack = []
+        self.last_lattice = None
+
+    @torch.no_grad()
+    def reconstruction(self, viewpoint_stack, opt=None):
+        self.clean()
+        self.viewpoint_stack = viewpoint_stack
+        if self.render is None:
+            background = torch.tensor(self._bg_color, dtype=torch.float32, device=self.device)
+            self.render = partial(self._render, pipe=self._pipe, bg_color=background)
+        for cam in self.viewpoint_stack:
+            pkg = self.render(cam, self.gaussians, opt=opt)
+            depth = pkg["surf_depth"]
+            _need_device(depth, "render_pkg['surf_depth']")
+            mask = getattr(cam, "gt_alpha_mask", None)
+            if mask is not None:
+                mask = mask.to(depth.device)
+                depth = depth * mask + (1 - mask) * 10                   # :147
+            self.depthmaps.append(depth.detach())
+        self.estimate_bounding_sphere()
+
+    def estimate_bounding_sphere(self):
+        self.center_host, self.radius = bounding_sphere(self.viewpoint_stack)
+        self.center = torch.from_numpy(self.center_host).float().to(self.device)
+        print(f"The estimated bounding radius is {self.radius:.2f}")
+        print(f"Use at least {2.0 * self.radius:.2f} for depth_trunc")
+
+    def _views(self, depthmaps):
+        return [(cam.full_proj_transform, d) for cam, d in zip(self.viewpoint_stack, depthmaps)]
+
+    @torch.no_grad()
+    def extract_mesh_bounded(self, voxel_size=0.004, sdf_trunc=0.02, depth_trunc=3, mask_backgrond=True):
+        """TSDF fusion on the plain lattice of spacing voxel_size that fills the cube of side depth_trunc around the estimated centre.
+        Texels that are 0 (masked background, :239-240) or beyond depth_trunc invalidate a tap, as the reference's call into Open3D
+        discards such depths."""
+        n = int(np.ceil(float(depth_trunc) / float(voxel_size))) + 1
+        if n < 2 or n ** 3 > _MAX_LATTICE_POINTS:
+            raise ValueError(f"extract_mesh_bounded: depth_trunc / voxel_size gives a lattice of {n}^3 points (2 .. 2^31 - 1 points are served)")
+        depthmaps = []
+        for cam, depth in zip(self.viewpoint_stack, self.depthmaps):
+            mask = getattr(cam, "gt_alpha_mask", None)
+            if mask_backgrond and mask is not None:
+                depth = torch.where(mask.to(depth.device) < 0.5, torch.zeros_like(depth), depth)
+            depthmaps.append(depth)
+        origin = (self.center_host - 0.5 * float(depth_trunc)).astype(np.float32)
+        # what the kernels were given, in fp32 as they see it
+        self.last_lattice = dict(shape=(n, n, n), origin=origin, spacing=np.float32(voxel_size), trunc=np.float32(sdf_trunc),
+                                 depth_trunc=np.float32(depth_trunc), contraction=None)
+        field = tsdf_fuse(self._views(depthmaps), sdf_trunc, shape=(n, n, n), origin=origin, spacing=voxel_size, depth_trunc=depth_trunc,
+                          device=self.device)
+        return marching_tetrahedra(field, 0.0, origin, voxel_size)
+
+    @torch.no_grad()
+    def extract_mesh_unbounded(self, resolution=1024):
+        """:309-404 on one lattice of resolution^3 points in contracted space (the reference's `resolution % 512 == 0` belongs to its
+        512^3 crops).  No vertex colours."""
+        N = int(resolution)
+        if N < 2 or N ** 3 > _MAX_LATTICE_POINTS:
+            raise ValueError(f"extract_mesh_unbounded: a lattice of {N}^3 points is not served (2 .. 2^31 - 1 points)")
+        voxel_size = self.radius * 2 / N
+        xyz = self.gaussians.get_xyz.detach()
+        norms = _contract((xyz - self.center.to(xyz.device)) / self.radius).norm(dim=-1).cpu().numpy()
+        R = min(float(np.quantile(norms, q=0.95)) + 0.01, 1.9)                # :385-387
+        contraction = (self.center_host.astype(np.float32), np.float32(self.radius))
+        self.last_lattice = dict(shape=(N, N, N), origin=np.float32(-R), spacing=np.float32(2.0 * R / (N - 1)), trunc=np.float32(5 * voxel_size),
+                                 depth_trunc=None, contraction=contraction)
+        field = tsdf_fuse(self._views(self.depthmaps), 5 * voxel_size, shape=(N, N, N), origin=-R, spacing=2.0 * R / (N - 1), contraction=contraction,
+                          device=self.device)
+        return marching_tetrahedra(field, 0.0, -R, 2.0 * R / (N - 1), contraction=contraction)

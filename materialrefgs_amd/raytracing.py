@@ -20,7 +20,9 @@ class RayTracer:
             triangles = triangles.detach().cpu().numpy()
         vertices = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 3)
         triangles = np.ascontiguousarray(triangles, dtype=np.int32).reshape(-1, 3)
-        assert triangles.shape[0] > 8, "BVH needs at least 8 triangles."          # raytracer.py:15
+        if not triangles.shape[0] > 8:                                            # raytracer.py:15
+            raise AssertionError(f"RayTracer needs more than 8 triangles for its BVH, got {triangles.shape[0]}: post_process_mesh removes every "
+                                 "cluster of fewer than 50 triangles, so an extraction whose largest cluster is smaller leaves an empty mesh")
         self.n_triangles = int(triangles.shape[0])
         lib = _lib.lib()
         nbytes = lib.mrgs_bvh_bytes(self.n_triangles)
