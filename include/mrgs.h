@@ -498,6 +498,41 @@ int mrgs_loss_backward(const MrgsLossConfig* cfg, const float* image, const floa
                        const float* image_weight, const void* ws, const float* g_loss, float* g_image, float* g_rend_normal,
                        float* g_surf_normal, float* g_rend_dist, void* stream);
 
+/* ---- per-pixel prior terms of one view (fused) ---------------------------------------------------------------------------------
+ * The terms the training scripts add to the loss outside calculate_loss, in three groups; a group is on when its pointers are given
+ * and off when they are all NULL (a group with only some of them is MRGS_E_BAD_ARG).  N = H W pixels, all maps contiguous fp32.
+ *   normal prior (mono_normal_loss, train_refnerf.py:202-251): surf_normal / rend_normal [3,H,W], prior [N,3] (the monocular normal,
+ *     camera space), mask [N] or NULL, Rt[9] HOST floats = the camera's R transposed, row-major (v = Rt x).  With a = normalize(v),
+ *     b = normalize(prior), normalize(x) = x / max(|x|, 1e-12): l1 = sum m sum_c |a_c - b_c| / sum m, cos = sum m (1 - a.b) / sum m
+ *     (m = 1 without a mask).  Where |v| < 1e-12 the clamp is active: the gradient is g / 1e-12 with no projection term.
+ *   mask entropy (train_refnerf.py:1213-1215): rend_alpha [N], alpha_mask [N]; o = clamp(alpha, 1e-6f, (float)(1 - 1e-6)),
+ *     -mean(m log o + (1 - m) log(1 - o)); the gradient passes where lo <= alpha <= hi.  alpha_mask may be the same pointer as mask.
+ *   ref score (train_refreal.py:1238-1258): refl / rough [N], ref_score [N] uint8 (S = nonzero): a1 = mean_S |refl - 0.9|,
+ *     a2 = mean_S |rough - 0.05|, b1 = mean_notS |refl - 0.05|, b2 = mean_notS |0.9 - rough|.
+ * out_terms[16] (device): [0..3] l1 and cos of surf_normal, then of rend_normal; [4] entropy; [5..8] a1, a2, b1, b2; [9] sum m;
+ * [10] |S|; [11] |not S|; [12] a1 + a2 + b1 + b2 / 2; the rest and the terms of a group that is off are 0.  Divisions are IEEE: an
+ * all-zero mask or an empty set gives NaN, as the reference does.  Sums are reduced in a fixed order (no atomics): both calls are
+ * bitwise repeatable.  Forward: two launches; backward: one.  No host synchronisation in either call.
+ * Backward: fwd_terms = the forward's out_terms (the denominators are read from it on the device); g_terms = HOST table of 16 device
+ * scalars, the upstream gradients of out_terms[0..8] and [12] (NULL = 0; the other slots are not read).  Every non-NULL gradient map
+ * is written in full (g_surf_normal / g_rend_normal [3,H,W], g_alpha / g_refl / g_rough [N]); a map whose group has no upstream
+ * gradient is written as zeros without reading the group's inputs.  Nothing reaches the prior, the masks or ref_score.
+ * MRGS_E_BAD_ARG before anything is read: wrong struct_size, H or W <= 0, flags != 0, no group at all, a partial group, a mask
+ * without the normal group, a missing or misaligned (16 bytes) or too small workspace, a gradient map of a group that is off. */
+typedef struct MrgsPriorConfig {
+    uint32_t struct_size;           /* = sizeof(MrgsPriorConfig) */
+    int32_t H, W;
+    uint32_t flags;                 /* reserved: 0 */
+} MrgsPriorConfig;
+size_t mrgs_prior_ws_bytes(int32_t H, int32_t W);
+int mrgs_prior_terms_forward(const MrgsPriorConfig* cfg, const float* Rt, const float* surf_normal, const float* rend_normal,
+                             const float* prior, const float* mask, const float* rend_alpha, const float* alpha_mask, const float* refl,
+                             const float* rough, const uint8_t* ref_score, void* ws, size_t ws_bytes, float* out_terms, void* stream);
+int mrgs_prior_terms_backward(const MrgsPriorConfig* cfg, const float* Rt, const float* surf_normal, const float* rend_normal,
+                              const float* prior, const float* mask, const float* rend_alpha, const float* alpha_mask, const float* refl,
+                              const float* rough, const uint8_t* ref_score, const float* fwd_terms, const float* const* g_terms,
+                              float* g_surf_normal, float* g_rend_normal, float* g_alpha, float* g_refl, float* g_rough, void* stream);
+
 /* ---- multi-view material consistency loss (calc_warp_loss, train_refnerf.py:414-739, train_refreal.py:405-729) ------------------
  * View v and neighbour n, both H x W.  Geometry: every pixel p of v is back-projected through depth_v, projected into n, looked up in
  * depth_n (bilinear, border, align_corners), back-projected and re-projected into v; e = |p' - p|.  valid = inside n (strict bounds,

@@ -95,6 +95,10 @@ class MrgsLossConfig(ctypes.Structure):
                 ("lambda_dist", c_float)]
 
 
+class MrgsPriorConfig(_Sized):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("H", c_int32), ("W", c_int32), ("flags", ctypes.c_uint32)]
+
+
 MRGS_WARP_GEO, MRGS_WARP_MATERIAL, MRGS_WARP_METALLIC, MRGS_WARP_ROUGHNESS = 1, 2, 4, 8
 
 
@@ -207,6 +211,11 @@ SYMBOLS = {
                                          c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
     "mrgs_loss_backward": (ctypes.c_int, [ctypes.POINTER(MrgsLossConfig), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mrgs_prior_ws_bytes": (c_size_t, [c_int32, c_int32]),
+    "mrgs_prior_terms_forward": (ctypes.c_int, [ctypes.POINTER(MrgsPriorConfig), ctypes.POINTER(c_float)] + [c_void_p] * 10 + [c_size_t, c_void_p,
+                                                                                                                          c_void_p]),
+    "mrgs_prior_terms_backward": (ctypes.c_int, [ctypes.POINTER(MrgsPriorConfig), ctypes.POINTER(c_float)] + [c_void_p] * 10 +
+                                  [ctypes.POINTER(c_void_p)] + [c_void_p] * 6),
     "mrgs_warp_loss_ws_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32]),
     "mrgs_warp_loss_forward": (ctypes.c_int, [ctypes.POINTER(MrgsWarpConfig), ctypes.POINTER(MrgsWarpMaps), c_void_p, c_void_p, c_size_t,
                                               c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -552,6 +552,7 @@ int mrgs_mark_visible(int32_t P, const float* means3D, const float* viewmatrix, 
 }
 
 // ---- mesh extraction (kernels, checks and launches: mrgs_mesh.hip) ------------------------------------
+// (also the form of the prior terms' entry points below)
 #define MRGS_MESH_ENTRY(call) do { bool launched = false; if (int rc = (call)) return rc; return launched ? MRGS_LAUNCH_STATUS() : MRGS_OK; } while (0)
 int mrgs_tsdf_fuse(const MrgsTsdfConfig* cfg, const MrgsTsdfView* views_dev, float* field, float* weight_debug, void* stream_)
 {
@@ -578,6 +579,23 @@ int mrgs_mesh_select(int64_t V, int64_t T, const int32_t* triangles, const int32
 int mrgs_mesh_reindex(int64_t V_old, int64_t V_new, const int32_t* new_to_old, int32_t* remap_ws, int64_t T, int32_t* triangles, void* stream_)
 {
     MRGS_MESH_ENTRY(mrgs_mesh_reindex_launch(V_old, V_new, new_to_old, remap_ws, T, triangles, stream_, &launched));
+}
+
+// ---- per-pixel prior terms (kernels, checks and launches: mrgs_prior.hip) ------------------------------
+int mrgs_prior_terms_forward(const MrgsPriorConfig* cfg, const float* Rt, const float* surf_normal, const float* rend_normal, const float* prior,
+                             const float* mask, const float* rend_alpha, const float* alpha_mask, const float* refl, const float* rough,
+                             const uint8_t* ref_score, void* ws, size_t ws_bytes, float* out_terms, void* stream_)
+{
+    MRGS_MESH_ENTRY(mrgs_prior_forward_launch(cfg, Rt, surf_normal, rend_normal, prior, mask, rend_alpha, alpha_mask, refl, rough, ref_score, ws,
+                                              ws_bytes, out_terms, stream_, &launched));
+}
+int mrgs_prior_terms_backward(const MrgsPriorConfig* cfg, const float* Rt, const float* surf_normal, const float* rend_normal, const float* prior,
+                              const float* mask, const float* rend_alpha, const float* alpha_mask, const float* refl, const float* rough,
+                              const uint8_t* ref_score, const float* fwd_terms, const float* const* g_terms, float* g_surf_normal,
+                              float* g_rend_normal, float* g_alpha, float* g_refl, float* g_rough, void* stream_)
+{
+    MRGS_MESH_ENTRY(mrgs_prior_backward_launch(cfg, Rt, surf_normal, rend_normal, prior, mask, rend_alpha, alpha_mask, refl, rough, ref_score,
+                                               fwd_terms, g_terms, g_surf_normal, g_rend_normal, g_alpha, g_refl, g_rough, stream_, &launched));
 }
 
 // ---- introspection for the parity tests --------------------------------------------------------------

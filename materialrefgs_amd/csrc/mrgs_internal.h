@@ -192,6 +192,15 @@ int mrgs_mesh_select_launch(int64_t V, int64_t T, const int32_t* triangles, cons
 int mrgs_mesh_reindex_launch(int64_t V_old, int64_t V_new, const int32_t* new_to_old, int32_t* remap_ws, int64_t T, int32_t* triangles,
                              void* stream, bool* launched);
 
+// per-pixel prior terms (mrgs_prior.hip): the same split
+int mrgs_prior_forward_launch(const MrgsPriorConfig* cfg, const float* Rt, const float* surf_normal, const float* rend_normal, const float* prior,
+                              const float* mask, const float* rend_alpha, const float* alpha_mask, const float* refl, const float* rough,
+                              const uint8_t* ref_score, void* ws, size_t ws_bytes, float* out_terms, void* stream, bool* launched);
+int mrgs_prior_backward_launch(const MrgsPriorConfig* cfg, const float* Rt, const float* surf_normal, const float* rend_normal, const float* prior,
+                               const float* mask, const float* rend_alpha, const float* alpha_mask, const float* refl, const float* rough,
+                               const uint8_t* ref_score, const float* fwd_terms, const float* const* g_terms, float* g_surf_normal,
+                               float* g_rend_normal, float* g_alpha, float* g_refl, float* g_rough, void* stream, bool* launched);
+
 #ifndef MRGS_EXP
 #define MRGS_EXP(x) expf(x)
 #endif

@@ -17,6 +17,7 @@ import math
 import os
 from types import SimpleNamespace
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -761,16 +762,32 @@ class _MirrorRaysBlended(torch.autograd.Function):
 _CAM_CONSTS = Bounded(4096)
 
 
-def _camera_consts(viewpoint_camera, dev):
-    """K^-1 (host tuple), Camera.R and Camera.T as device tensors, built once per camera object AND pose: an entry is only reused while
-    R, T and the intrinsics are what it was built from (a pose refinement or new intrinsics on the same object rebuild it)."""
+def _camera_entry(viewpoint_camera, dev):
     K = viewpoint_camera.HWK[2]
 
     def build():
         R = torch.as_tensor(viewpoint_camera.R, dtype=torch.float32, device=dev).contiguous()
         T = torch.as_tensor(viewpoint_camera.T, dtype=torch.float32, device=dev).contiguous()
-        return viewpoint_camera, _kinv_tuple(K), R, T       # holds the camera: its id stays its own
-    return derived(_CAM_CONSTS, (id(viewpoint_camera), dev), (viewpoint_camera.R, viewpoint_camera.T, K), build)[1:]
+        return viewpoint_camera, _kinv_tuple(K), R, T, []   # holds the camera: its id stays its own; [] is filled by _camera_rt_host
+    return derived(_CAM_CONSTS, (id(viewpoint_camera), dev), (viewpoint_camera.R, viewpoint_camera.T, K), build)
+
+
+def _camera_consts(viewpoint_camera, dev):
+    """K^-1 (host tuple), Camera.R and Camera.T as device tensors, built once per camera object AND pose: an entry is only reused while
+    R, T and the intrinsics are what it was built from (a pose refinement or new intrinsics on the same object rebuild it)."""
+    return _camera_entry(viewpoint_camera, dev)[1:4]
+
+
+def _camera_rt_host(viewpoint_camera, dev):
+    """Camera.R transposed as nine host floats (row-major, float32 values), kept in the camera's `_camera_consts` entry: the world-to-
+    camera rotation of the normal prior (priors.py).  Filled at the first request; an R held on the device costs one host read then,
+    none afterwards, a numpy or CPU R none at all."""
+    slot = _camera_entry(viewpoint_camera, dev)[4]
+    if not slot:
+        R = viewpoint_camera.R
+        R = R.detach().to("cpu", torch.float32).numpy() if torch.is_tensor(R) else np.asarray(R, dtype=np.float32)
+        slot.append(tuple(float(x) for x in R.T.reshape(-1)))
+    return slot[0]
 
 
 def _mirror_rays_blended(viewpoint_camera, rend_normal, rend_alpha, surf_depth):
