@@ -611,6 +611,39 @@ int mrgs_warp_ncc_forward(const MrgsWarpConfig* cfg, const MrgsWarpMaps* maps, c
 int mrgs_warp_ncc_backward(const MrgsWarpConfig* cfg, const void* warp_ws, const void* ws, float ncc_weight, const float* g_term,
                            float* g_normal_v, float* g_distance_v, void* stream);
 
+/* ---- multi-view reflection score of one view (calc_ref_score, train_refreal.py:782-1001, train_refnerf.py:791-1010) ----------------
+ * For every pixel p of view v: how much the photographs of its K neighbours disagree with v's own over a plane-warped patch.  One call
+ * handles all K neighbours of the view; `neighbours_dev` is a DEVICE table of K records, read in order.  All views are H x W.
+ * A neighbour n is valid at p under the reprojection check of mrgs_warp_loss_forward: p back-projected through depth_v, projected
+ * into n (0 < u < W, 0 < v < H, z > 0.1), depth_n read there (bilinear, border, align_corners), back-projected, re-projected into v,
+ * and |p' - p| < pixel_noise_th.  Taps t of the (2 patch_half + 1)^2 = P patch: a[c,t] = image_v at the integer texel (zeros
+ * outside), s_n[c,t] = image_n through the plane homography of p built from normal_v(p) and distance_v(p) (bilinear, zeros,
+ * align_corners, + 1e-10 on the third component; a non-finite position samples zero).  cnt(p) = valid neighbours;
+ * score(p) = [cnt > 0] (1/P) sum_t sum_c (sum_{n valid} |s_n[c,t] - a[c,t]|) / (cnt + 1e-8).
+ * depth_v, distance_v [H,W]; normal_v, image_v [3,H,W]; cam_v: device record of 28 floats as in MrgsWarpMaps.  score [H,W] float and
+ * count [H,W] int32 (may be NULL) are written in full.  Geometry and homography in double, colours in fp32.  No atomics, no
+ * workspace, no host synchronisation; neighbours and taps go in a fixed order, so the call is bitwise repeatable.  n_neighbours = 0
+ * writes zeros (neighbours_dev may then be NULL).
+ * MRGS_E_BAD_ARG before any HIP call: a wrong struct_size, H or W <= 0, H W >= 2^30, patch_half outside 1..4, n_neighbours < 0,
+ * an intrinsic or pixel_noise_th that is NaN, fx or fy not > 0, a NULL pointer other than count (and neighbours_dev with K = 0). */
+typedef struct MrgsRefScoreConfig {
+    uint32_t struct_size;           /* = sizeof(MrgsRefScoreConfig) */
+    int32_t H, W;
+    int32_t patch_half;             /* 1 .. 4 (the reference uses 4: 81 taps) */
+    int32_t n_neighbours;           /* K >= 0 */
+    float fx_v, fy_v, cx_v, cy_v;   /* Fx, Fy, Cx, Cy of the view (scene/cameras.py:65-68) */
+    float pixel_noise_th;           /* opt.multi_view_pixel_noise_th */
+} MrgsRefScoreConfig;
+typedef struct MrgsRefScoreNeighbour {
+    const float* depth;             /* surf_depth of the neighbour [H,W] */
+    const float* image;             /* its photograph [3,H,W] */
+    float cam[28];                  /* world_view_transform (16), R (9), T (3) */
+    float fx, fy, cx, cy;
+} MrgsRefScoreNeighbour;
+int mrgs_ref_score(const MrgsRefScoreConfig* cfg, const float* depth_v, const float* normal_v, const float* distance_v,
+                   const float* image_v, const float* cam_v, const MrgsRefScoreNeighbour* neighbours_dev, float* score, int32_t* count,
+                   void* stream);
+
 /* ---- closest-hit ray queries against a triangle mesh (visibility rays) --------------------
  * Replaces RayTracer(vertices, triangles).trace (submodules/raytracing/raytracing/raytracer.py:8-56,
  * raytracing_brdf/raytracer.py:18-123) = create_raytracer + TriangleBvh4::build / ray_trace_gpu

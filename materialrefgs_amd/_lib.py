@@ -114,6 +114,16 @@ class MrgsWarpMaps(ctypes.Structure):
                                         "rough_n", "fg_v", "keep_v", "cam_v", "cam_n")]
 
 
+class MrgsRefScoreConfig(_Sized):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("H", c_int32), ("W", c_int32), ("patch_half", c_int32), ("n_neighbours", c_int32)] + \
+               [(n, c_float) for n in ("fx_v", "fy_v", "cx_v", "cy_v", "pixel_noise_th")]
+
+
+class MrgsRefScoreNeighbour(ctypes.Structure):
+    _fields_ = [("depth", c_void_p), ("image", c_void_p), ("cam", c_float * 28), ("fx", c_float), ("fy", c_float), ("cx", c_float),
+                ("cy", c_float)]
+
+
 class MrgsAdamTensor(ctypes.Structure):
     _fields_ = [("param", c_void_p), ("grad", c_void_p), ("exp_avg", c_void_p), ("exp_avg_sq", c_void_p), ("numel", c_int64),
                 ("lr", c_float), ("step", c_int32)]
@@ -225,6 +235,7 @@ SYMBOLS = {
                                              c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_float] + [c_void_p] * 6),
     "mrgs_warp_ncc_backward": (ctypes.c_int, [ctypes.POINTER(MrgsWarpConfig), c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p,
                                               c_void_p]),
+    "mrgs_ref_score": (ctypes.c_int, [ctypes.POINTER(MrgsRefScoreConfig)] + [c_void_p] * 9),
     "mrgs_bvh_bytes": (c_size_t, [c_int64]),
     "mrgs_bvh_build": (ctypes.c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_size_t]),
     "mrgs_bvh_trace": (ctypes.c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -598,6 +598,13 @@ int mrgs_prior_terms_backward(const MrgsPriorConfig* cfg, const float* Rt, const
                                                fwd_terms, g_terms, g_surf_normal, g_rend_normal, g_alpha, g_refl, g_rough, stream_, &launched));
 }
 
+// ---- reflection score (kernel, checks and launch: mrgs_multiview.hip) ---------------------------------
+int mrgs_ref_score(const MrgsRefScoreConfig* cfg, const float* depth_v, const float* normal_v, const float* distance_v, const float* image_v,
+                   const float* cam_v, const MrgsRefScoreNeighbour* neighbours_dev, float* score, int32_t* count, void* stream_)
+{
+    MRGS_MESH_ENTRY(mrgs_ref_score_launch(cfg, depth_v, normal_v, distance_v, image_v, cam_v, neighbours_dev, score, count, stream_, &launched));
+}
+
 // ---- introspection for the parity tests --------------------------------------------------------------
 __global__ void export_rec_kernel(int P, int which, const float4* __restrict__ rec, const uint8_t* __restrict__ clamped, void* dst)
 {

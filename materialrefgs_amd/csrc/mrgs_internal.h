@@ -181,6 +181,11 @@ void mrgs_launch_render_bwd(const MrgsRasterConfig& cfg, const MrgsRasterInputs&
                             const uint8_t* cflag, const MrgsImgWs& img, const float* dL_dpix, const float* dL_dpix_f, const float* dL_dothers,
                             float* grad_rec, bool forward_queues, hipStream_t stream);
 
+// reflection score (mrgs_multiview.hip): all argument checks, then the launch
+int mrgs_ref_score_launch(const MrgsRefScoreConfig* cfg, const float* depth_v, const float* normal_v, const float* distance_v,
+                          const float* image_v, const float* cam_v, const MrgsRefScoreNeighbour* neighbours_dev, float* score, int32_t* count,
+                          void* stream, bool* launched);
+
 // mesh extraction (mrgs_mesh.hip): all argument checks, then the launches; *launched = something was queued (mrgs_api.hip reports its status)
 int mrgs_tsdf_fuse_launch(const MrgsTsdfConfig* cfg, const MrgsTsdfView* views, float* field, float* weight_debug, void* stream, bool* launched);
 int mrgs_mesh_count_launch(const MrgsMeshConfig* cfg, const float* field, void* ws, size_t ws_bytes, int64_t* totals_dev, void* stream, bool* launched);

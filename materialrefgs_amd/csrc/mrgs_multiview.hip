@@ -20,6 +20,8 @@
 //   warp_nbr_scatter    per sample wave: the bilinear corners of every neighbour tap (atomics).
 // Grey-image NCC (train_refreal.py's get_consistency_loss2), a second pair of calls on the same draw: warp_ncc_fwd / warp_ncc_finalize /
 // warp_ncc_bwd, described where they stand at the end of the file.
+// Reflection score (calc_ref_score, the producer of the ref-score loss's input): ref_score_fwd at the end of the file, one dense gather
+// pass per view over all of its neighbours with the geometry, homography and bilinear helpers of the kernels above.
 // The file is compiled with -ffp-contract=off: the tap positions of the backward kernels repeat the forward's arithmetic bit for bit.
 #include "mrgs_internal.h"
 #include "mrgs_wave.h"
@@ -1072,4 +1074,117 @@ extern "C" int mrgs_warp_ncc_backward(const MrgsWarpConfig* cfg, const void* war
     const int32_t* slot = (a.flags & MRGS_WARP_MATERIAL) ? w.slot : n.slot;
     warp_ncc_bwd<<<(HW + WB - 1) / WB, WB, 0, (hipStream_t)stream>>>(HW, slot, n, ncc_weight, g_term, g_normal_v, g_distance_v);
     return MRGS_LAUNCH_STATUS();
+}
+
+// ---- multi-view reflection score (calc_ref_score, train_refreal.py:782-1001) ---------------------------------------------------------
+// Dense, where the kernels above work on a sample list: every pixel of the view against all of its K neighbours, (2h+1)^2 <= 81 taps.
+//   ref_score_fwd       one 64-lane wave per 8x8 pixel block, one pixel per lane.  The view's (8+2h)^2 x 3 anchor tile sits in LDS.
+//                       Neighbours outside, taps inside: geo_pixel decides validity, a ballot skips a neighbour no lane is valid for
+//                       (background blocks cost the geometry only), then every valid lane walks its patch through its own homography
+//                       (homography, nbr_foot and bil above: positions in double, colours in fp32).  |s - a| is summed per tap row,
+//                       the rows per neighbour, the neighbours per pixel, all in fp32 and in a fixed order: no atomics, no workspace.
+namespace {
+
+constexpr int RS_B = 8;                  // pixel block side: 8 x 8 = one wave
+constexpr int RS_TS = RS_B + 2 * 4;      // anchor tile side at the largest patch
+constexpr int RS_LD = 24;                // tile row stride in floats: rows 0..3 (and 4..7) of a half wave fall on distinct banks
+
+struct RefArgs {
+    int H, W, h, K;
+    double fxv, fyv, cxv, cyv;
+    float th;
+};
+
+__global__ __launch_bounds__(64) void ref_score_fwd(RefArgs r, const float* __restrict__ Dv, const float* __restrict__ Nv,
+                                                    const float* __restrict__ dist_v, const float* __restrict__ img_v,
+                                                    const float* __restrict__ camv, const MrgsRefScoreNeighbour* __restrict__ nbrs,
+                                                    float* __restrict__ score, int32_t* __restrict__ count)
+{
+    __shared__ float tile[3][RS_TS][RS_LD];
+    const int lane = threadIdx.x;
+    const int lx = lane & (RS_B - 1), ly = lane >> 3;
+    const int nbx = (r.W + RS_B - 1) / RS_B;
+    const int bx0 = (int)(blockIdx.x % nbx) * RS_B, by0 = (int)(blockIdx.x / nbx) * RS_B;
+    const int x = bx0 + lx, y = by0 + ly;
+    const size_t HW = (size_t)r.H * r.W;
+    const int side = 2 * r.h + 1, ts = RS_B + 2 * r.h;
+    // the anchor tile: image_v at the integer texels around the block, zero outside the image
+    for (int i = lane; i < 3 * ts * ts; i += 64) {
+        const int c = i / (ts * ts), q = i - c * ts * ts;
+        const int ty = q / ts, tx = q - ty * ts;
+        const int gx = bx0 - r.h + tx, gy = by0 - r.h + ty;
+        const bool in = gx >= 0 && gy >= 0 && gx < r.W && gy < r.H;
+        tile[c][ty][tx] = in ? img_v[c * HW + (size_t)gy * r.W + gx] : 0.f;
+    }
+    __syncthreads();
+    const bool in = x < r.W && y < r.H;
+    const int p = in ? y * r.W + x : 0;
+    const float dv = in ? Dv[p] : 0.f;
+    WarpArgs a{};
+    a.H = r.H; a.W = r.W; a.h = r.h; a.P = side * side;
+    a.fxv = r.fxv; a.fyv = r.fyv; a.cxv = r.cxv; a.cyv = r.cyv;
+    a.th = r.th;
+    Maps m{};
+    m.normal_v = Nv; m.dist_v = dist_v;
+    Cam cv;
+    load_cam(camv, cv);
+    float total = 0.f;
+    int cnt = 0;
+    for (int k = 0; k < r.K; ++k) {
+        const MrgsRefScoreNeighbour& nb = nbrs[k];
+        Cam cn;
+        load_cam(nb.cam, cn);
+        a.fxn = (double)nb.fx; a.fyn = (double)nb.fy; a.cxn = (double)nb.cx; a.cyn = (double)nb.cy;
+        bool valid = false;
+        if (in) {
+            const GeoOut g = geo_pixel(a, cv, cn, nb.depth, x, y, dv);
+            valid = is_valid(a, g);
+        }
+        if (__ballot(valid) == 0ull) continue;              // wave-uniform
+        if (valid) {
+            double Hs[9];
+            homography(a, cv, cn, m, p, Hs);
+            const float* __restrict__ img_n = nb.image;
+            float acc = 0.f;
+            for (int oy = 0; oy < side; ++oy) {
+                float row = 0.f;
+                for (int ox = 0; ox < side; ++ox) {
+                    const Foot f = nbr_foot(a, Hs, x + ox - r.h, y + oy - r.h);
+                    for (int c = 0; c < 3; ++c) row += fabsf(bil(a, f, img_n + c * HW) - tile[c][ly + oy][lx + ox]);
+                }
+                acc += row;
+            }
+            total += acc;
+            ++cnt;
+        }
+    }
+    if (in) {
+        score[p] = cnt > 0 ? total / ((float)cnt + 1e-8f) / (float)(side * side) : 0.f;
+        if (count) count[p] = cnt;
+    }
+}
+
+}   // namespace
+
+// every check, then the launch (the extern "C" half, which reports the launch status, is in mrgs_api.hip)
+int mrgs_ref_score_launch(const MrgsRefScoreConfig* cfg, const float* depth_v, const float* normal_v, const float* distance_v,
+                          const float* image_v, const float* cam_v, const MrgsRefScoreNeighbour* neighbours_dev, float* score, int32_t* count,
+                          void* stream, bool* launched)
+{
+    if (!cfg || cfg->struct_size != sizeof(MrgsRefScoreConfig)) return MRGS_E_BAD_ARG;
+    if (cfg->H <= 0 || cfg->W <= 0 || (int64_t)cfg->H * cfg->W >= ((int64_t)1 << 30)) return MRGS_E_BAD_ARG;
+    if (cfg->patch_half < 1 || cfg->patch_half > 4 || cfg->n_neighbours < 0) return MRGS_E_BAD_ARG;
+    const float f[5] = {cfg->fx_v, cfg->fy_v, cfg->cx_v, cfg->cy_v, cfg->pixel_noise_th};
+    for (int i = 0; i < 5; ++i)
+        if (!(f[i] == f[i]) || (i < 2 && !(f[i] > 0.f))) return MRGS_E_BAD_ARG;
+    if (!depth_v || !normal_v || !distance_v || !image_v || !cam_v || !score) return MRGS_E_BAD_ARG;
+    if (cfg->n_neighbours > 0 && !neighbours_dev) return MRGS_E_BAD_ARG;
+    RefArgs r;
+    r.H = cfg->H; r.W = cfg->W; r.h = cfg->patch_half; r.K = cfg->n_neighbours;
+    r.fxv = cfg->fx_v; r.fyv = cfg->fy_v; r.cxv = cfg->cx_v; r.cyv = cfg->cy_v;
+    r.th = cfg->pixel_noise_th;
+    const int64_t nblk = (int64_t)((r.W + RS_B - 1) / RS_B) * ((r.H + RS_B - 1) / RS_B);      // < 2^30
+    ref_score_fwd<<<(unsigned)nblk, 64, 0, (hipStream_t)stream>>>(r, depth_v, normal_v, distance_v, image_v, cam_v, neighbours_dev, score, count);
+    *launched = true;
+    return MRGS_OK;
 }
