@@ -854,6 +854,83 @@ int mrgs_densify_emit(const MrgsDensifyConfig* cfg, const void* ws, const int64_
 int mrgs_densify_stats(int64_t P, const float* grad, const uint8_t* visible, const int32_t* radii, float* accum, float* denom,
                        float* max_radii, void* stream);
 
+/* ---- EnvGaussianModel.densify_and_prune and add_densification_stats (scene/env_gaussian_model.py:384-603) --------------------------
+ * The six-stage chain of the environment set in classify passes over per-row numbers and ONE emit pass; no intermediate copy of a
+ * parameter tensor exists.  Per source row i (fp32): a = accum, d = denom, r = max_radii, w = weight_accum, s = exp(scaling_raw),
+ * m = max(s), o = sigmoid(opacity_raw), t = percent_dense_extent.  Literal to the reference, its quirks included:
+ *   1 clone   g = a / d (IEEE, NaN -> 0); clone iff |g| >= max_grad and m <= t.  A clone copies every parameter and a, d, r; its
+ *             weight is w * W0, W0 = max of w over the P rows (QUIRK: densify_stats multiplies by xyz_weight_accum.max(), :388).
+ *   2 split   over the P + clones rows: split iff m > t and g >= max_grad (QUIRK: a clone carries its source's g, but m <= t, so with
+ *             split_screen_threshold None -- the only value served: MRGS_ENV_DENSIFY_SPLIT_SCREEN in flags is MRGS_E_UNSUPPORTED --
+ *             clones never split).  Two children: raw scaling log(s / 1.6), xyz + R(normalize(rot)) (s_x z0, s_y z1, 0), radius
+ *             r * fl32(1 / 1.6), d copied, weight w * W1 with W1 = max of the weights over the rows before the split, clones included.
+ *             Sources are removed.
+ *   3 opacity rows with o < min_opacity go.
+ *   4 scene / screen   over the n rows now present: wavg = weight / d (IEEE, NaN -> 0), q = their 0.1 quantile (rule below),
+ *             big = (MRGS_ENV_DENSIFY_SCREEN and radius > max_screen_size) or m_row > world_size_limit (a child's m_row is exp of the raw
+ *             scaling it was given), low = wavg < q.  big and low: pruned.  big and not low: replaced by FIVE children with divisor 2.5,
+ *             the same formulas, weight * W4, W4 = max of the weights over the rows left after this stage's prune, the sources about to
+ *             be split included.  A stage-2 child split here compounds both offsets and both scalings.
+ *   5 cap     with more than n_after rows present, the rows - n_after rows of smallest wavg go.  TIES: among equal wavg (-0 = +0) the
+ *             row earlier in the output order goes first (torch.topk leaves ties unspecified: this rule is this library's).
+ *   6 reset   the caller zeroes the four statistics vectors at the new length.
+ * Zero rows after stage 3 end the call with zero rows (the reference would raise inside torch.quantile).
+ * Quantile, every operation a single fp32 rounding: rank = 0.1f * (float)(n - 1), lo = floor(rank), hi = ceil(rank), f = rank - lo, v_lo /
+ * v_hi the exact order statistics, q = v_lo + f (v_hi - v_lo) if f < 0.5 else v_hi - (v_hi - v_lo)(1 - f): torch's fp32 quantile / lerp up
+ * to whether torch fuses the multiply-add; to the last ulp it is this library's.  The weight path (w, W0, W1, W4, the products, wavg, q,
+ * the cut) and the radius path are single IEEE multiplies / divides / maxima / compares.  NaN in weight_accum is not served.
+ * Output order: kept slot rows -- unsplit originals, clones, stage-2 child 0, child 1, each in source-row order --, then the stage-4
+ * children child-major (child j of every split slot row in that same order, j = 0..4); stage 5 removes rows without reordering.
+ * Roles as MrgsDensifyTensor's: COPY; MOMENT travels with surviving originals and is zero for every clone and child; XYZ, SCALING up to
+ * two generations.  z of stage-2 child k: noise[(row * 2 + k) * 2 + {0,1}] or Philox4x32-10 as mrgs_densify_emit, counter (row lo, row
+ * hi, k, 0); of stage-4 child j of slot sigma (0 original, 1 clone, 2 + k stage-2 child k): noise4[((row * 4 + sigma) * 5 + j) * 2 +
+ * {0,1}] or counter (row lo, row hi, j, 1 + sigma).
+ * Host reads: ONE.  mrgs_env_densify_classify queues every pass (the selections take k from device memory) and writes
+ * MRGS_ENV_DENSIFY_COUNTS int64 to counts_dev: [0,24) rows per output segment (kept slot sigma: sigma; stage-4 child j of slot sigma:
+ * 4 + 4 j + sigma), [24] their sum, [25] rows cloned by stage 1, [26] rows split by stage 2, [27] n, [28] / [29] slot rows pruned / split
+ * by stage 4, [30] rows removed by stage 5, [31] float bits of q, [32..34] of W0, W1, W4, [35] of the stage-5 cut, [36] rows before
+ * stage 5, [37] stage 5 ran.  The caller reads them once, allocates counts[24]-row destinations and calls mrgs_env_densify_emit.
+ * Workspace: mrgs_env_densify_ws_bytes(P) = 8192 + align256(40 P) + align256(4 P) + 2 align256(96 ceil(P / 256)) bytes (ten keys and a
+ * record per row, sized for the 10 P-row worst case; two [24][blocks] matrices), 256-byte aligned.  No allocation, no synchronisation.
+ * Codes, all before any launch: MRGS_E_BAD_ARG for a wrong struct_size, P < 0, n_after < 0, max_grad not > 0, unknown flags, a NULL
+ * pointer with P > 0 (a dst may be NULL when n_rows is 0), ws too small or misaligned, n_rows outside 0..10 P, a bad tensor entry as
+ * mrgs_densify_emit; MRGS_E_UNSUPPORTED for MRGS_ENV_DENSIFY_SPLIT_SCREEN and for 10 P >= 2^31; P = 0 returns MRGS_OK and launches nothing. */
+#define MRGS_ENV_DENSIFY_SCREEN 1u        /* max_screen_size is given (not None) */
+#define MRGS_ENV_DENSIFY_SPLIT_SCREEN 2u  /* split_screen_threshold is given: not served */
+#define MRGS_ENV_DENSIFY_COUNTS 40
+typedef struct MrgsEnvDensifyConfig {
+    uint32_t struct_size;            /* = sizeof(MrgsEnvDensifyConfig) */
+    uint32_t flags;                  /* MRGS_ENV_DENSIFY_* */
+    int64_t P;                       /* rows before the call */
+    int64_t n_after;                 /* int(max_gs * max_gs_threshold) */
+    float max_grad, min_opacity, percent_dense_extent;
+    float world_size_limit;          /* 0.1 * extent */
+    float max_screen_size;           /* read with MRGS_ENV_DENSIFY_SCREEN */
+    float reserved;
+    const float* xyz_raw;            /* [P,3]  read by mrgs_env_densify_emit when a table entry has role XYZ */
+    const float* scaling_raw;        /* [P,2] */
+    const float* rotation_raw;       /* [P,4]  (w,x,y,z), un-normalised */
+} MrgsEnvDensifyConfig;
+size_t mrgs_env_densify_ws_bytes(int64_t P);
+int mrgs_env_densify_classify(const MrgsEnvDensifyConfig* cfg, const float* accum, const float* denom, const float* max_radii,
+                              const float* weight_accum, const float* scaling_raw, const float* opacity_raw, void* ws, size_t ws_bytes,
+                              int64_t* counts_dev, void* stream);
+int mrgs_env_densify_emit(const MrgsEnvDensifyConfig* cfg, const void* ws, int64_t n_rows, const MrgsDensifyTensor* tensors,
+                          int32_t n_tensors, uint64_t seed, const float* noise, const float* noise4, void* stream);
+/* The selection both stages use, on its own: the k-th smallest (k from 0) of n fp32 values by a radix select over the order-preserving
+ * integer image of the float, 8-bit digits, histograms in LDS, one global add per non-empty bin and block; -0 and +0 are one value, NaN
+ * is not served.  out_dev (device uint32[4]): float bits of the value, how many values are smaller, how many are equal, k.  ws:
+ * mrgs_env_select_ws_bytes() bytes, 256-byte aligned.  MRGS_E_BAD_ARG: n < 0, n >= 2^31, k outside [0, n), a NULL pointer, ws too small;
+ * n = 0 returns MRGS_OK and launches nothing. */
+size_t mrgs_env_select_ws_bytes(void);
+int mrgs_env_select(int64_t n, const float* values, int64_t k, void* ws, size_t ws_bytes, uint32_t* out_dev, void* stream);
+/* EnvGaussianModel.add_densification_stats (:600-603).  For rows with visible[i] != 0: accum[i] += ||grad[i, 0:3]||_2, denom[i] += 1 and,
+ * when weight_accumulate is given, weight_accum[i] += weight_accumulate[i].  In place, one launch, nothing read back; max_radii2D is not
+ * touched (the reference's update_env_gs never updates it).  MRGS_E_BAD_ARG: P < 0, a NULL pointer with P > 0 (weight_accumulate may be
+ * NULL; weight_accum then too). */
+int mrgs_env_densify_stats(int64_t P, const float* grad, const uint8_t* visible, const float* weight_accumulate, float* accum, float* denom,
+                           float* weight_accum, void* stream);
+
 /* View-parallel training (materialrefgs_amd/dist.py): sum over V views of the SH colour gradients from each view's masked colour
  * gradient dRGB_v = dL/dsh_v[:,0,:] / SH_C0 and camera centre: dL_dsh[p][k][c] = sum_v B_k(normalize(means3D[p] - campos_v)) dRGB_v[p][c]
  * for k < (D+1)^2, 0 beyond (backward.cu:22-141).  gathered = V rows of row_stride floats, row v = [dRGB_v (P x 3) | campos_v (3)]

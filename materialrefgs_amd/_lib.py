@@ -146,6 +146,15 @@ class MrgsDensifyTensor(ctypes.Structure):
     _fields_ = [("src", c_void_p), ("dst", c_void_p), ("row_floats", c_int32), ("role", c_int32)]
 
 
+MRGS_ENV_DENSIFY_SCREEN, MRGS_ENV_DENSIFY_SPLIT_SCREEN, MRGS_ENV_DENSIFY_COUNTS = 1, 2, 40
+
+
+class MrgsEnvDensifyConfig(_Sized):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("P", c_int64), ("n_after", c_int64), ("max_grad", c_float),
+                ("min_opacity", c_float), ("percent_dense_extent", c_float), ("world_size_limit", c_float), ("max_screen_size", c_float),
+                ("reserved", c_float), ("xyz_raw", c_void_p), ("scaling_raw", c_void_p), ("rotation_raw", c_void_p)]
+
+
 MRGS_TSDF_CONTRACTED, MRGS_TSDF_PLAIN, MRGS_TSDF_POINTS = 0, 1, 2
 
 
@@ -286,6 +295,14 @@ SYMBOLS = {
     "mrgs_densify_emit": (ctypes.c_int, [ctypes.POINTER(MrgsDensifyConfig), c_void_p, ctypes.POINTER(c_int64),
                                          ctypes.POINTER(MrgsDensifyTensor), c_int32, ctypes.c_uint64, c_void_p, c_void_p]),
     "mrgs_densify_stats": (ctypes.c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mrgs_env_densify_ws_bytes": (c_size_t, [c_int64]),
+    "mrgs_env_densify_classify": (ctypes.c_int, [ctypes.POINTER(MrgsEnvDensifyConfig), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                 c_void_p, c_size_t, c_void_p, c_void_p]),
+    "mrgs_env_densify_emit": (ctypes.c_int, [ctypes.POINTER(MrgsEnvDensifyConfig), c_void_p, c_int64, ctypes.POINTER(MrgsDensifyTensor), c_int32,
+                                             ctypes.c_uint64, c_void_p, c_void_p, c_void_p]),
+    "mrgs_env_select_ws_bytes": (c_size_t, []),
+    "mrgs_env_select": (ctypes.c_int, [c_int64, c_void_p, c_int64, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "mrgs_env_densify_stats": (ctypes.c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "mrgs_tsdf_fuse": (ctypes.c_int, [ctypes.POINTER(MrgsTsdfConfig), c_void_p, c_void_p, c_void_p, c_void_p]),
     "mrgs_mesh_ws_bytes": (c_size_t, [ctypes.POINTER(MrgsMeshConfig)]),
     "mrgs_mesh_count": (ctypes.c_int, [ctypes.POINTER(MrgsMeshConfig), c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),

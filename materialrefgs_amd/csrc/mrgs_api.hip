@@ -598,6 +598,29 @@ int mrgs_prior_terms_backward(const MrgsPriorConfig* cfg, const float* Rt, const
                                                fwd_terms, g_terms, g_surf_normal, g_rend_normal, g_alpha, g_refl, g_rough, stream_, &launched));
 }
 
+// ---- the environment set's policy (kernels, checks and launches: mrgs_env_densify.hip) ------------------
+int mrgs_env_densify_classify(const MrgsEnvDensifyConfig* cfg, const float* accum, const float* denom, const float* max_radii,
+                              const float* weight_accum, const float* scaling_raw, const float* opacity_raw, void* ws, size_t ws_bytes,
+                              int64_t* counts_dev, void* stream_)
+{
+    MRGS_MESH_ENTRY(mrgs_env_densify_classify_launch(cfg, accum, denom, max_radii, weight_accum, scaling_raw, opacity_raw, ws, ws_bytes, counts_dev,
+                                                     stream_, &launched));
+}
+int mrgs_env_densify_emit(const MrgsEnvDensifyConfig* cfg, const void* ws, int64_t n_rows, const MrgsDensifyTensor* tensors, int32_t n_tensors,
+                          uint64_t seed, const float* noise, const float* noise4, void* stream_)
+{
+    MRGS_MESH_ENTRY(mrgs_env_densify_emit_launch(cfg, ws, n_rows, tensors, n_tensors, seed, noise, noise4, stream_, &launched));
+}
+int mrgs_env_select(int64_t n, const float* values, int64_t k, void* ws, size_t ws_bytes, uint32_t* out_dev, void* stream_)
+{
+    MRGS_MESH_ENTRY(mrgs_env_select_launch(n, values, k, ws, ws_bytes, out_dev, stream_, &launched));
+}
+int mrgs_env_densify_stats(int64_t P, const float* grad, const uint8_t* visible, const float* weight_accumulate, float* accum, float* denom,
+                           float* weight_accum, void* stream_)
+{
+    MRGS_MESH_ENTRY(mrgs_env_densify_stats_launch(P, grad, visible, weight_accumulate, accum, denom, weight_accum, stream_, &launched));
+}
+
 // ---- reflection score (kernel, checks and launch: mrgs_multiview.hip) ---------------------------------
 int mrgs_ref_score(const MrgsRefScoreConfig* cfg, const float* depth_v, const float* normal_v, const float* distance_v, const float* image_v,
                    const float* cam_v, const MrgsRefScoreNeighbour* neighbours_dev, float* score, int32_t* count, void* stream_)

@@ -206,6 +206,16 @@ int mrgs_prior_backward_launch(const MrgsPriorConfig* cfg, const float* Rt, cons
                                const uint8_t* ref_score, const float* fwd_terms, const float* const* g_terms, float* g_surf_normal,
                                float* g_rend_normal, float* g_alpha, float* g_refl, float* g_rough, void* stream, bool* launched);
 
+// the environment set's policy (mrgs_env_densify.hip): the same split
+int mrgs_env_densify_classify_launch(const MrgsEnvDensifyConfig* cfg, const float* accum, const float* denom, const float* max_radii,
+                                     const float* weight_accum, const float* scaling_raw, const float* opacity_raw, void* ws, size_t ws_bytes,
+                                     int64_t* counts_dev, void* stream, bool* launched);
+int mrgs_env_densify_emit_launch(const MrgsEnvDensifyConfig* cfg, const void* ws, int64_t n_rows, const MrgsDensifyTensor* tensors,
+                                 int32_t n_tensors, uint64_t seed, const float* noise, const float* noise4, void* stream, bool* launched);
+int mrgs_env_select_launch(int64_t n, const float* values, int64_t k, void* ws, size_t ws_bytes, uint32_t* out_dev, void* stream, bool* launched);
+int mrgs_env_densify_stats_launch(int64_t P, const float* grad, const uint8_t* visible, const float* weight_accumulate, float* accum,
+                                  float* denom, float* weight_accum, void* stream, bool* launched);
+
 #ifndef MRGS_EXP
 #define MRGS_EXP(x) expf(x)
 #endif
