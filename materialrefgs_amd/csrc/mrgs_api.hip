@@ -551,83 +551,6 @@ int mrgs_mark_visible(int32_t P, const float* means3D, const float* viewmatrix, 
     return MRGS_LAUNCH_STATUS();
 }
 
-// ---- mesh extraction (kernels, checks and launches: mrgs_mesh.hip) ------------------------------------
-// (also the form of the prior terms' entry points below)
-#define MRGS_MESH_ENTRY(call) do { bool launched = false; if (int rc = (call)) return rc; return launched ? MRGS_LAUNCH_STATUS() : MRGS_OK; } while (0)
-int mrgs_tsdf_fuse(const MrgsTsdfConfig* cfg, const MrgsTsdfView* views_dev, float* field, float* weight_debug, void* stream_)
-{
-    MRGS_MESH_ENTRY(mrgs_tsdf_fuse_launch(cfg, views_dev, field, weight_debug, stream_, &launched));
-}
-int mrgs_mesh_count(const MrgsMeshConfig* cfg, const float* field, void* ws, size_t ws_bytes, int64_t* totals_dev, void* stream_)
-{
-    MRGS_MESH_ENTRY(mrgs_mesh_count_launch(cfg, field, ws, ws_bytes, totals_dev, stream_, &launched));
-}
-int mrgs_mesh_emit(const MrgsMeshConfig* cfg, const float* field, void* ws, size_t ws_bytes, const int64_t* totals_host, float* vertices,
-                   int32_t* triangles, void* stream_)
-{
-    MRGS_MESH_ENTRY(mrgs_mesh_emit_launch(cfg, field, ws, ws_bytes, totals_host, vertices, triangles, stream_, &launched));
-}
-int mrgs_mesh_clusters(int64_t V, int64_t T, const int32_t* triangles, int32_t* labels, int32_t* counts, void* stream_)
-{
-    MRGS_MESH_ENTRY(mrgs_mesh_clusters_launch(V, T, triangles, labels, counts, stream_, &launched));
-}
-int mrgs_mesh_select(int64_t V, int64_t T, const int32_t* triangles, const int32_t* labels, const int32_t* counts, int32_t threshold,
-                     uint8_t* keep_vertex, uint8_t* keep_triangle, void* stream_)
-{
-    MRGS_MESH_ENTRY(mrgs_mesh_select_launch(V, T, triangles, labels, counts, threshold, keep_vertex, keep_triangle, stream_, &launched));
-}
-int mrgs_mesh_reindex(int64_t V_old, int64_t V_new, const int32_t* new_to_old, int32_t* remap_ws, int64_t T, int32_t* triangles, void* stream_)
-{
-    MRGS_MESH_ENTRY(mrgs_mesh_reindex_launch(V_old, V_new, new_to_old, remap_ws, T, triangles, stream_, &launched));
-}
-
-// ---- per-pixel prior terms (kernels, checks and launches: mrgs_prior.hip) ------------------------------
-int mrgs_prior_terms_forward(const MrgsPriorConfig* cfg, const float* Rt, const float* surf_normal, const float* rend_normal, const float* prior,
-                             const float* mask, const float* rend_alpha, const float* alpha_mask, const float* refl, const float* rough,
-                             const uint8_t* ref_score, void* ws, size_t ws_bytes, float* out_terms, void* stream_)
-{
-    MRGS_MESH_ENTRY(mrgs_prior_forward_launch(cfg, Rt, surf_normal, rend_normal, prior, mask, rend_alpha, alpha_mask, refl, rough, ref_score, ws,
-                                              ws_bytes, out_terms, stream_, &launched));
-}
-int mrgs_prior_terms_backward(const MrgsPriorConfig* cfg, const float* Rt, const float* surf_normal, const float* rend_normal, const float* prior,
-                              const float* mask, const float* rend_alpha, const float* alpha_mask, const float* refl, const float* rough,
-                              const uint8_t* ref_score, const float* fwd_terms, const float* const* g_terms, float* g_surf_normal,
-                              float* g_rend_normal, float* g_alpha, float* g_refl, float* g_rough, void* stream_)
-{
-    MRGS_MESH_ENTRY(mrgs_prior_backward_launch(cfg, Rt, surf_normal, rend_normal, prior, mask, rend_alpha, alpha_mask, refl, rough, ref_score,
-                                               fwd_terms, g_terms, g_surf_normal, g_rend_normal, g_alpha, g_refl, g_rough, stream_, &launched));
-}
-
-// ---- the environment set's policy (kernels, checks and launches: mrgs_env_densify.hip) ------------------
-int mrgs_env_densify_classify(const MrgsEnvDensifyConfig* cfg, const float* accum, const float* denom, const float* max_radii,
-                              const float* weight_accum, const float* scaling_raw, const float* opacity_raw, void* ws, size_t ws_bytes,
-                              int64_t* counts_dev, void* stream_)
-{
-    MRGS_MESH_ENTRY(mrgs_env_densify_classify_launch(cfg, accum, denom, max_radii, weight_accum, scaling_raw, opacity_raw, ws, ws_bytes, counts_dev,
-                                                     stream_, &launched));
-}
-int mrgs_env_densify_emit(const MrgsEnvDensifyConfig* cfg, const void* ws, int64_t n_rows, const MrgsDensifyTensor* tensors, int32_t n_tensors,
-                          uint64_t seed, const float* noise, const float* noise4, void* stream_)
-{
-    MRGS_MESH_ENTRY(mrgs_env_densify_emit_launch(cfg, ws, n_rows, tensors, n_tensors, seed, noise, noise4, stream_, &launched));
-}
-int mrgs_env_select(int64_t n, const float* values, int64_t k, void* ws, size_t ws_bytes, uint32_t* out_dev, void* stream_)
-{
-    MRGS_MESH_ENTRY(mrgs_env_select_launch(n, values, k, ws, ws_bytes, out_dev, stream_, &launched));
-}
-int mrgs_env_densify_stats(int64_t P, const float* grad, const uint8_t* visible, const float* weight_accumulate, float* accum, float* denom,
-                           float* weight_accum, void* stream_)
-{
-    MRGS_MESH_ENTRY(mrgs_env_densify_stats_launch(P, grad, visible, weight_accumulate, accum, denom, weight_accum, stream_, &launched));
-}
-
-// ---- reflection score (kernel, checks and launch: mrgs_multiview.hip) ---------------------------------
-int mrgs_ref_score(const MrgsRefScoreConfig* cfg, const float* depth_v, const float* normal_v, const float* distance_v, const float* image_v,
-                   const float* cam_v, const MrgsRefScoreNeighbour* neighbours_dev, float* score, int32_t* count, void* stream_)
-{
-    MRGS_MESH_ENTRY(mrgs_ref_score_launch(cfg, depth_v, normal_v, distance_v, image_v, cam_v, neighbours_dev, score, count, stream_, &launched));
-}
-
 // ---- introspection for the parity tests --------------------------------------------------------------
 __global__ void export_rec_kernel(int P, int which, const float4* __restrict__ rec, const uint8_t* __restrict__ clamped, void* dst)
 {

@@ -16,6 +16,7 @@
 #include "mrgs_internal.h"
 #include "mrgs_wave.h"
 #include "mrgs_philox.h"
+#include "mrgs_densify_common.h"
 
 namespace {
 
@@ -108,13 +109,6 @@ __global__ __launch_bounds__(1024) void densify_scan_kernel(int nblocks, const u
     }
 }
 
-struct EmitTable {
-    const float* src[MRGS_COMPACT_MAX_TENSORS];
-    float* dst[MRGS_COMPACT_MAX_TENSORS];
-    int row_floats[MRGS_COMPACT_MAX_TENSORS];
-    int role[MRGS_COMPACT_MAX_TENSORS];
-};
-
 struct EmitArgs {
     long long P;
     int N, nblocks;
@@ -133,15 +127,9 @@ __device__ __forceinline__ float child_centre(const EmitArgs& a, long long row, 
     float z0, z1;
     if (a.noise) { const float* z = a.noise + ((size_t)row * a.N + k) * 2; z0 = z[0]; z1 = z[1]; }
     else normal_pair(a.seed, row, k, z0, z1);
-    const float* q = a.rotation + 4 * (size_t)row;
-    const float nrm = sqrtf(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-    const float r = q[0] / nrm, x = q[1] / nrm, y = q[2] / nrm, z = q[3] / nrm;
-    float R0, R1;                                                       // R[col][0], R[col][1]
-    if (col == 0) { R0 = 1.0f - 2.0f * (y * y + z * z); R1 = 2.0f * (x * y - r * z); }
-    else if (col == 1) { R0 = 2.0f * (x * y + r * z); R1 = 1.0f - 2.0f * (x * x + z * z); }
-    else { R0 = 2.0f * (x * z - r * y); R1 = 2.0f * (y * z + r * x); }
+    const RotationRow2 R = rotation_row2(a.rotation + 4 * (size_t)row, col);
     const float sx = expf(a.scaling[2 * (size_t)row]) * z0, sy = expf(a.scaling[2 * (size_t)row + 1]) * z1;
-    return a.xyz[3 * (size_t)row + col] + (R0 * sx + R1 * sy);
+    return a.xyz[3 * (size_t)row + col] + (R.R0 * sx + R.R1 * sy);
 }
 
 __global__ __launch_bounds__(256) void densify_emit_kernel(EmitArgs a, const uint8_t* __restrict__ cls_in, const unsigned* __restrict__ block_off,
@@ -202,9 +190,7 @@ __global__ __launch_bounds__(256) void densify_stats_kernel(long long P, const f
 {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= P || !visible[i]) return;
-    const float gx = grad[3 * i], gy = grad[3 * i + 1], gz = grad[3 * i + 2];
-    accum[i] += sqrtf(gx * gx + gy * gy + gz * gz);
-    denom[i] += 1.0f;
+    densify_stats_row(grad, i, accum, denom);
     if (radii && max_radii) max_radii[i] = fmaxf(max_radii[i], (float)radii[i]);
 }
 
@@ -257,16 +243,7 @@ extern "C" int mrgs_densify_emit(const MrgsDensifyConfig* cfg, const void* ws, c
     const int64_t n_keep = counts_host[0], n_clone = counts_host[1], n_child = counts_host[2];
     if (n_keep < 0 || n_clone < 0 || n_child < 0 || n_keep > cfg->P || n_clone > cfg->P || n_child > cfg->P) return MRGS_E_BAD_ARG;
     const bool empty = n_keep + n_clone + n_child == 0;                  // every destination is empty: its pointer may be NULL
-    bool needs_xyz = false;
-    for (int32_t i = 0; i < n_tensors; ++i) {
-        const MrgsDensifyTensor& e = tensors[i];
-        if (e.row_floats < 0 || e.row_floats > (1 << 20) || e.role < MRGS_DENSIFY_COPY || e.role > MRGS_DENSIFY_SCALING) return MRGS_E_BAD_ARG;
-        if (e.row_floats == 0) continue;
-        if (!e.src || (!e.dst && !empty)) return MRGS_E_BAD_ARG;
-        if (e.role == MRGS_DENSIFY_XYZ) { if (e.row_floats != 3) return MRGS_E_BAD_ARG; needs_xyz = true; }
-        if (e.role == MRGS_DENSIFY_SCALING) { if (e.row_floats != 2) return MRGS_E_BAD_ARG; }
-    }
-    if (needs_xyz && (!cfg->xyz_raw || !cfg->scaling_raw || !cfg->rotation_raw)) return MRGS_E_BAD_ARG;
+    if (int rc = densify_check_tensors(tensors, n_tensors, empty, cfg->xyz_raw, cfg->scaling_raw, cfg->rotation_raw)) return rc;
     if (empty) return MRGS_OK;
     const long long nb = densify_blocks(cfg->P);
     const uint8_t* cls = (const uint8_t*)ws;
@@ -276,17 +253,9 @@ extern "C" int mrgs_densify_emit(const MrgsDensifyConfig* cfg, const void* ws, c
     a.n_keep = (unsigned)n_keep; a.n_clone = (unsigned)n_clone; a.n_child = (unsigned)n_child;
     a.child_div = (float)(0.8 * (double)cfg->N);
     a.xyz = cfg->xyz_raw; a.scaling = cfg->scaling_raw; a.rotation = cfg->rotation_raw; a.noise = noise; a.seed = seed;
-    for (int32_t first = 0; first < n_tensors; first += MRGS_COMPACT_MAX_TENSORS) {
-        EmitTable t;
-        int m = 0;
-        for (int32_t i = first; i < n_tensors && i < first + MRGS_COMPACT_MAX_TENSORS; ++i) {
-            if (tensors[i].row_floats == 0) continue;
-            t.src[m] = tensors[i].src; t.dst[m] = tensors[i].dst; t.row_floats[m] = tensors[i].row_floats; t.role[m] = tensors[i].role;
-            ++m;
-        }
-        if (m == 0) continue;
+    densify_emit_chunks(tensors, n_tensors, [&](const EmitTable& t, int m) {
         densify_emit_kernel<<<dim3((unsigned)nb, (unsigned)m), 256, 0, (hipStream_t)stream>>>(a, cls, offs, t);
-    }
+    });
     return MRGS_LAUNCH_STATUS();
 }
 

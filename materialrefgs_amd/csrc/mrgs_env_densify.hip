@@ -25,6 +25,7 @@
 #include "mrgs_internal.h"
 #include "mrgs_wave.h"
 #include "mrgs_philox.h"
+#include "mrgs_densify_common.h"
 
 namespace {
 
@@ -431,13 +432,6 @@ __global__ __launch_bounds__(1024) void env_scan_kernel(int nblocks, const unsig
 }
 
 // ---- emit ------------------------------------------------------------------------------------------------------------------------
-struct EmitTable {
-    const float* src[MRGS_COMPACT_MAX_TENSORS];
-    float* dst[MRGS_COMPACT_MAX_TENSORS];
-    int row_floats[MRGS_COMPACT_MAX_TENSORS];
-    int role[MRGS_COMPACT_MAX_TENSORS];
-};
-
 struct EmitArgs {
     long long P, n_rows;
     int nblocks;
@@ -449,26 +443,20 @@ struct EmitArgs {
 // R(normalize(q)) (s_x z0, s_y z1, 0) with the scale of the row it splits (env_gaussian_model.py:413-418, 435-441)
 __device__ __forceinline__ float entry_centre(const EmitArgs& a, long long row, int sigma, int j, int col)
 {
-    const float* q = a.rotation + 4 * (size_t)row;
-    const float nrm = sqrtf(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-    const float r = q[0] / nrm, x = q[1] / nrm, y = q[2] / nrm, z = q[3] / nrm;
-    float R0, R1;                                                       // R[col][0], R[col][1]
-    if (col == 0) { R0 = 1.0f - 2.0f * (y * y + z * z); R1 = 2.0f * (x * y - r * z); }
-    else if (col == 1) { R0 = 2.0f * (x * y + r * z); R1 = 1.0f - 2.0f * (x * x + z * z); }
-    else { R0 = 2.0f * (x * z - r * y); R1 = 2.0f * (y * z + r * x); }
+    const RotationRow2 R = rotation_row2(a.rotation + 4 * (size_t)row, col);
     float s0 = expf(a.scaling[2 * (size_t)row]), s1 = expf(a.scaling[2 * (size_t)row + 1]);
     float c = a.xyz[3 * (size_t)row + col], z0, z1;
     if (sigma >= 2) {
         const int k = sigma - 2;
         if (a.noise) { const float* n = a.noise + ((size_t)row * 2 + k) * 2; z0 = n[0]; z1 = n[1]; }
         else normal_pair(a.seed, row, k, z0, z1);
-        c = c + (R0 * (s0 * z0) + R1 * (s1 * z1));
+        c = c + (R.R0 * (s0 * z0) + R.R1 * (s1 * z1));
         s0 = expf(logf(s0 / DIV2)); s1 = expf(logf(s1 / DIV2));
     }
     if (j >= 0) {
         if (a.noise4) { const float* n = a.noise4 + (((size_t)row * 4 + sigma) * 5 + j) * 2; z0 = n[0]; z1 = n[1]; }
         else normal_pair(a.seed, row, j, z0, z1, 1u + (unsigned)sigma);
-        c = c + (R0 * (s0 * z0) + R1 * (s1 * z1));
+        c = c + (R.R0 * (s0 * z0) + R.R1 * (s1 * z1));
     }
     return c;
 }
@@ -530,9 +518,7 @@ __global__ __launch_bounds__(256) void env_stats_kernel(long long P, const float
 {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= P || !visible[i]) return;
-    const float gx = grad[3 * i], gy = grad[3 * i + 1], gz = grad[3 * i + 2];
-    accum[i] += sqrtf(gx * gx + gy * gy + gz * gz);
-    denom[i] += 1.0f;
+    densify_stats_row(grad, i, accum, denom);
     if (weight) weight_accum[i] += weight[i];
 }
 
@@ -584,10 +570,9 @@ extern "C" size_t mrgs_env_densify_ws_bytes(int64_t P)
     return env_carve(nullptr, P).total;
 }
 
-// The entry points' checks and launches; mrgs_api.hip reports the launches' status (*launched = something was queued).
-int mrgs_env_densify_classify_launch(const MrgsEnvDensifyConfig* cfg, const float* accum, const float* denom, const float* max_radii,
-                                     const float* weight_accum, const float* scaling_raw, const float* opacity_raw, void* ws, size_t ws_bytes,
-                                     int64_t* counts_dev, void* stream, bool* launched)
+extern "C" int mrgs_env_densify_classify(const MrgsEnvDensifyConfig* cfg, const float* accum, const float* denom, const float* max_radii,
+                                         const float* weight_accum, const float* scaling_raw, const float* opacity_raw, void* ws, size_t ws_bytes,
+                                         int64_t* counts_dev, void* stream)
 {
     if (int rc = env_check_cfg(cfg)) return rc;
     if (cfg->P == 0) return MRGS_OK;
@@ -601,7 +586,6 @@ int mrgs_env_densify_classify_launch(const MrgsEnvDensifyConfig* cfg, const floa
     a.world_limit = cfg->world_size_limit; a.screen_limit = cfg->max_screen_size; a.has_screen = (cfg->flags & MRGS_ENV_DENSIFY_SCREEN) ? 1 : 0;
     a.accum = accum; a.denom = denom; a.radii = max_radii; a.weight = weight_accum; a.scaling = scaling_raw; a.opacity = opacity_raw;
     const int rg = reduce_grid(P), nb = (int)env_blocks(P);
-    *launched = true;
     MRGS_HIP_TRY(hipMemsetAsync(ws, 0, HEAD_BYTES, st));
     env_w0_kernel<<<rg, 256, 0, st>>>(P, weight_accum, w.scal);
     env_w1_kernel<<<rg, 256, 0, st>>>(a, w.scal);
@@ -618,51 +602,33 @@ int mrgs_env_densify_classify_launch(const MrgsEnvDensifyConfig* cfg, const floa
     env_scan_kernel<<<1, 1024, 0, st>>>(nb, w.mat, w.off, w.scal, w.sel, nullptr);
     env_final_kernel<<<nb, 256, 0, st>>>(P, nb, w.rec, w.keys, w.sel, w.scal, w.off, w.mat);
     env_scan_kernel<<<1, 1024, 0, st>>>(nb, w.mat, w.off, w.scal, w.sel, (long long*)counts_dev);
-    *launched = true;
-    return MRGS_OK;
+    return MRGS_LAUNCH_STATUS();
 }
 
-int mrgs_env_densify_emit_launch(const MrgsEnvDensifyConfig* cfg, const void* ws, int64_t n_rows, const MrgsDensifyTensor* tensors,
-                                 int32_t n_tensors, uint64_t seed, const float* noise, const float* noise4, void* stream, bool* launched)
+extern "C" int mrgs_env_densify_emit(const MrgsEnvDensifyConfig* cfg, const void* ws, int64_t n_rows, const MrgsDensifyTensor* tensors,
+                                     int32_t n_tensors, uint64_t seed, const float* noise, const float* noise4, void* stream)
 {
     if (int rc = env_check_cfg(cfg)) return rc;
     if (n_tensors < 0 || (n_tensors > 0 && !tensors)) return MRGS_E_BAD_ARG;
     if (cfg->P == 0 || n_tensors == 0) return MRGS_OK;
     if (!ws || ((uintptr_t)ws & 255) || n_rows < 0 || n_rows > (int64_t)NENT * cfg->P) return MRGS_E_BAD_ARG;
     const bool empty = n_rows == 0;                                               // every destination is empty: its pointer may be NULL
-    bool needs_xyz = false;
-    for (int32_t i = 0; i < n_tensors; ++i) {
-        const MrgsDensifyTensor& e = tensors[i];
-        if (e.row_floats < 0 || e.row_floats > (1 << 20) || e.role < MRGS_DENSIFY_COPY || e.role > MRGS_DENSIFY_SCALING) return MRGS_E_BAD_ARG;
-        if (e.row_floats == 0) continue;
-        if (!e.src || (!e.dst && !empty)) return MRGS_E_BAD_ARG;
-        if (e.role == MRGS_DENSIFY_XYZ) { if (e.row_floats != 3) return MRGS_E_BAD_ARG; needs_xyz = true; }
-        if (e.role == MRGS_DENSIFY_SCALING) { if (e.row_floats != 2) return MRGS_E_BAD_ARG; }
-    }
-    if (needs_xyz && (!cfg->xyz_raw || !cfg->scaling_raw || !cfg->rotation_raw)) return MRGS_E_BAD_ARG;
+    if (int rc = densify_check_tensors(tensors, n_tensors, empty, cfg->xyz_raw, cfg->scaling_raw, cfg->rotation_raw)) return rc;
     if (empty) return MRGS_OK;
     const EnvWs w = env_carve(const_cast<void*>(ws), cfg->P);
     EmitArgs a;
     a.P = cfg->P; a.n_rows = n_rows; a.nblocks = (int)env_blocks(cfg->P);
     a.xyz = cfg->xyz_raw; a.scaling = cfg->scaling_raw; a.rotation = cfg->rotation_raw; a.noise = noise; a.noise4 = noise4; a.seed = seed;
-    for (int32_t first = 0; first < n_tensors; first += MRGS_COMPACT_MAX_TENSORS) {
-        EmitTable t;
-        int m = 0;
-        for (int32_t i = first; i < n_tensors && i < first + MRGS_COMPACT_MAX_TENSORS; ++i) {
-            if (tensors[i].row_floats == 0) continue;
-            t.src[m] = tensors[i].src; t.dst[m] = tensors[i].dst; t.row_floats[m] = tensors[i].row_floats; t.role[m] = tensors[i].role;
-            ++m;
-        }
-        if (m == 0) continue;
+    const bool any = densify_emit_chunks(tensors, n_tensors, [&](const EmitTable& t, int m) {
         env_emit_kernel<<<dim3((unsigned)a.nblocks, (unsigned)m), 256, 0, (hipStream_t)stream>>>(a, w.rec, w.off, t);
-        *launched = true;
-    }
-    return MRGS_OK;
+    });
+    if (!any) return MRGS_OK;                                                     // every tensor has empty rows: nothing was queued
+    return MRGS_LAUNCH_STATUS();
 }
 
 extern "C" size_t mrgs_env_select_ws_bytes(void) { return mrgs_align_up(SEL_BYTES, 256); }
 
-int mrgs_env_select_launch(int64_t n, const float* values, int64_t k, void* ws, size_t ws_bytes, uint32_t* out_dev, void* stream, bool* launched)
+extern "C" int mrgs_env_select(int64_t n, const float* values, int64_t k, void* ws, size_t ws_bytes, uint32_t* out_dev, void* stream)
 {
     if (n < 0 || n >= (1ll << 31) || k < 0 || (n > 0 && k >= n)) return MRGS_E_BAD_ARG;
     if (n == 0) return MRGS_OK;
@@ -670,21 +636,19 @@ int mrgs_env_select_launch(int64_t n, const float* values, int64_t k, void* ws, 
     hipStream_t st = (hipStream_t)stream;
     SelState* sel = (SelState*)ws;
     unsigned* hist = (unsigned*)((uint8_t*)ws + sizeof(SelState));
-    *launched = true;
     MRGS_HIP_TRY(hipMemsetAsync(ws, 0, SEL_BYTES, st));
     sel_set_kernel<<<1, 1, 0, st>>>(sel, (unsigned)k);
     launch_select((const unsigned*)values, n, sel, hist, st);
     sel_out_kernel<<<1, 1, 0, st>>>(sel, out_dev);
-    return MRGS_OK;
+    return MRGS_LAUNCH_STATUS();
 }
 
-int mrgs_env_densify_stats_launch(int64_t P, const float* grad, const uint8_t* visible, const float* weight_accumulate, float* accum,
-                                  float* denom, float* weight_accum, void* stream, bool* launched)
+extern "C" int mrgs_env_densify_stats(int64_t P, const float* grad, const uint8_t* visible, const float* weight_accumulate, float* accum,
+                                      float* denom, float* weight_accum, void* stream)
 {
     if (P < 0 || P >= (1ll << 31) * 256) return MRGS_E_BAD_ARG;
     if (P == 0) return MRGS_OK;
     if (!grad || !visible || !accum || !denom || (weight_accumulate && !weight_accum)) return MRGS_E_BAD_ARG;
     env_stats_kernel<<<dim3((unsigned)((P + 255) / 256)), 256, 0, (hipStream_t)stream>>>(P, grad, visible, weight_accumulate, accum, denom, weight_accum);
-    *launched = true;
-    return MRGS_OK;
+    return MRGS_LAUNCH_STATUS();
 }

@@ -181,41 +181,6 @@ void mrgs_launch_render_bwd(const MrgsRasterConfig& cfg, const MrgsRasterInputs&
                             const uint8_t* cflag, const MrgsImgWs& img, const float* dL_dpix, const float* dL_dpix_f, const float* dL_dothers,
                             float* grad_rec, bool forward_queues, hipStream_t stream);
 
-// reflection score (mrgs_multiview.hip): all argument checks, then the launch
-int mrgs_ref_score_launch(const MrgsRefScoreConfig* cfg, const float* depth_v, const float* normal_v, const float* distance_v,
-                          const float* image_v, const float* cam_v, const MrgsRefScoreNeighbour* neighbours_dev, float* score, int32_t* count,
-                          void* stream, bool* launched);
-
-// mesh extraction (mrgs_mesh.hip): all argument checks, then the launches; *launched = something was queued (mrgs_api.hip reports its status)
-int mrgs_tsdf_fuse_launch(const MrgsTsdfConfig* cfg, const MrgsTsdfView* views, float* field, float* weight_debug, void* stream, bool* launched);
-int mrgs_mesh_count_launch(const MrgsMeshConfig* cfg, const float* field, void* ws, size_t ws_bytes, int64_t* totals_dev, void* stream, bool* launched);
-int mrgs_mesh_emit_launch(const MrgsMeshConfig* cfg, const float* field, void* ws, size_t ws_bytes, const int64_t* totals_host, float* vertices,
-                          int32_t* triangles, void* stream, bool* launched);
-int mrgs_mesh_clusters_launch(int64_t V, int64_t T, const int32_t* triangles, int32_t* labels, int32_t* counts, void* stream, bool* launched);
-int mrgs_mesh_select_launch(int64_t V, int64_t T, const int32_t* triangles, const int32_t* labels, const int32_t* counts, int32_t threshold,
-                            uint8_t* keep_vertex, uint8_t* keep_triangle, void* stream, bool* launched);
-int mrgs_mesh_reindex_launch(int64_t V_old, int64_t V_new, const int32_t* new_to_old, int32_t* remap_ws, int64_t T, int32_t* triangles,
-                             void* stream, bool* launched);
-
-// per-pixel prior terms (mrgs_prior.hip): the same split
-int mrgs_prior_forward_launch(const MrgsPriorConfig* cfg, const float* Rt, const float* surf_normal, const float* rend_normal, const float* prior,
-                              const float* mask, const float* rend_alpha, const float* alpha_mask, const float* refl, const float* rough,
-                              const uint8_t* ref_score, void* ws, size_t ws_bytes, float* out_terms, void* stream, bool* launched);
-int mrgs_prior_backward_launch(const MrgsPriorConfig* cfg, const float* Rt, const float* surf_normal, const float* rend_normal, const float* prior,
-                               const float* mask, const float* rend_alpha, const float* alpha_mask, const float* refl, const float* rough,
-                               const uint8_t* ref_score, const float* fwd_terms, const float* const* g_terms, float* g_surf_normal,
-                               float* g_rend_normal, float* g_alpha, float* g_refl, float* g_rough, void* stream, bool* launched);
-
-// the environment set's policy (mrgs_env_densify.hip): the same split
-int mrgs_env_densify_classify_launch(const MrgsEnvDensifyConfig* cfg, const float* accum, const float* denom, const float* max_radii,
-                                     const float* weight_accum, const float* scaling_raw, const float* opacity_raw, void* ws, size_t ws_bytes,
-                                     int64_t* counts_dev, void* stream, bool* launched);
-int mrgs_env_densify_emit_launch(const MrgsEnvDensifyConfig* cfg, const void* ws, int64_t n_rows, const MrgsDensifyTensor* tensors,
-                                 int32_t n_tensors, uint64_t seed, const float* noise, const float* noise4, void* stream, bool* launched);
-int mrgs_env_select_launch(int64_t n, const float* values, int64_t k, void* ws, size_t ws_bytes, uint32_t* out_dev, void* stream, bool* launched);
-int mrgs_env_densify_stats_launch(int64_t P, const float* grad, const uint8_t* visible, const float* weight_accumulate, float* accum,
-                                  float* denom, float* weight_accum, void* stream, bool* launched);
-
 #ifndef MRGS_EXP
 #define MRGS_EXP(x) expf(x)
 #endif

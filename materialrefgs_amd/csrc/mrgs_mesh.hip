@@ -404,10 +404,7 @@ MeshArgs mesh_slab(const MrgsMeshConfig* cfg, int p0, const float* field, const 
 
 }   // namespace
 
-// The entry points' bodies: every check, then the launches; *launched says whether anything was queued.  The extern "C" halves, which
-// report the launch status, sit in mrgs_api.hip with the rasterizer's, whose kernels live in files of their own as well: the set of files
-// that report a launch status is pinned (tests/test_status.py keeps one failing call per such file).
-int mrgs_tsdf_fuse_launch(const MrgsTsdfConfig* cfg, const MrgsTsdfView* views, float* field, float* weight_debug, void* stream, bool* launched)
+extern "C" int mrgs_tsdf_fuse(const MrgsTsdfConfig* cfg, const MrgsTsdfView* views, float* field, float* weight_debug, void* stream)
 {
     if (!cfg || cfg->struct_size != sizeof(MrgsTsdfConfig)) return MRGS_E_BAD_ARG;
     if (cfg->mode < MRGS_TSDF_CONTRACTED || cfg->mode > MRGS_TSDF_POINTS || cfg->n_views < 0 || !(cfg->trunc > 0.0f)) return MRGS_E_BAD_ARG;
@@ -428,8 +425,7 @@ int mrgs_tsdf_fuse_launch(const MrgsTsdfConfig* cfg, const MrgsTsdfView* views, 
     for (int ax = 0; ax < 3; ++ax) { a.origin[ax] = cfg->origin[ax]; a.spacing[ax] = cfg->spacing[ax]; a.center[ax] = cfg->center[ax]; }
     a.radius = cfg->radius; a.trunc = cfg->trunc; a.depth_trunc = cfg->depth_trunc; a.points = cfg->points;
     tsdf_fuse_kernel<<<dim3(blocks256(n)), 256, 0, (hipStream_t)stream>>>(a, views, field, weight_debug);
-    *launched = true;
-    return MRGS_OK;
+    return MRGS_LAUNCH_STATUS();
 }
 
 extern "C" size_t mrgs_mesh_ws_bytes(const MrgsMeshConfig* cfg)
@@ -438,7 +434,7 @@ extern "C" size_t mrgs_mesh_ws_bytes(const MrgsMeshConfig* cfg)
     return mesh_carve(nullptr, slab_points_max(cfg)).total;
 }
 
-int mrgs_mesh_count_launch(const MrgsMeshConfig* cfg, const float* field, void* ws, size_t ws_bytes, int64_t* totals_dev, void* stream, bool* launched)
+extern "C" int mrgs_mesh_count(const MrgsMeshConfig* cfg, const float* field, void* ws, size_t ws_bytes, int64_t* totals_dev, void* stream)
 {
     if (int rc = mesh_check_cfg(cfg)) return rc;
     if (!field || !ws || ((uintptr_t)ws & 7) || !totals_dev) return MRGS_E_BAD_ARG;
@@ -446,12 +442,11 @@ int mrgs_mesh_count_launch(const MrgsMeshConfig* cfg, const float* field, void* 
     hipStream_t st = (hipStream_t)stream;
     const MeshWs w = mesh_carve(ws, slab_points_max(cfg));
     for (int p0 = 0; p0 < cfg->n0 - 1; p0 += cfg->slab_planes) mesh_slab(cfg, p0, field, w, (long long*)totals_dev, nullptr, st);
-    *launched = true;
-    return MRGS_OK;
+    return MRGS_LAUNCH_STATUS();
 }
 
-int mrgs_mesh_emit_launch(const MrgsMeshConfig* cfg, const float* field, void* ws, size_t ws_bytes, const int64_t* totals_host,
-                          float* vertices, int32_t* triangles, void* stream, bool* launched)
+extern "C" int mrgs_mesh_emit(const MrgsMeshConfig* cfg, const float* field, void* ws, size_t ws_bytes, const int64_t* totals_host,
+                              float* vertices, int32_t* triangles, void* stream)
 {
     if (int rc = mesh_check_cfg(cfg)) return rc;
     if (!totals_host) return MRGS_E_BAD_ARG;
@@ -467,11 +462,10 @@ int mrgs_mesh_emit_launch(const MrgsMeshConfig* cfg, const float* field, void* w
         const MeshArgs a = mesh_slab(cfg, p0, field, w, w.run, w.slab_base, st);
         mesh_emit_kernel<<<dim3((unsigned)a.nblocks), 256, 0, st>>>(a, field, w.words, w.offs, w.slab_base, vertices, triangles);
     }
-    *launched = true;
-    return MRGS_OK;
+    return MRGS_LAUNCH_STATUS();
 }
 
-int mrgs_mesh_clusters_launch(int64_t V, int64_t T, const int32_t* triangles, int32_t* labels, int32_t* counts, void* stream, bool* launched)
+extern "C" int mrgs_mesh_clusters(int64_t V, int64_t T, const int32_t* triangles, int32_t* labels, int32_t* counts, void* stream)
 {
     if (V < 0 || T < 0) return MRGS_E_BAD_ARG;
     if (V > 0x7FFFFFFFll || T > 0x7FFFFFFFll) return MRGS_E_UNSUPPORTED;
@@ -482,12 +476,11 @@ int mrgs_mesh_clusters_launch(int64_t V, int64_t T, const int32_t* triangles, in
     if (T > 0) cc_hook_kernel<<<dim3(blocks256(T)), 256, 0, st>>>(T, V, triangles, labels);
     cc_flatten_kernel<<<dim3(blocks256(V)), 256, 0, st>>>(V, labels);
     if (T > 0) cc_count_kernel<<<dim3(blocks256(T)), 256, 0, st>>>(T, V, triangles, labels, counts);
-    *launched = true;
-    return MRGS_OK;
+    return MRGS_LAUNCH_STATUS();
 }
 
-int mrgs_mesh_select_launch(int64_t V, int64_t T, const int32_t* triangles, const int32_t* labels, const int32_t* counts, int32_t threshold,
-                            uint8_t* keep_vertex, uint8_t* keep_triangle, void* stream, bool* launched)
+extern "C" int mrgs_mesh_select(int64_t V, int64_t T, const int32_t* triangles, const int32_t* labels, const int32_t* counts, int32_t threshold,
+                                uint8_t* keep_vertex, uint8_t* keep_triangle, void* stream)
 {
     if (V < 0 || T < 0) return MRGS_E_BAD_ARG;
     if (V > 0x7FFFFFFFll || T > 0x7FFFFFFFll) return MRGS_E_UNSUPPORTED;
@@ -495,12 +488,11 @@ int mrgs_mesh_select_launch(int64_t V, int64_t T, const int32_t* triangles, cons
     if (!labels || !counts || (V > 0 && !keep_vertex) || (T > 0 && (!triangles || !keep_triangle)) || (V == 0 && T > 0)) return MRGS_E_BAD_ARG;
     mesh_select_kernel<<<dim3(blocks256(V > T ? V : T)), 256, 0, (hipStream_t)stream>>>(V, T, triangles, labels, counts, threshold, keep_vertex,
                                                                                          keep_triangle);
-    *launched = true;
-    return MRGS_OK;
+    return MRGS_LAUNCH_STATUS();
 }
 
-int mrgs_mesh_reindex_launch(int64_t V_old, int64_t V_new, const int32_t* new_to_old, int32_t* remap_ws, int64_t T, int32_t* triangles,
-                             void* stream, bool* launched)
+extern "C" int mrgs_mesh_reindex(int64_t V_old, int64_t V_new, const int32_t* new_to_old, int32_t* remap_ws, int64_t T, int32_t* triangles,
+                                 void* stream)
 {
     if (V_old < 0 || V_new < 0 || T < 0 || V_new > V_old) return MRGS_E_BAD_ARG;
     if (V_old > 0x7FFFFFFFll || T > 0x7FFFFFFFll) return MRGS_E_UNSUPPORTED;
@@ -509,6 +501,5 @@ int mrgs_mesh_reindex_launch(int64_t V_old, int64_t V_new, const int32_t* new_to
     hipStream_t st = (hipStream_t)stream;
     mesh_remap_kernel<<<dim3(blocks256(V_new)), 256, 0, st>>>(V_new, V_old, new_to_old, remap_ws);
     mesh_reindex_kernel<<<dim3(blocks256(3 * T)), 256, 0, st>>>(3 * T, V_old, remap_ws, triangles);
-    *launched = true;
-    return MRGS_OK;
+    return MRGS_LAUNCH_STATUS();
 }

@@ -1166,10 +1166,9 @@ __global__ __launch_bounds__(64) void ref_score_fwd(RefArgs r, const float* __re
 
 }   // namespace
 
-// every check, then the launch (the extern "C" half, which reports the launch status, is in mrgs_api.hip)
-int mrgs_ref_score_launch(const MrgsRefScoreConfig* cfg, const float* depth_v, const float* normal_v, const float* distance_v,
-                          const float* image_v, const float* cam_v, const MrgsRefScoreNeighbour* neighbours_dev, float* score, int32_t* count,
-                          void* stream, bool* launched)
+extern "C" int mrgs_ref_score(const MrgsRefScoreConfig* cfg, const float* depth_v, const float* normal_v, const float* distance_v,
+                              const float* image_v, const float* cam_v, const MrgsRefScoreNeighbour* neighbours_dev, float* score, int32_t* count,
+                              void* stream)
 {
     if (!cfg || cfg->struct_size != sizeof(MrgsRefScoreConfig)) return MRGS_E_BAD_ARG;
     if (cfg->H <= 0 || cfg->W <= 0 || (int64_t)cfg->H * cfg->W >= ((int64_t)1 << 30)) return MRGS_E_BAD_ARG;
@@ -1185,6 +1184,5 @@ int mrgs_ref_score_launch(const MrgsRefScoreConfig* cfg, const float* depth_v, c
     r.th = cfg->pixel_noise_th;
     const int64_t nblk = (int64_t)((r.W + RS_B - 1) / RS_B) * ((r.H + RS_B - 1) / RS_B);      // < 2^30
     ref_score_fwd<<<(unsigned)nblk, 64, 0, (hipStream_t)stream>>>(r, depth_v, normal_v, distance_v, image_v, cam_v, neighbours_dev, score, count);
-    *launched = true;
-    return MRGS_OK;
+    return MRGS_LAUNCH_STATUS();
 }

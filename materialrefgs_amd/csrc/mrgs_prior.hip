@@ -389,10 +389,9 @@ extern "C" size_t mrgs_prior_ws_bytes(int32_t H, int32_t W)
     return (size_t)prior_blocks((int64_t)H * W) * ROW * sizeof(float);
 }
 
-// all argument checks, then the launches; *launched = something was queued (mrgs_api.hip holds the entry points and reports the status)
-int mrgs_prior_forward_launch(const MrgsPriorConfig* cfg, const float* Rt, const float* surf_normal, const float* rend_normal, const float* prior,
-                              const float* mask, const float* rend_alpha, const float* alpha_mask, const float* refl, const float* rough,
-                              const uint8_t* ref_score, void* ws, size_t ws_bytes, float* out_terms, void* stream, bool* launched)
+extern "C" int mrgs_prior_terms_forward(const MrgsPriorConfig* cfg, const float* Rt, const float* surf_normal, const float* rend_normal,
+                                        const float* prior, const float* mask, const float* rend_alpha, const float* alpha_mask, const float* refl,
+                                        const float* rough, const uint8_t* ref_score, void* ws, size_t ws_bytes, float* out_terms, void* stream)
 {
     PriorMaps a;
     if (int rc = make_maps(cfg, Rt, surf_normal, rend_normal, prior, mask, rend_alpha, alpha_mask, refl, rough, ref_score, a)) return rc;
@@ -401,14 +400,13 @@ int mrgs_prior_forward_launch(const MrgsPriorConfig* cfg, const float* Rt, const
     hipStream_t st = (hipStream_t)stream;
     prior_terms_fwd<<<nblocks, 256, 0, st>>>(a, (float*)ws);
     prior_terms_finalize<<<1, 256, 0, st>>>(a, (const float*)ws, nblocks, out_terms);
-    *launched = true;
-    return MRGS_OK;
+    return MRGS_LAUNCH_STATUS();
 }
 
-int mrgs_prior_backward_launch(const MrgsPriorConfig* cfg, const float* Rt, const float* surf_normal, const float* rend_normal, const float* prior,
-                               const float* mask, const float* rend_alpha, const float* alpha_mask, const float* refl, const float* rough,
-                               const uint8_t* ref_score, const float* fwd_terms, const float* const* g_terms, float* g_surf_normal,
-                               float* g_rend_normal, float* g_alpha, float* g_refl, float* g_rough, void* stream, bool* launched)
+extern "C" int mrgs_prior_terms_backward(const MrgsPriorConfig* cfg, const float* Rt, const float* surf_normal, const float* rend_normal,
+                                         const float* prior, const float* mask, const float* rend_alpha, const float* alpha_mask, const float* refl,
+                                         const float* rough, const uint8_t* ref_score, const float* fwd_terms, const float* const* g_terms,
+                                         float* g_surf_normal, float* g_rend_normal, float* g_alpha, float* g_refl, float* g_rough, void* stream)
 {
     PriorMaps a;
     if (int rc = make_maps(cfg, Rt, surf_normal, rend_normal, prior, mask, rend_alpha, alpha_mask, refl, rough, ref_score, a)) return rc;
@@ -425,6 +423,5 @@ int mrgs_prior_backward_launch(const MrgsPriorConfig* cfg, const float* Rt, cons
     u.live_alpha = g_alpha && u.g[4];
     u.live_ref = (g_refl || g_rough) && (u.g[5] || u.g[6] || u.g[7] || u.g[8] || u.g[12]);
     prior_terms_bwd<<<prior_blocks(a.N), 256, 0, (hipStream_t)stream>>>(a, u);
-    *launched = true;
-    return MRGS_OK;
+    return MRGS_LAUNCH_STATUS();
 }

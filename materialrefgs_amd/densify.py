@@ -144,14 +144,68 @@ def group_attr(name: str) -> str:
     return GROUP_ATTRS.get(name, "_" + name)
 
 
-def _device_f32(t, what, shape=None):
+def device_f32(t, what, shape=None, who="densify"):
+    """`t` if it is a float32 device tensor (of `shape`); `who`: the module whose name the message carries."""
     if not torch.is_tensor(t) or not t.is_cuda:
-        raise RuntimeError(f"materialrefgs_amd.densify: {what} must be a device tensor (libmrgs.so has no CPU path)")
+        raise RuntimeError(f"materialrefgs_amd.{who}: {what} must be a device tensor (libmrgs.so has no CPU path)")
     if t.dtype is not torch.float32:
-        raise TypeError(f"materialrefgs_amd.densify: {what} must be float32, got {t.dtype}")
+        raise TypeError(f"materialrefgs_amd.{who}: {what} must be float32, got {t.dtype}")
     if shape is not None and tuple(t.shape) != tuple(shape):
-        raise ValueError(f"materialrefgs_amd.densify: {what} must have shape {tuple(shape)}, got {tuple(t.shape)}")
+        raise ValueError(f"materialrefgs_amd.{who}: {what} must have shape {tuple(shape)}, got {tuple(t.shape)}")
     return t
+
+
+def emit_sources(optimizer, groups, P, dev, who="densify"):
+    """What an emit pass reads, for both models: (src, slots, data) -- every group's parameter and, where the optimizer has stepped, its
+    two moments, contiguous; one slot (group, "param" | "exp_avg" | "exp_avg_sq", role) per source; {group name: parameter data}."""
+    src, slots, data = [], [], {}
+    for g in groups:
+        p = g["params"][0]
+        device_f32(p, f"parameter '{g['name']}'", who=who)
+        if p.shape[0] != P or p.device != dev:
+            raise ValueError(f"densify_and_prune: parameter '{g['name']}' does not share dim 0 / the device with xyz")
+        src.append(p.detach().contiguous()); slots.append((g, "param", _ROLES.get(g["name"], _lib.MRGS_DENSIFY_COPY)))
+        data[g["name"]] = src[-1]
+        st = optimizer.state.get(p, None)
+        if st is not None and "exp_avg" in st:
+            for kind in ("exp_avg", "exp_avg_sq"):
+                src.append(device_f32(st[kind], f"{kind} of '{g['name']}'", p.shape, who).contiguous())
+                slots.append((g, kind, _lib.MRGS_DENSIFY_MOMENT))
+    for name, width in (("xyz", 3), ("scaling", 2), ("rotation", 4), ("opacity", 1)):
+        device_f32(data[name], name, (P, width), who)
+    return src, slots, data
+
+
+def draw_seed(seed, needed=True):
+    """The 64-bit key of the split offsets' generator; None with `needed` draws it from torch's CPU default generator (no device sync)."""
+    if seed is None and needed:
+        seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
+    return int(seed or 0) & 0xFFFFFFFFFFFFFFFF
+
+
+def emit_and_install(optimizer, groups, src, slots, m, emit_call):
+    """The emit pass of both models: allocates one m-row output per source, hands emit_call(tensors, n_tensors) the MrgsDensifyTensor
+    list (it returns the library's status) and puts the outputs into the optimizer.  Returns {group name: parameter}."""
+    P, dev = int(src[0].shape[0]), src[0].device
+    out = [torch.empty((m,) + tuple(t.shape[1:]), dtype=t.dtype, device=dev) for t in src]
+    arr = (_lib.MrgsDensifyTensor * len(src))()
+    for i, (s, d, slot) in enumerate(zip(src, out, slots)):
+        arr[i] = _lib.MrgsDensifyTensor(s.data_ptr(), d.data_ptr(), int(s.numel() // P), slot[2])
+    _lib.check(emit_call(arr, len(src)))
+    return _install(optimizer, groups, slots, out)
+
+
+def stats_args(grad, update_filter, stats, who="densify"):
+    """The checks both add_densification_stats share.  stats: ((tensor, name), ...), accum first.  Returns (P, grad, filter as uint8)."""
+    P = int(stats[0][0].shape[0])
+    grad = device_f32(grad, "the view-space gradient", (P, 3), who).contiguous()
+    for t, what in stats:
+        device_f32(t, what, who=who)
+        if t.numel() != P or not t.is_contiguous():
+            raise ValueError(f"add_densification_stats: {what} must be a contiguous [P,1] tensor")
+    if not update_filter.is_cuda or update_filter.dtype not in (torch.bool, torch.uint8) or tuple(update_filter.shape) != (P,):
+        raise ValueError("add_densification_stats: update_filter must be a device bool / uint8 tensor of shape [P]")
+    return P, grad, update_filter.contiguous().view(torch.uint8)
 
 
 def densify_and_prune(model, max_grad, min_opacity, extent, max_screen_size, *, N=2, seed=None, noise=None):
@@ -190,30 +244,15 @@ def densify_and_prune(model, max_grad, min_opacity, extent, max_screen_size, *, 
     by_name = {g["name"]: g["params"][0] for g in groups}
     P = int(by_name["xyz"].shape[0])
     dev = by_name["xyz"].device
-    src, slots, data = [], [], {}
-    for g in groups:
-        p = g["params"][0]
-        _device_f32(p, f"parameter '{g['name']}'")
-        if p.shape[0] != P or p.device != dev:
-            raise ValueError(f"densify_and_prune: parameter '{g['name']}' does not share dim 0 / the device with xyz")
-        src.append(p.detach().contiguous()); slots.append((g, "param", _ROLES.get(g["name"], _lib.MRGS_DENSIFY_COPY)))
-        data[g["name"]] = src[-1]
-        st = optimizer.state.get(p, None)
-        if st is not None and "exp_avg" in st:
-            for kind in ("exp_avg", "exp_avg_sq"):
-                src.append(_device_f32(st[kind], f"{kind} of '{g['name']}'", p.shape).contiguous())
-                slots.append((g, kind, _lib.MRGS_DENSIFY_MOMENT))
+    src, slots, data = emit_sources(optimizer, groups, P, dev)
     xyz, scaling, rotation, opacity = data["xyz"], data["scaling"], data["rotation"], data["opacity"]
-    _device_f32(xyz, "xyz", (P, 3)); _device_f32(scaling, "scaling", (P, 2)); _device_f32(rotation, "rotation", (P, 4)); _device_f32(opacity, "opacity", (P, 1))
-    accum = _device_f32(model.xyz_gradient_accum, "xyz_gradient_accum").contiguous()
-    denom = _device_f32(model.denom, "denom").contiguous()
+    accum = device_f32(model.xyz_gradient_accum, "xyz_gradient_accum").contiguous()
+    denom = device_f32(model.denom, "denom").contiguous()
     if accum.numel() != P or denom.numel() != P:
         raise ValueError("densify_and_prune: xyz_gradient_accum and denom must hold one value per row")
     if noise is not None:
-        noise = _device_f32(noise, "noise", (P, N, 2)).contiguous()
-    elif seed is None:
-        seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())       # CPU default generator: no device sync
-    seed = int(seed or 0) & 0xFFFFFFFFFFFFFFFF
+        noise = device_f32(noise, "noise", (P, N, 2)).contiguous()
+    seed = draw_seed(seed, needed=noise is None)
     counts = (0, 0, 0)
     if P > 0:
         lib = _lib.lib()
@@ -226,14 +265,10 @@ def densify_and_prune(model, max_grad, min_opacity, extent, max_screen_size, *, 
             _lib.check(lib.mrgs_densify_classify(ctypes.byref(cfg), accum.data_ptr(), denom.data_ptr(), scaling.data_ptr(), opacity.data_ptr(),
                                                  ws.data_ptr(), ws.numel(), cnt.data_ptr(), stream))
             counts = tuple(int(c) for c in cnt.tolist())             # the one host read of the whole operation
-            m = counts[0] + counts[1] + N * counts[2]
-            out = [torch.empty((m,) + tuple(t.shape[1:]), dtype=t.dtype, device=dev) for t in src]
-            arr = (_lib.MrgsDensifyTensor * len(src))()
-            for i, (s, d, slot) in enumerate(zip(src, out, slots)):
-                arr[i] = _lib.MrgsDensifyTensor(s.data_ptr(), d.data_ptr(), int(s.numel() // P), slot[2])
             host = (_lib.c_int64 * 3)(*counts)
-            _lib.check(lib.mrgs_densify_emit(ctypes.byref(cfg), ws.data_ptr(), host, arr, len(src), seed, _lib.ptr(noise), stream))
-        for name, p in _install(optimizer, groups, slots, out).items():
+            new = emit_and_install(optimizer, groups, src, slots, counts[0] + counts[1] + N * counts[2], lambda arr, n: lib.mrgs_densify_emit(
+                ctypes.byref(cfg), ws.data_ptr(), host, arr, n, seed, _lib.ptr(noise), stream))
+        for name, p in new.items():
             setattr(model, group_attr(name), p)
     rows = counts[0] + counts[1] + N * counts[2]
     model.xyz_gradient_accum = torch.zeros((rows, 1), device=dev)
@@ -260,20 +295,12 @@ def add_densification_stats(model_or_tensors, viewspace_point_tensor, update_fil
     grad = viewspace_point_tensor.grad if viewspace_point_tensor.grad is not None else viewspace_point_tensor
     if grad.requires_grad:
         raise RuntimeError("add_densification_stats: viewspace_point_tensor has no .grad yet (call it after backward())")
-    P = int(accum.shape[0])
-    grad = _device_f32(grad, "the view-space gradient", (P, 3)).contiguous()
+    P, grad, vis = stats_args(grad, update_filter, ((accum, "xyz_gradient_accum"), (denom, "denom")))
     dev = grad.device
-    for t, what in ((accum, "xyz_gradient_accum"), (denom, "denom")):
-        _device_f32(t, what)
-        if t.numel() != P or not t.is_contiguous():
-            raise ValueError(f"add_densification_stats: {what} must be a contiguous [P,1] tensor")
-    if not update_filter.is_cuda or update_filter.dtype not in (torch.bool, torch.uint8) or tuple(update_filter.shape) != (P,):
-        raise ValueError("add_densification_stats: update_filter must be a device bool / uint8 tensor of shape [P]")
-    vis = update_filter.contiguous().view(torch.uint8)
     if radii is not None:
         if max_radii is None:
             raise ValueError("add_densification_stats: radii given but there is no max_radii2D to update")
-        _device_f32(max_radii, "max_radii2D", (P,))
+        device_f32(max_radii, "max_radii2D", (P,))
         if not radii.is_cuda or radii.dtype is not torch.int32 or tuple(radii.shape) != (P,) or not max_radii.is_contiguous():
             raise ValueError("add_densification_stats: radii must be a device int32 tensor of shape [P] and max_radii2D contiguous")
         radii = radii.contiguous()

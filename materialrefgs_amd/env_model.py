@@ -19,7 +19,6 @@ from .gs_utils import RGB2SH, build_scaling_rotation, flip_align_view, safe_norm
 GROUP_ATTRS = {"xyz": "_xyz", "f_dc": "_features_dc", "f_rest": "_features_rest", "opacity": "_opacity", "scaling": "_scaling",
                "rotation": "_rotation"}
 STATS = ("xyz_gradient_accum", "xyz_weight_accum", "denom", "max_radii2D")
-_ROLES = {"xyz": _lib.MRGS_DENSIFY_XYZ, "scaling": _lib.MRGS_DENSIFY_SCALING}
 _SLOTS = ("original", "clone", "child0", "child1")
 
 
@@ -41,13 +40,7 @@ def expon_lr_func(lr_init, lr_final, lr_delay_steps=0, lr_delay_mult=1.0, max_st
 
 
 def _device_f32(t, what, shape=None):
-    if not torch.is_tensor(t) or not t.is_cuda:
-        raise RuntimeError(f"materialrefgs_amd.env_model: {what} must be a device tensor (libmrgs.so has no CPU path)")
-    if t.dtype is not torch.float32:
-        raise TypeError(f"materialrefgs_amd.env_model: {what} must be float32, got {t.dtype}")
-    if shape is not None and tuple(t.shape) != tuple(shape):
-        raise ValueError(f"materialrefgs_amd.env_model: {what} must have shape {tuple(shape)}, got {tuple(t.shape)}")
-    return t
+    return densify.device_f32(t, what, shape, who="env_model")
 
 
 def select_kth(values, k):
@@ -71,16 +64,9 @@ def select_kth(values, k):
 def add_densification_stats(accum, denom, weight_accum, grad, update_filter, weight_accumulate=None):
     """For rows with the filter set: accum += ||grad[0:3]||_2, denom += 1, weight_accum += weight_accumulate (skipped when None).  In
     place, one launch, nothing read back."""
-    P = int(accum.shape[0])
-    grad = _device_f32(grad, "the view-space gradient", (P, 3)).contiguous()
+    P, grad, vis = densify.stats_args(grad, update_filter, ((accum, "xyz_gradient_accum"), (denom, "denom"), (weight_accum, "xyz_weight_accum")),
+                                      who="env_model")
     dev = grad.device
-    for t, what in ((accum, "xyz_gradient_accum"), (denom, "denom"), (weight_accum, "xyz_weight_accum")):
-        _device_f32(t, what)
-        if t.numel() != P or not t.is_contiguous():
-            raise ValueError(f"add_densification_stats: {what} must be a contiguous [P,1] tensor")
-    if not update_filter.is_cuda or update_filter.dtype not in (torch.bool, torch.uint8) or tuple(update_filter.shape) != (P,):
-        raise ValueError("add_densification_stats: update_filter must be a device bool / uint8 tensor of shape [P]")
-    vis = update_filter.contiguous().view(torch.uint8)
     if weight_accumulate is not None:
         weight_accumulate = _device_f32(weight_accumulate, "weight_accumulate").detach().contiguous()
         if weight_accumulate.numel() != P:
@@ -284,21 +270,8 @@ class EnvGaussianModel:
             raise ValueError("densify_and_prune: the optimizer must hold the six groups of training_setup")
         P = int(self._xyz.shape[0])
         dev = self._xyz.device
-        src, slots, data = [], [], {}
-        for g in groups:
-            p = g["params"][0]
-            _device_f32(p, f"parameter '{g['name']}'")
-            if p.shape[0] != P or p.device != dev:
-                raise ValueError(f"densify_and_prune: parameter '{g['name']}' does not share dim 0 / the device with xyz")
-            src.append(p.detach().contiguous()); slots.append((g, "param", _ROLES.get(g["name"], _lib.MRGS_DENSIFY_COPY)))
-            data[g["name"]] = src[-1]
-            st = optimizer.state.get(p, None)
-            if st is not None and "exp_avg" in st:
-                for kind in ("exp_avg", "exp_avg_sq"):
-                    src.append(_device_f32(st[kind], f"{kind} of '{g['name']}'", p.shape).contiguous())
-                    slots.append((g, kind, _lib.MRGS_DENSIFY_MOMENT))
+        src, slots, data = densify.emit_sources(optimizer, groups, P, dev, who="env_model")
         xyz, scaling, rotation, opacity = data["xyz"], data["scaling"], data["rotation"], data["opacity"]
-        _device_f32(xyz, "xyz", (P, 3)); _device_f32(scaling, "scaling", (P, 2)); _device_f32(rotation, "rotation", (P, 4)); _device_f32(opacity, "opacity", (P, 1))
         stats = []
         for s in STATS:
             t = _device_f32(getattr(self, s), s).contiguous()
@@ -310,9 +283,7 @@ class EnvGaussianModel:
             noise = _device_f32(noise, "noise", (P, 2, 2)).contiguous()
         if noise4 is not None:
             noise4 = _device_f32(noise4, "noise4", (P, 4, 5, 2)).contiguous()
-        if seed is None and (noise is None or noise4 is None):
-            seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())       # CPU default generator: no device sync
-        seed = int(seed or 0) & 0xFFFFFFFFFFFFFFFF
+        seed = densify.draw_seed(seed, needed=noise is None or noise4 is None)
         raw = [0] * _lib.MRGS_ENV_DENSIFY_COUNTS
         if P > 0:
             lib = _lib.lib()
@@ -327,13 +298,9 @@ class EnvGaussianModel:
                 _lib.check(lib.mrgs_env_densify_classify(ctypes.byref(cfg), accum.data_ptr(), denom.data_ptr(), radii.data_ptr(), weight.data_ptr(),
                                                          scaling.data_ptr(), opacity.data_ptr(), ws.data_ptr(), ws.numel(), cnt.data_ptr(), stream))
                 raw = [int(c) for c in cnt.tolist()]                       # the one host read of the whole operation
-                m = raw[24]
-                out = [torch.empty((m,) + tuple(t.shape[1:]), dtype=t.dtype, device=dev) for t in src]
-                arr = (_lib.MrgsDensifyTensor * len(src))()
-                for i, (s, d, slot) in enumerate(zip(src, out, slots)):
-                    arr[i] = _lib.MrgsDensifyTensor(s.data_ptr(), d.data_ptr(), int(s.numel() // P), slot[2])
-                _lib.check(lib.mrgs_env_densify_emit(ctypes.byref(cfg), ws.data_ptr(), m, arr, len(src), seed, _lib.ptr(noise), _lib.ptr(noise4), stream))
-            for name, p in densify._install(optimizer, groups, slots, out).items():
+                new = densify.emit_and_install(optimizer, groups, src, slots, raw[24], lambda arr, n: lib.mrgs_env_densify_emit(
+                    ctypes.byref(cfg), ws.data_ptr(), raw[24], arr, n, seed, _lib.ptr(noise), _lib.ptr(noise4), stream))
+            for name, p in new.items():
                 setattr(self, GROUP_ATTRS[name], p)
         self.reset_stats()
         return _counts(raw)

@@ -40,7 +40,7 @@ class PriorTerms(NamedTuple):
 
 
 def _map_f32(t, what, shapes):
-    """A rendered map: a float32 tensor of one of `shapes` (checked in the style of densify._device_f32; dtype and shape of every map
+    """A rendered map: a float32 tensor of one of `shapes` (checked in the style of densify.device_f32; dtype and shape of every map
     first, then `_on_device`, so that the message names the first thing a caller has to change)."""
     if not torch.is_tensor(t):
         raise TypeError(f"materialrefgs_amd.priors: {what} must be a tensor, got {type(t).__name__}")

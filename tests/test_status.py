@@ -37,6 +37,12 @@ def _ncc_backward(L):
     return L.mrgs_warp_ncc_backward(ctypes.byref(cfg), P, P, 1.0, P, P, P, None)
 
 
+def _prior_terms(L):
+    from materialrefgs_amd._lib import MrgsPriorConfig
+    cfg = MrgsPriorConfig(8, 8, 0)          # the alpha group alone: rend_alpha and alpha_mask
+    return L.mrgs_prior_terms_forward(ctypes.byref(cfg), None, None, None, None, None, P, P, None, None, None, P, L.mrgs_prior_ws_bytes(8, 8), P, None)
+
+
 # one well-formed call per translation unit that has launch entry points: file -> call(L) -> status
 CALLS = {
     "mrgs_api": lambda L: L.mrgs_mark_visible(4, P, P, P, P, None),
@@ -50,6 +56,9 @@ CALLS = {
     "mrgs_bvh": lambda L: L.mrgs_bvh_trace(P, 4, 4, P, P, P, P, P, P, None),
     "mrgs_knn": lambda L: L.mrgs_knn_mean_dist2(P, 64, P, P, L.mrgs_knn_ws_bytes(64), None),
     "mrgs_densify": lambda L: L.mrgs_densify_stats(4, *([P] * 6), None),
+    "mrgs_env_densify": lambda L: L.mrgs_env_densify_stats(4, P, P, None, P, P, None, None),
+    "mrgs_mesh": lambda L: L.mrgs_mesh_select(4, 0, None, P, P, 1, P, None, None),
+    "mrgs_prior": _prior_terms,
     "mrgs_optim": lambda L: L.mrgs_compact_count(0, P, P, L.mrgs_compact_ws_bytes(0), P, None),
     "mrgs_cubemapenc": lambda L: L.mrgs_cubemap_encode_forward(P, P, P, P, 0, 0, 4, 3, 1, None),
 }
