@@ -5,7 +5,8 @@
 // host sync each, 16 repeat()s and 16 cat()s twice over).  Everything those stages decide follows per SOURCE row from five numbers
 // (accum, denom, two raw scalings, raw opacity), so here they are two passes:
 //   classify  one thread per row, 1024 rows per workgroup: a class byte per row (bit 0 keep the original, bit 1 emit a clone, bit 2
-//             emit N children), per-block counts of the three output segments, then a one-workgroup scan into per-block offsets and
+//             emit N children), per-block counts of the three output segments, then one workgroup scans each segment's counts
+//             (block_counts_exclusive_scan, mrgs_wave.h; offsets restart at 0 per segment) into per-block offsets and
 //             the three totals the host reads (24 bytes: the call's only synchronisation).  Reads 20 B, writes 1 B per row.
 //   emit      grid (row blocks, tensors): a block rebuilds its rows' three destinations in LDS from the class bytes and the block
 //             offsets and streams its slab of one source once; originals, clones and the N children are written from that one read.
@@ -16,20 +17,16 @@
 #include "mrgs_internal.h"
 #include "mrgs_wave.h"
 #include "mrgs_philox.h"
-#include "mrgs_densify_common.h"
+#include "mrgs_rows_common.h"
 
 namespace {
 
 constexpr int DENSIFY_ROWS = 1024;              // rows per workgroup (256 threads x 4), as in the compaction of mrgs_optim.hip
 constexpr unsigned NONE = 0xFFFFFFFFu;
 constexpr unsigned CLS_KEEP = 1u, CLS_CLONE = 2u, CLS_CHILD = 4u;
-constexpr int FIELD = 21;                       // the three per-thread counts travel through one scan, 21 bits each (block totals <= 1024)
-constexpr unsigned long long FIELD_MASK = (1ull << FIELD) - 1;
 
-__device__ __forceinline__ unsigned long long pack_counts(unsigned cls)
-{
-    return (unsigned long long)(cls & 1u) | ((unsigned long long)((cls >> 1) & 1u) << FIELD) | ((unsigned long long)((cls >> 2) & 1u) << (2 * FIELD));
-}
+// the three per-thread counts of a class byte travel through one scan (pack_fields, mrgs_wave.h)
+__device__ __forceinline__ unsigned long long pack_counts(unsigned cls) { return pack_fields(cls & 1u, (cls >> 1) & 1u, (cls >> 2) & 1u); }
 
 struct ClassifyArgs {
     long long P;
@@ -77,35 +74,17 @@ __global__ __launch_bounds__(256) void densify_classify_kernel(ClassifyArgs a, c
     *reinterpret_cast<unsigned*>(cls_out + r0) = word;                  // the class array is padded to whole blocks
     unsigned long long total;
     block_exclusive_scan_256(c, s_wave, total);
-    if (threadIdx.x < 3) block_count[(size_t)threadIdx.x * nblocks + blockIdx.x] = (unsigned)((total >> (FIELD * threadIdx.x)) & FIELD_MASK);
+    if (threadIdx.x < 3) block_count[(size_t)threadIdx.x * nblocks + blockIdx.x] = unpack_field(total, threadIdx.x);
 }
 
 // block_count / block_off: [3][nblocks] (originals, clones, children per k); totals: device int64[3]
 __global__ __launch_bounds__(1024) void densify_scan_kernel(int nblocks, const unsigned* __restrict__ block_count, unsigned* __restrict__ block_off,
                                                             long long* __restrict__ totals)
 {
-    __shared__ unsigned s_part[3][1024];
-    const int per = (nblocks + 1023) / 1024, b0 = threadIdx.x * per;
-    for (int seg = 0; seg < 3; ++seg) {
-        unsigned s = 0;
-        for (int i = 0; i < per && b0 + i < nblocks; ++i) s += block_count[(size_t)seg * nblocks + b0 + i];
-        s_part[seg][threadIdx.x] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        const int seg = threadIdx.x;
-        unsigned run = 0;
-        for (int i = 0; i < 1024; ++i) { const unsigned v = s_part[seg][i]; s_part[seg][i] = run; run += v; }
-        totals[seg] = (long long)run;
-    }
-    __syncthreads();
-    for (int seg = 0; seg < 3; ++seg) {
-        unsigned run = s_part[seg][threadIdx.x];
-        for (int i = 0; i < per && b0 + i < nblocks; ++i) {
-            const size_t at = (size_t)seg * nblocks + b0 + i;
-            block_off[at] = run;
-            run += block_count[at];
-        }
+    __shared__ unsigned s_wave[16];
+    for (int seg = 0; seg < 3; ++seg) {                                 // offsets restart per segment: the emit pass adds n_keep and n_keep + n_clone
+        const unsigned total = block_counts_exclusive_scan<1024>(nblocks, block_count + (size_t)seg * nblocks, block_off + (size_t)seg * nblocks, s_wave);
+        if (threadIdx.x == 0) totals[seg] = (long long)total;
     }
 }
 
@@ -145,9 +124,9 @@ __global__ __launch_bounds__(256) void densify_emit_kernel(EmitArgs a, const uin
     unsigned long long total;
     const unsigned long long pre = block_exclusive_scan_256(c, s_wave, total);
     unsigned d[3];
-    d[0] = block_off[blockIdx.x] + (unsigned)(pre & FIELD_MASK);
-    d[1] = a.n_keep + block_off[(size_t)a.nblocks + blockIdx.x] + (unsigned)((pre >> FIELD) & FIELD_MASK);
-    d[2] = a.n_keep + a.n_clone + block_off[2 * (size_t)a.nblocks + blockIdx.x] + (unsigned)((pre >> (2 * FIELD)) & FIELD_MASK);
+    d[0] = block_off[blockIdx.x] + unpack_field(pre, 0);
+    d[1] = a.n_keep + block_off[(size_t)a.nblocks + blockIdx.x] + unpack_field(pre, 1);
+    d[2] = a.n_keep + a.n_clone + block_off[2 * (size_t)a.nblocks + blockIdx.x] + unpack_field(pre, 2);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const unsigned cls = (word >> (8 * j)) & 0xFFu;
@@ -253,7 +232,7 @@ extern "C" int mrgs_densify_emit(const MrgsDensifyConfig* cfg, const void* ws, c
     a.n_keep = (unsigned)n_keep; a.n_clone = (unsigned)n_clone; a.n_child = (unsigned)n_child;
     a.child_div = (float)(0.8 * (double)cfg->N);
     a.xyz = cfg->xyz_raw; a.scaling = cfg->scaling_raw; a.rotation = cfg->rotation_raw; a.noise = noise; a.seed = seed;
-    densify_emit_chunks(tensors, n_tensors, [&](const EmitTable& t, int m) {
+    tensor_table_chunks<EmitTable>(tensors, n_tensors, emit_table_fill, [&](const EmitTable& t, int m) {
         densify_emit_kernel<<<dim3((unsigned)nb, (unsigned)m), 256, 0, (hipStream_t)stream>>>(a, cls, offs, t);
     });
     return MRGS_LAUNCH_STATUS();

@@ -16,7 +16,7 @@
 //                   launch (bins in LDS, one global add per non-empty bin and block) and one one-block launch that picks the digit.
 //                   Exact k-th smallest, the count below it and the count equal to it; no sort.
 //   rank passes     one thread per row, 256 rows per block, ranks inside a block from wave ballots, 24 segment counts per block written
-//                   to a [24][blocks] matrix and scanned segment-major by one block: first the rows equal to the cut (the tie rule is
+//                   to a [24][blocks] matrix and scanned segment-major by one block (one block_counts_exclusive_scan, mrgs_wave.h, over all 24 rows): first the rows equal to the cut (the tie rule is
 //                   "earlier row goes first"), then the survivors (the destinations).  The host reads the totals once.
 //   emit            grid (row blocks, tensors): a block rebuilds its rows' up to ten destinations in LDS from the records and streams
 //                   its slab of one source once.  Per tensor of L floats a row: reads 4 L P bytes, writes 4 L bytes per output row.
@@ -25,7 +25,7 @@
 #include "mrgs_internal.h"
 #include "mrgs_wave.h"
 #include "mrgs_philox.h"
-#include "mrgs_densify_common.h"
+#include "mrgs_rows_common.h"
 
 namespace {
 
@@ -398,31 +398,18 @@ __global__ __launch_bounds__(256) void env_final_kernel(long long P, int nblocks
 __global__ __launch_bounds__(1024) void env_scan_kernel(int nblocks, const unsigned* __restrict__ mat, unsigned* __restrict__ off,
                                                         const unsigned* __restrict__ scal, const SelState* __restrict__ st, long long* __restrict__ counts)
 {
-    __shared__ unsigned s_part[1024];
-    __shared__ unsigned s_grand;
-    const int n = NSEG * nblocks, per = (n + 1023) / 1024, b0 = threadIdx.x * per;
-    unsigned s = 0;
-    for (int i = 0; i < per && b0 + i < n; ++i) s += mat[b0 + i];
-    s_part[threadIdx.x] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned run = 0;
-        for (int i = 0; i < 1024; ++i) { const unsigned v = s_part[i]; s_part[i] = run; run += v; }
-        s_grand = run;
-    }
-    __syncthreads();
-    unsigned run = s_part[threadIdx.x];
-    for (int i = 0; i < per && b0 + i < n; ++i) { off[b0 + i] = run; run += mat[b0 + i]; }
+    __shared__ unsigned s_wave[16];
+    const unsigned grand = block_counts_exclusive_scan<1024>(NSEG * nblocks, mat, off, s_wave);
     if (!counts) return;
     __threadfence_block();
     __syncthreads();
     if (threadIdx.x < NSEG) {
         const unsigned lo = off[(size_t)threadIdx.x * nblocks];
-        const unsigned hi = threadIdx.x == NSEG - 1 ? s_grand : off[(size_t)(threadIdx.x + 1) * nblocks];
+        const unsigned hi = threadIdx.x == NSEG - 1 ? grand : off[(size_t)(threadIdx.x + 1) * nblocks];
         counts[threadIdx.x] = (long long)(hi - lo);
     }
     if (threadIdx.x == 0) {
-        counts[24] = s_grand;
+        counts[24] = grand;
         counts[25] = scal[S_NCLONE]; counts[26] = scal[S_NSPLIT2]; counts[27] = scal[S_N3]; counts[28] = scal[S_PRUNE4];
         counts[29] = scal[S_SPLIT4]; counts[30] = scal[S_PRUNE5]; counts[31] = scal[S_Q];
         counts[32] = __float_as_uint(unord_f(scal[S_W0])); counts[33] = __float_as_uint(unord_f(scal[S_W1]));
@@ -619,7 +606,7 @@ extern "C" int mrgs_env_densify_emit(const MrgsEnvDensifyConfig* cfg, const void
     EmitArgs a;
     a.P = cfg->P; a.n_rows = n_rows; a.nblocks = (int)env_blocks(cfg->P);
     a.xyz = cfg->xyz_raw; a.scaling = cfg->scaling_raw; a.rotation = cfg->rotation_raw; a.noise = noise; a.noise4 = noise4; a.seed = seed;
-    const bool any = densify_emit_chunks(tensors, n_tensors, [&](const EmitTable& t, int m) {
+    const bool any = tensor_table_chunks<EmitTable>(tensors, n_tensors, emit_table_fill, [&](const EmitTable& t, int m) {
         env_emit_kernel<<<dim3((unsigned)a.nblocks, (unsigned)m), 256, 0, (hipStream_t)stream>>>(a, w.rec, w.off, t);
     });
     if (!any) return MRGS_OK;                                                     // every tensor has empty rows: nothing was queued

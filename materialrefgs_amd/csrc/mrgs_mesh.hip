@@ -9,7 +9,7 @@
 //             Algorithmic bytes: 4 per sample written, the depth maps through L2 (their taps are neighbours where the lanes are).
 //   count     per slab of planes along the slowest axis, one thread per lattice point: the 7-bit mask of its crossing edges (an edge is
 //             owned by its lower end), the triangles of the cube above it, an in-block scan; one word per point, three sums per block,
-//             then a one-workgroup scan into block offsets and the running totals.  The host reads 16 bytes.
+//             then one workgroup scans the three rows of sums (block_counts_exclusive_scan, mrgs_wave.h) into block offsets and the running totals.  The host reads 16 bytes.
 //   emit      the same two launches per slab again (the words are slab-sized, not lattice-sized), then one thread per lattice point
 //             writes its vertices and its cube's triangles: a corner's index is base[owner] + popcount(mask[owner] below its kind), so
 //             triangles share indices by construction -- no sort, no merge.
@@ -23,8 +23,6 @@
 namespace {
 
 constexpr int MESH_BLOCK = 256;                 // lattice points per workgroup, one per thread
-constexpr int FIELD = 21;                       // three counts travel through one scan, 21 bits each (block totals <= 12 * 256)
-constexpr unsigned long long FIELD_MASK = (1ull << FIELD) - 1;
 constexpr long long MESH_MAX_SLAB_POINTS = 1ll << 28;   // 12 triangles a point still fit the 32-bit slab-local offsets
 // word of a lattice point: bits 0-6 mask of crossing edges (bit c-1: direction code c = 4 dx + 2 dy + dz), 7-17 vertices before it in
 // its block (<= 7 * 255), 18-29 triangles before it in its block (<= 12 * 255)
@@ -159,11 +157,11 @@ __global__ __launch_bounds__(256) void mesh_count_kernel(MeshArgs a, const float
         owned = p.i < a.own_end ? 1u : 0u;
     }
     const unsigned nv = __popc(mask);
-    const unsigned long long c = (unsigned long long)nv | ((unsigned long long)ntri << FIELD) | ((unsigned long long)(owned ? nv : 0u) << (2 * FIELD));
+    const unsigned long long c = pack_fields(nv, ntri, owned ? nv : 0u);
     unsigned long long total;
     const unsigned long long pre = block_exclusive_scan_256(c, s_wave, total);
-    if (q < a.slab_points) words[q] = mask | ((unsigned)(pre & FIELD_MASK) << 7) | ((unsigned)((pre >> FIELD) & FIELD_MASK) << 18);
-    if (threadIdx.x < 3) block_count[(size_t)threadIdx.x * a.nblocks + blockIdx.x] = (unsigned)((total >> (FIELD * threadIdx.x)) & FIELD_MASK);
+    if (q < a.slab_points) words[q] = mask | (unpack_field(pre, 0) << 7) | (unpack_field(pre, 1) << 18);
+    if (threadIdx.x < 3) block_count[(size_t)threadIdx.x * a.nblocks + blockIdx.x] = unpack_field(total, threadIdx.x);
 }
 
 // block_count [3][nblocks] (vertices, triangles, owned vertices); block_off [2][nblocks]; slab_base = run before this slab (0 for the
@@ -172,23 +170,14 @@ __global__ __launch_bounds__(1024) void mesh_scan_kernel(int nblocks, const unsi
                                                          long long* __restrict__ run, long long* __restrict__ slab_base, int first)
 {
     __shared__ uint32_t s_wave[16];
-    unsigned carry[3] = {0u, 0u, 0u};                                   // the same in every thread
-    for (int base = 0; base < nblocks; base += 1024) {                  // 1024 consecutive blocks a step: coalesced, one shuffle scan each
-        const int b = base + (int)threadIdx.x;
-#pragma unroll
-        for (int seg = 0; seg < 3; ++seg) {
-            const unsigned v = b < nblocks ? block_count[(size_t)seg * nblocks + b] : 0u;
-            uint32_t total;
-            const uint32_t pre = block_exclusive_scan<1024>(v, s_wave, total);
-            if (seg < 2 && b < nblocks) block_off[(size_t)seg * nblocks + b] = carry[seg] + pre;
-            carry[seg] += total;
-        }
-    }
+    block_counts_exclusive_scan<1024>(nblocks, block_count, block_off, s_wave);
+    const unsigned ntri = block_counts_exclusive_scan<1024>(nblocks, block_count + (size_t)nblocks, block_off + (size_t)nblocks, s_wave);
+    const unsigned nown = block_counts_exclusive_scan<1024>(nblocks, block_count + 2 * (size_t)nblocks, nullptr, s_wave);
     if (threadIdx.x == 0) {
         const long long rv = first ? 0 : run[0], rt = first ? 0 : run[1];
         if (slab_base) { slab_base[0] = rv; slab_base[1] = rt; }
-        run[0] = rv + (long long)carry[2];
-        run[1] = rt + (long long)carry[1];
+        run[0] = rv + (long long)nown;
+        run[1] = rt + (long long)ntri;
     }
 }
 

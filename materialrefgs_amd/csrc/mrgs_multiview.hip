@@ -7,8 +7,10 @@
 //                       weight map, a valid byte map and one (sum w e, count) partial per workgroup.
 //   warp_geo_finalize   one workgroup: the partials in a fixed order -> n_valid and the geometric term.
 //   warp_sel_hist / warp_sel_scan (twice)   radix select of the k smallest per-pixel keys over the valid pixels.  The key is a seeded
-//                       bijection of the pixel index, so keys never tie and the k smallest are one well-defined set.
-//   warp_compact_count / warp_compact_scan / warp_compact_write   the selected pixels in ascending pixel order and the sample-slot map.
+//                       bijection of the pixel index, so keys never tie and the k smallest are one well-defined set.  warp_sel_scan: 64 bins a
+//                       thread, block_exclusive_scan (mrgs_wave.h) over the 1024 sums, then one thread walks its bins.
+//   warp_compact_count / warp_compact_scan / warp_compact_write   the selected pixels in ascending pixel order and the sample-slot map; the scan is
+//                       block_counts_exclusive_scan (mrgs_wave.h), in place.
 //   warp_patch_fwd      one 64-lane wave per sample, one lane per tap of the (2h+1)^2 patch: the view's taps at integer texels, the
 //                       neighbour's through the sample's plane homography (bilinear, zeros, align_corners), wave reductions in a fixed
 //                       order -> the per-sample base-colour, metallic and roughness terms.
@@ -269,23 +271,15 @@ __global__ __launch_bounds__(WB) void warp_sel_hist(WarpArgs a, WarpWs w, int pa
 // finds the bin holding the rank-th smallest key (rank = st[ST_REM], 1-based); pass 0: the high 16 bits, pass 1: the low 16 bits
 __global__ __launch_bounds__(FIN) void warp_sel_scan(WarpWs w, int pass)
 {
-    __shared__ uint32_t sh[FIN];
+    __shared__ uint32_t s_wave[FIN / 64];
     if (w.st[ST_TAKEALL]) return;
     const uint32_t* hist = w.hist + pass * NBINS;
     constexpr int PER = NBINS / FIN;
     uint32_t mine = 0;
     for (int i = 0; i < PER; ++i) mine += hist[threadIdx.x * PER + i];
-    sh[threadIdx.x] = mine;
-    __syncthreads();
-    for (int off = 1; off < FIN; off <<= 1) {            // inclusive scan (Hillis-Steele)
-        const uint32_t v = (int)threadIdx.x >= off ? sh[threadIdx.x - off] : 0u;
-        __syncthreads();
-        sh[threadIdx.x] += v;
-        __syncthreads();
-    }
-    const uint32_t rank = (uint32_t)w.st[ST_REM];
-    const uint32_t before = sh[threadIdx.x] - mine;
-    __syncthreads();
+    const uint32_t rank = (uint32_t)w.st[ST_REM];        // read before the scan's barriers: the one thread below rewrites it
+    uint32_t total;
+    const uint32_t before = block_exclusive_scan<FIN>(mine, s_wave, total);
     if (before < rank && rank <= before + mine) {          // exactly one thread
         uint32_t c = before;
         for (int i = 0; i < PER; ++i) {
@@ -323,29 +317,12 @@ __global__ __launch_bounds__(WB) void warp_compact_count(WarpArgs a, WarpWs w)
     if (threadIdx.x == 0) w.blk[blockIdx.x] = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
 }
 
-// exclusive scan of the per-workgroup counts, in place (one workgroup; chunks of FIN)
+// exclusive scan of the per-workgroup counts, in place (one workgroup)
 __global__ __launch_bounds__(FIN) void warp_compact_scan(WarpWs w, int nbg)
 {
-    __shared__ int sh[FIN];
-    __shared__ int carry;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    for (int base = 0; base < nbg; base += FIN) {
-        const int i = base + threadIdx.x;
-        const int v = i < nbg ? w.blk[i] : 0;
-        sh[threadIdx.x] = v;
-        __syncthreads();
-        for (int off = 1; off < FIN; off <<= 1) {
-            const int t = (int)threadIdx.x >= off ? sh[threadIdx.x - off] : 0;
-            __syncthreads();
-            sh[threadIdx.x] += t;
-            __syncthreads();
-        }
-        if (i < nbg) w.blk[i] = carry + sh[threadIdx.x] - v;
-        __syncthreads();
-        if (threadIdx.x == FIN - 1) carry += sh[FIN - 1];
-        __syncthreads();
-    }
+    __shared__ uint32_t s_wave[FIN / 64];
+    uint32_t* blk = reinterpret_cast<uint32_t*>(w.blk);                  // counts: non-negative ints
+    block_counts_exclusive_scan<FIN>(nbg, blk, blk, s_wave);
 }
 
 __global__ __launch_bounds__(WB) void warp_compact_write(WarpArgs a, WarpWs w)

@@ -12,6 +12,7 @@
 // (torch/optim/adam.py _single_tensor_adam, non-capturable, amsgrad = False, weight_decay = 0, maximize = False).
 #include "mrgs_internal.h"
 #include "mrgs_wave.h"
+#include "mrgs_rows_common.h"
 
 namespace {
 
@@ -119,8 +120,9 @@ extern "C" int mrgs_adam_step(const MrgsAdamTensor* tensors, int32_t n_tensors, 
 // ---- densify / prune compaction (scene/gaussian_model.py:856-905: _prune_optimizer + prune_points) -------------------------------
 // The reference drops pruned gaussians with `tensor[mask]` on each of ~16 parameter tensors, their two Adam moments and three
 // statistics vectors: ~50 boolean-index calls, each with its own nonzero() pass and host sync.  Here the keep mask is scanned once
-// (count per 1024-row block, one-workgroup scan of the block counts) and ONE launch gathers the surviving rows of every tensor:
-// grid = (row blocks, tensors), rows keep their order (stable, like boolean indexing).
+// (count per 1024-row block, then one workgroup scans the block counts: block_counts_exclusive_scan, mrgs_wave.h) and ONE launch
+// gathers the surviving rows of every tensor: grid = (row blocks, tensors), rows keep their order (stable, like boolean indexing).
+// The tensor list is validated whole before the first launch and chunked into launch tables by tensor_table_chunks (mrgs_rows_common.h).
 namespace {
 
 constexpr int COMPACT_ROWS = 1024;      // rows per workgroup
@@ -146,20 +148,9 @@ __global__ __launch_bounds__(256) void compact_count_kernel(long long n, const u
 __global__ __launch_bounds__(1024) void compact_scan_kernel(int nblocks, const unsigned* __restrict__ block_count, unsigned* __restrict__ block_off,
                                                             long long* __restrict__ total_out)
 {
-    __shared__ unsigned s_part[1024];
-    const int per = (nblocks + 1023) / 1024, b0 = threadIdx.x * per;
-    unsigned s = 0;
-    for (int i = 0; i < per && b0 + i < nblocks; ++i) s += block_count[b0 + i];
-    s_part[threadIdx.x] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned run = 0;
-        for (int i = 0; i < 1024; ++i) { const unsigned v = s_part[i]; s_part[i] = run; run += v; }
-        total_out[0] = (long long)run;
-    }
-    __syncthreads();
-    unsigned run = s_part[threadIdx.x];
-    for (int i = 0; i < per && b0 + i < nblocks; ++i) { block_off[b0 + i] = run; run += block_count[b0 + i]; }
+    __shared__ unsigned s_wave[16];
+    const unsigned total = block_counts_exclusive_scan<1024>(nblocks, block_count, block_off, s_wave);
+    if (threadIdx.x == 0) total_out[0] = (long long)total;
 }
 
 __global__ __launch_bounds__(256) void compact_gather_kernel(long long n, const uint8_t* __restrict__ keep, const unsigned* __restrict__ block_off,
@@ -221,18 +212,16 @@ extern "C" int mrgs_compact_rows(int64_t n_rows, const uint8_t* keep, const void
     if (!keep || !ws) return MRGS_E_BAD_ARG;
     const long long nb = (n_rows + COMPACT_ROWS - 1) / COMPACT_ROWS;
     const unsigned* offs = (const unsigned*)ws + nb;
-    for (int32_t first = 0; first < n_tensors; first += MRGS_COMPACT_MAX_TENSORS) {
-        CompactTable t;
-        int m = 0;
-        for (int32_t i = first; i < n_tensors && i < first + MRGS_COMPACT_MAX_TENSORS; ++i) {
-            if (tensors[i].row_floats < 0 || tensors[i].row_floats > (1 << 20)) return MRGS_E_BAD_ARG;
-            if (tensors[i].row_floats == 0) continue;
-            if (!tensors[i].src || !tensors[i].dst) return MRGS_E_BAD_ARG;
-            t.src[m] = tensors[i].src; t.dst[m] = tensors[i].dst; t.row_floats[m] = tensors[i].row_floats;
-            ++m;
-        }
-        if (m == 0) continue;
-        compact_gather_kernel<<<dim3((unsigned)nb, (unsigned)m), 256, 0, (hipStream_t)stream>>>(n_rows, keep, offs, t);
+    for (int32_t i = 0; i < n_tensors; ++i) {                           // the whole list before the first launch: a refused call moves nothing
+        const MrgsCompactTensor& e = tensors[i];
+        if (e.row_floats < 0 || e.row_floats > (1 << 20)) return MRGS_E_BAD_ARG;
+        if (e.row_floats != 0 && (!e.src || !e.dst)) return MRGS_E_BAD_ARG;
     }
+    tensor_table_chunks<CompactTable>(
+        tensors, n_tensors,
+        [](CompactTable& t, int m, const MrgsCompactTensor& e) { t.src[m] = e.src; t.dst[m] = e.dst; t.row_floats[m] = e.row_floats; },
+        [&](const CompactTable& t, int m) {
+            compact_gather_kernel<<<dim3((unsigned)nb, (unsigned)m), 256, 0, (hipStream_t)stream>>>(n_rows, keep, offs, t);
+        });
     return MRGS_LAUNCH_STATUS();
 }

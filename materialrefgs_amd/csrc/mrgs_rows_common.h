@@ -1,6 +1,8 @@
-// mrgs_densify_common.h -- what the two densifiers (mrgs_densify.hip, mrgs_env_densify.hip) state in the same words: the emit pass's tensor
-// table with its host-side checks and chunking, and the device expressions both policies start from.  Each file is built with its own
-// contraction setting (Makefile) and these functions inherit it, so nothing here may be rewritten for one file without checking the other.
+// mrgs_rows_common.h -- what the passes that move whole rows of a list of tensors state in the same words.  For all three (the compaction of
+// mrgs_optim.hip, mrgs_densify.hip, mrgs_env_densify.hip): the chunking of a tensor list into the tables of their gather / emit launches.
+// For the two densifiers: the emit pass's table with its host-side checks, and the device expressions both policies start from.  Each
+// file is built with its own contraction setting (Makefile) and these functions inherit it, so nothing here may be rewritten for one file
+// without checking the others.
 // Not here: the head of the row decision (g, s0, s1, ms, o, clone, split, faint; classify_row and row_eval).  The two files load its inputs
 // at different points and keep its results in different places, and every shared form of it changed the generated code of
 // densify_classify_kernel or env_stage4_kernel (`make X.s` against the parent), so each file keeps its own.
@@ -33,24 +35,26 @@ static inline int densify_check_tensors(const MrgsDensifyTensor* tensors, int32_
     return MRGS_OK;
 }
 
-// launch(table, m) for every chunk of MRGS_COMPACT_MAX_TENSORS list entries that has m > 0 tensors with rows to move; false when there was none
-template <typename Launch>
-static inline bool densify_emit_chunks(const MrgsDensifyTensor* tensors, int32_t n_tensors, Launch launch)
+// launch(table, m) for every chunk of MRGS_COMPACT_MAX_TENSORS list entries that has m > 0 tensors with rows to move; false when there was none.
+// fill(table, slot, entry) copies one list entry into the table.  The whole list is validated BEFORE this is called: a launch cannot be recalled.
+template <typename Table, typename Tensor, typename Fill, typename Launch>
+static inline bool tensor_table_chunks(const Tensor* tensors, int32_t n_tensors, Fill fill, Launch launch)
 {
     bool any = false;
     for (int32_t first = 0; first < n_tensors; first += MRGS_COMPACT_MAX_TENSORS) {
-        EmitTable t;
+        Table t;
         int m = 0;
-        for (int32_t i = first; i < n_tensors && i < first + MRGS_COMPACT_MAX_TENSORS; ++i) {
-            if (tensors[i].row_floats == 0) continue;
-            t.src[m] = tensors[i].src; t.dst[m] = tensors[i].dst; t.row_floats[m] = tensors[i].row_floats; t.role[m] = tensors[i].role;
-            ++m;
-        }
+        for (int32_t i = first; i < n_tensors && i < first + MRGS_COMPACT_MAX_TENSORS; ++i)
+            if (tensors[i].row_floats != 0) fill(t, m++, tensors[i]);
         if (m == 0) continue;
         launch(t, m);
         any = true;
     }
     return any;
+}
+static inline void emit_table_fill(EmitTable& t, int m, const MrgsDensifyTensor& e)
+{
+    t.src[m] = e.src; t.dst[m] = e.dst; t.row_floats[m] = e.row_floats; t.role[m] = e.role;
 }
 
 // R[col][0] and R[col][1] of R(normalize(q)), q = (r, x, y, z): the two matrix entries a surfel's in-plane offset meets (build_rotation).

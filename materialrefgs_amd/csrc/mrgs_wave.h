@@ -1,5 +1,8 @@
 // mrgs_wave.h -- wave64 and workgroup primitives shared by the kernel files: each exists here once.
 //
+// Wave reductions, the workgroup scans (of one value per thread, and of a whole array of per-workgroup counts by one workgroup), the packed
+// triple of counts that travels through those scans, and the last-block fold of six maxima.
+//
 // Two families of wave-wide reductions, told apart by name:
 //   wave_shfl_*   __shfl_xor butterfly: six ds_bpermute round trips through the LDS crossbar, the result in EVERY lane (a vector register)
 //   wave_dpp_*    six DPP steps on the VALU, the result read from lane 63 and therefore wave-uniform (a scalar register)
@@ -135,6 +138,45 @@ __device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v, uint32_t* l
     total = tot;
     return wave_off + inc - v;
 }
+// exclusive scan of n per-workgroup counts by ONE workgroup of THREADS threads: THREADS consecutive words a step (coalesced), the running
+// total carried in registers.  out may be null (total only) or alias in, hence no __restrict__: thread t writes only the words
+// t + k THREADS, each after it has read it; the one word it reads that is not its own is in[n - 1], by the clamped loads behind the
+// tail, and that value is thrown away.  Returns the total in every thread.  Every one-workgroup pass that turns per-block counts into
+// offsets (compaction, both densifiers, the mesh, the multi-view sampler) is this.
+// Why not the plain loop (v = i < n ? in[i] : 0; scan; store): a lone workgroup has nothing to hide a step's load behind, and
+// mesh_scan_kernel, which had its three rows' loads of a step in flight together, lost 3 % of count + emit to it (tools/mesh_time.py,
+// figures in DESIGN.md).  So the next step's word is loaded before this step's is scanned.  Seen in the generated code (make
+// mrgs_optim.s, compact_scan_kernel): with that load under `if (i + THREADS < n)` an s_waitcnt vmcnt(0) follows it at once; with the
+// use of `next` left to the end of the body the wait stands behind the store and covers it too.  Hence the clamped index and the empty
+// asm that uses `next` before the store; only this final form was timed.
+template <int THREADS>
+__device__ __forceinline__ uint32_t block_counts_exclusive_scan(int n, const uint32_t* in, uint32_t* out, uint32_t* lds_wave_sums /*[THREADS/64]*/)
+{
+    if (n <= 0) return 0u;
+    uint32_t carry = 0, v = in[min((int)threadIdx.x, n - 1)];
+    if ((int)threadIdx.x >= n) v = 0u;
+    for (int i = threadIdx.x; i - (int)threadIdx.x < n; i += THREADS) {
+        uint32_t next = in[min(i + THREADS, n - 1)];
+        if (i + THREADS >= n) next = 0u;
+        uint32_t total;
+        const uint32_t pre = block_exclusive_scan<THREADS>(v, lds_wave_sums, total);   // its trailing barrier frees lds_wave_sums for the next step
+        asm volatile("" : "+v"(next));              // the load's wait goes here, before the store
+        if (out && i < n) out[i] = carry + pre;
+        carry += total;
+        v = next;
+    }
+    return carry;
+}
+
+// Three counts through one 64-bit scan, FIELD bits each: a workgroup's three totals stay below 2^21 (1024 rows; 12 * 256 triangles).
+// The packer takes 64-bit parameters on purpose: with 32-bit ones widened inside, mesh_count_kernel came out with other code.
+constexpr int FIELD = 21;
+constexpr unsigned long long FIELD_MASK = (1ull << FIELD) - 1;
+__device__ __forceinline__ unsigned long long pack_fields(unsigned long long c0, unsigned long long c1, unsigned long long c2)
+{
+    return c0 | (c1 << FIELD) | (c2 << (2 * FIELD));
+}
+__device__ __forceinline__ unsigned unpack_field(unsigned long long packed, int k) { return (unsigned)((packed >> (FIELD * k)) & FIELD_MASK); }
 
 // ---- six maxima over a whole grid without same-address atomics -----------------------------------------------------------------------
 // Tail of a 256-thread kernel whose threads each hold six ordered-uint maxima (ext): every block leaves one partial row, takes a ticket,

@@ -159,15 +159,13 @@ def test_philox_statement_known_answer():
 
 
 # ---------------------------------------------------------------- on the GPU ---------------------------------------------------------
-def make_inputs(P, mix, seed, N=2):
-    """Parameters, moments, statistics and noise of P rows on the CPU (float32).  Every decision quantity is drawn from bands that stay
-    well clear of its threshold: g in {0, [0.2, 0.6] max_grad, [1.5, 4] max_grad}; max(s) in t x {[0.3, 0.7], [2, 4], [11, 14], [30, 40]}
-    (world limit 0.1 extent = 10 t; children are s / (0.8 N), N = 2, 3: [1.25, 2.5] t, [4.6, 8.75] t, [12.5, 25] t); o in {0.018, >= 0.62}."""
-    g = torch.Generator().manual_seed(seed)
+def make_decision_inputs(P, mix, g):
+    """The decision inputs of P rows from generator g: accum [P,1], denom [P,1], raw scaling [P,2], raw opacity [P,1] (CPU, float32).  Every
+    decision quantity is drawn from bands that stay well clear of its threshold: g in {0, [0.2, 0.6] max_grad, [1.5, 4] max_grad}; max(s) in
+    t x {[0.3, 0.7], [2, 4], [11, 14], [30, 40]} (world limit 0.1 extent = 10 t; children are s / (0.8 N), N = 2, 3: [1.25, 2.5] t,
+    [4.6, 8.75] t, [12.5, 25] t); o in {0.018, >= 0.62}."""
     u = lambda *sh: torch.rand(*sh, generator=g)
     pick = lambda probs: torch.multinomial(torch.tensor(probs), P, replacement=True, generator=g)
-    params = {n: torch.randn((P,) + sh, generator=g) for n, sh in GROUPS}
-    params["xyz"] = params["xyz"] * 2.0
     g_cat = {"typical": [0.35, 0.35, 0.30], "none": [0.5, 0.5, 0.0], "all_split": [0.0, 0.0, 1.0], "all_pruned": [0.35, 0.35, 0.30]}[mix]
     s_cat = {"typical": [0.65, 0.25, 0.05, 0.05], "none": [0.5, 0.5, 0.0, 0.0], "all_split": [0.0, 0.8, 0.2, 0.0], "all_pruned": [0.6, 0.3, 0.05, 0.05]}[mix]
     o_low = {"typical": 0.10, "none": 0.0, "all_split": 0.0, "all_pruned": 1.0}[mix]
@@ -181,11 +179,20 @@ def make_inputs(P, mix, seed, N=2):
     smax = (lo + (hi - lo) * u(P)) * T
     other = smax * (0.1 + 0.85 * u(P))
     first = u(P) < 0.5
-    params["scaling"] = torch.log(torch.stack([torch.where(first, smax, other), torch.where(first, other, smax)], dim=1))
-    params["opacity"] = torch.where(u(P, 1) < o_low, torch.full((P, 1), -4.0), 0.5 + 2.0 * u(P, 1))
+    scaling = torch.log(torch.stack([torch.where(first, smax, other), torch.where(first, other, smax)], dim=1))
+    opacity = torch.where(u(P, 1) < o_low, torch.full((P, 1), -4.0), 0.5 + 2.0 * u(P, 1))
+    return accum.reshape(P, 1), denom.reshape(P, 1), scaling, opacity
+
+
+def make_inputs(P, mix, seed, N=2):
+    """Parameters, moments, statistics and noise of P rows on the CPU (float32); the decision inputs are make_decision_inputs'."""
+    g = torch.Generator().manual_seed(seed)
+    params = {n: torch.randn((P,) + sh, generator=g) for n, sh in GROUPS}
+    params["xyz"] = params["xyz"] * 2.0
+    accum, denom, params["scaling"], params["opacity"] = make_decision_inputs(P, mix, g)
     moments = {n: (torch.randn(v.shape, generator=g), torch.rand(v.shape, generator=g)) for n, v in params.items()}
     noise = torch.randn(P, N, 2, generator=g)
-    return params, moments, accum.reshape(P, 1), denom.reshape(P, 1), noise
+    return params, moments, accum, denom, noise
 
 
 def make_model(params, moments, accum, denom, dev, stepped=True):
@@ -277,6 +284,38 @@ def test_row_counts_around_the_block_edge(gpu_device, P):
         assert fates == {(0, 0, 0), (1, 0, 0), (1, 1, 0), (0, 0, 1)}
     if P >= 1023:
         assert min(ref.counts) > 0
+
+
+@pytest.mark.gpu
+def test_offsets_carry_across_the_scan_step(gpu_device):
+    """P = 1024 * 1024 + 1027 rows are 1026 row blocks: the one-workgroup scan takes 1024 block counts a step, so the last two blocks'
+    offsets need the first step's total, in each of the three segments.  Straight through mrgs_densify_classify and mrgs_densify_emit with
+    one COPY tensor of one float a row that holds the row index (exact in fp32 below 2^24), against the three masks of the statement."""
+    from materialrefgs_amd import _lib
+    dev, P, N = gpu_device, 1024 * 1024 + 1027, 2
+    accum, denom, scaling, opacity = make_decision_inputs(P, "typical", torch.Generator().manual_seed(7))
+    params = {"xyz": torch.zeros(P, 3), "scaling": scaling, "rotation": torch.tensor([1.0, 0.0, 0.0, 0.0]).repeat(P, 1), "opacity": opacity}
+    ref = ds.densify_and_prune(params, None, accum, denom, PERCENT_DENSE, MAX_GRAD, MIN_OPACITY, EXTENT, 20, torch.zeros(P, N, 2), N=N)
+    assert ref.margin >= 1e-3, ref.margin                                                # the condition of the exact comparison
+    keep, clone, child = (torch.zeros(P, dtype=torch.bool).index_fill_(0, ref.row[ref.kind == k], True) for k in (0, 1, 2))
+    assert int(keep[-1027:].sum()) > 0 and int(clone[-1027:].sum()) > 0 and int(child[-1027:].sum()) > 0     # the second step has all three
+    L = _lib.lib()
+    accum, denom, scaling, opacity = (t.to(dev).contiguous() for t in (accum, denom, scaling, opacity))
+    idx = torch.arange(P, dtype=torch.float32, device=dev)
+    cfg = _lib.MrgsDensifyConfig(N, P, MAX_GRAD, MIN_OPACITY, PERCENT_DENSE * EXTENT, 0.1 * EXTENT, None, scaling.data_ptr(), None)
+    with _lib.guard(dev):
+        st = _lib.stream_ptr(dev)
+        ws = torch.empty(L.mrgs_densify_ws_bytes(P), dtype=torch.uint8, device=dev)
+        cnt = torch.empty(3, dtype=torch.int64, device=dev)
+        assert L.mrgs_densify_classify(ctypes.byref(cfg), accum.data_ptr(), denom.data_ptr(), scaling.data_ptr(), opacity.data_ptr(),
+                                       ws.data_ptr(), ws.numel(), cnt.data_ptr(), st) == 0
+        counts = cnt.tolist()
+        assert counts == [int(keep.sum()), int(clone.sum()), int(child.sum())] and tuple(counts) == ref.counts
+        dst = torch.full((counts[0] + counts[1] + N * counts[2],), -1.0, device=dev)
+        arr = (_lib.MrgsDensifyTensor * 1)(_lib.MrgsDensifyTensor(idx.data_ptr(), dst.data_ptr(), 1, _lib.MRGS_DENSIFY_COPY))
+        assert L.mrgs_densify_emit(ctypes.byref(cfg), ws.data_ptr(), (ctypes.c_int64 * 3)(*counts), arr, 1, 0, None, st) == 0
+    want = torch.arange(P, dtype=torch.float32)
+    assert torch.equal(dst.cpu(), torch.cat([want[keep], want[clone]] + [want[child]] * N))
 
 
 @pytest.mark.gpu

@@ -320,7 +320,7 @@ SINGLE_ROW_SEEDS = (17, 0, 5, 3, 51)       # pruned, kept, cloned, split once, s
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("P", [1, 1023, 1024, 1025, 5000])
+@pytest.mark.parametrize("P", [1, 1023, 1024, 1025, 5000, 11009])     # 11 009 rows: 44 blocks, 24 * 44 = 1056 count words, two scan steps
 def test_row_counts_around_the_block_edge(gpu_device, P):
     if P == 1:
         fates = [single_row_fate(run_case(gpu_device, 1, "seen", seed)[1]) for seed in SINGLE_ROW_SEEDS]

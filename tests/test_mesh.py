@@ -357,6 +357,18 @@ def test_extraction_edge_cases(gpu_device):
 
 
 @pytest.mark.gpu
+def test_extraction_more_than_1024_blocks_in_one_slab(gpu_device):
+    """66 x 64 x 64 points in a single slab are 1056 blocks of 256: the one-workgroup scan takes 1024 block sums a step, so the blocks of
+    the last two planes get their offsets from a second step that needs the first one's totals.  The sphere leaves the lattice through
+    those planes, so they own vertices and triangles."""
+    shape, origin, spacing = (66, 64, 64), np.array([-0.651, -0.633, -0.627], np.float32), np.full(3, 0.02, np.float32)
+    F = ms.field_sphere(ms.lattice_points(origin.astype(np.float64), spacing.astype(np.float64), shape), centre=(0.2, 0.05, -0.03)).astype(np.float32)
+    _m, st = _check_extraction("66 x 64 x 64", F, gpu_device, origin=origin, spacing=spacing)
+    beyond = 1024 * 256 * 8                                             # keys are lattice index * 8 + direction code
+    assert (st["keys"] >= beyond).sum() > 100 and (st["tkeys"].min(axis=1) >= beyond).sum() > 100
+
+
+@pytest.mark.gpu
 def test_clusters_and_post_process(gpu_device):
     """Two spheres (radii 0.25 and 0.13) plus a blob of fewer than 50 triangles: cluster_to_keep = 1 keeps the large sphere, 2 keeps both
     spheres and drops the blob (the floor of 50), 1000 clamps to the three clusters and still drops the blob.  Survivors keep their order,

@@ -206,3 +206,63 @@ def test_prune_matches_boolean_indexing(P, frac):
     oa.step()
     rep = densify.replace_tensor_to_optimizer(oa, torch.full((m + n_new, 1), -3.0, device=dev), "opacity")
     assert float(oa.state[rep["opacity"]]["exp_avg"].abs().sum()) == 0.0
+
+
+SENTINEL = -12345.0      # no draw of randn equals it
+
+
+def _compact_through_ctypes(mask, src, dev, row_floats=None):
+    """mrgs_compact_count and mrgs_compact_rows on (mask, src) straight through ctypes, the destinations filled with SENTINEL beforehand;
+    row_floats overrides the list's widths.  Returns (status of mrgs_compact_rows, count, destinations)."""
+    from materialrefgs_amd import _lib
+    L = _lib.lib()
+    n = mask.shape[0]
+    keep = mask.to(torch.uint8).to(dev)
+    with _lib.guard(dev):
+        st = _lib.stream_ptr(dev)
+        ws = torch.empty(L.mrgs_compact_ws_bytes(n), dtype=torch.uint8, device=dev)
+        cnt = torch.empty(1, dtype=torch.int64, device=dev)
+        assert L.mrgs_compact_count(n, keep.data_ptr(), ws.data_ptr(), ws.numel(), cnt.data_ptr(), st) == 0
+        count = int(cnt.item())
+        dst = [torch.full((count,) + tuple(t.shape[1:]), SENTINEL, device=dev) for t in src]
+        widths = row_floats or [t.shape[1] for t in src]
+        arr = (_lib.MrgsCompactTensor * len(src))(*[_lib.MrgsCompactTensor(t.data_ptr(), d.data_ptr(), w) for t, d, w in zip(src, dst, widths)])
+        rc = L.mrgs_compact_rows(n, keep.data_ptr(), ws.data_ptr(), arr, len(src), st)
+    torch.cuda.synchronize(dev)
+    return rc, count, dst
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n_rows", [1024 * 1024, 1024 * 1024 + 1, 1024 * 1024 + 1027])
+def test_compaction_carries_offsets_across_the_scan_step(n_rows):
+    """A row block is 1024 rows and the one-workgroup scan takes 1024 block counts a step: 1024, 1025 and 1026 blocks are one full step, a
+    one-word second step and a ragged second step.  Blocks 1000..1023 are dropped whole and block 1024 is kept whole, so the offsets of the
+    second step are right only with the first step's total carried into them.  Two tensors, one and three floats a row."""
+    from materialrefgs_amd import _lib
+    dev = torch.device("cuda")
+    g = torch.Generator().manual_seed(n_rows)
+    mask = torch.rand(n_rows, generator=g) < 0.5
+    mask[1000 * 1024:1024 * 1024] = False
+    mask[1024 * 1024:1025 * 1024] = True
+    src = [torch.randn(n_rows, 1, generator=g).to(dev), torch.randn(n_rows, 3, generator=g).to(dev)]
+    rc, count, dst = _compact_through_ctypes(mask, src, dev)
+    assert rc == _lib.MRGS_OK and count == int(mask.sum())
+    for t, d in zip(src, dst):
+        assert torch.equal(d, t[mask.to(dev)])
+
+
+@pytest.mark.gpu
+def test_compaction_refuses_a_bad_list_before_it_moves_a_row():
+    """One entry more than a launch table holds, the last with row_floats = -1: MRGS_E_BAD_ARG, and no destination of the first table's
+    entries has been written -- the whole list is validated before the first launch."""
+    import re
+    from materialrefgs_amd import _lib
+    dev = torch.device("cuda")
+    with open(os.path.join(ROOT, "include", "mrgs.h")) as f:        # the binding has the status codes but not this constant
+        max_tensors = int(re.search(r"^#define MRGS_COMPACT_MAX_TENSORS (\d+)$", f.read(), re.M).group(1))
+    mask = torch.ones(8, dtype=torch.bool)
+    src = [torch.randn(8, 2, generator=torch.Generator().manual_seed(i)).to(dev) for i in range(max_tensors + 1)]
+    rc, count, dst = _compact_through_ctypes(mask, src, dev, row_floats=[2] * max_tensors + [-1])
+    assert count == 8 and rc == _lib.MRGS_E_BAD_ARG
+    for d in dst[:max_tensors]:
+        assert d.shape == (8, 2) and bool((d == SENTINEL).all())
