@@ -1064,6 +1064,23 @@ int mrgs_mesh_reindex(int64_t V_old, int64_t V_new, const int32_t* new_to_old, i
 int mrgs_debug_export(const MrgsRasterConfig* cfg, const void* geom_ws, const void* binning_ws, const void* img_ws,
                       int64_t num_rendered, int32_t which, void* dst, void* stream);
 
+/* The two look-back primitives of the binning on their own, for the tests (tests/test_sort_scan.py); production paths do not go through
+ * these.  All pointers but the workspace sizes' are device pointers.  Both calls clear their workspace, synchronise the stream and
+ * return MRGS_E_INTERNAL if a look-back gave up.  Before any HIP call: MRGS_E_BAD_ARG for a NULL pointer (n_dev excepted), n < 0,
+ * bit_lo < 0, bit_hi > 32, bit_lo >= bit_hi with n > 0, a scan workspace that is not 8-byte aligned; MRGS_E_UNSUPPORTED for n >= 2^30
+ * (the scan: n > 2^30); MRGS_E_WORKSPACE for ws_bytes below the size query's answer.
+ * mrgs_debug_radix_sort_pairs: stable sort of the n (key, value) pairs on key bits [bit_lo, bit_hi) in place; the other key bits ride
+ * along and take no part in the order.  n_dev (nullable): the count is read from the device, n is the capacity; a count above n means
+ * "nothing to do" and leaves keys / vals unspecified.
+ * mrgs_debug_scan_tiles: offsets[i] = sum of tiles_touched[order[j]] for j < i, *total = the whole sum, saturated at 0xFFFFFFFF (the
+ * offsets are then meaningless).  The sum of any 2 048 consecutive terms must stay below 2^32. */
+size_t mrgs_debug_sort_ws_bytes(int64_t n);
+int mrgs_debug_radix_sort_pairs(uint32_t* keys, uint32_t* vals, int64_t n, const uint32_t* n_dev, int32_t bit_lo, int32_t bit_hi, void* ws,
+                                size_t ws_bytes, void* stream);
+size_t mrgs_debug_scan_ws_bytes(int64_t n);
+int mrgs_debug_scan_tiles(const uint32_t* tiles_touched, const uint32_t* order, int32_t n, uint32_t* offsets, uint32_t* total, void* ws,
+                          size_t ws_bytes, void* stream);
+
 /* HIP-event timing of the last forward_render / backward call's dominant kernels on their stream (bench.py). */
 typedef struct MrgsKernelTimes {
     float preprocess_ms, sort_ms, duplicate_ms, render_fwd_ms, render_bwd_ms, preprocess_bwd_ms;

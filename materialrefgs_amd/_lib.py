@@ -326,6 +326,10 @@ SYMBOLS = {
     "mrgs_surfel_shade_composite_backward": (ctypes.c_int, [ctypes.POINTER(MrgsEnvMips), ctypes.POINTER(MrgsShadeFrame), c_int32] + [c_void_p] * 13),
     "mrgs_debug_export": (ctypes.c_int, [ctypes.POINTER(MrgsRasterConfig), c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p,
                                          c_void_p]),
+    "mrgs_debug_sort_ws_bytes": (c_size_t, [c_int64]),
+    "mrgs_debug_radix_sort_pairs": (ctypes.c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_int32, c_void_p, c_size_t, c_void_p]),
+    "mrgs_debug_scan_ws_bytes": (c_size_t, [c_int64]),
+    "mrgs_debug_scan_tiles": (ctypes.c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "mrgs_set_profiling": (ctypes.c_int, [c_int32]),
     "mrgs_get_kernel_times": (ctypes.c_int, [ctypes.POINTER(MrgsKernelTimes)]),
     "mrgs_strerror": (ctypes.c_char_p, [ctypes.c_int]),

@@ -612,6 +612,72 @@ int mrgs_debug_export(const MrgsRasterConfig* cfg, const void* geom_ws, const vo
     return MRGS_LAUNCH_STATUS();
 }
 
+// ---- the sort and the scan of mrgs_sort.hip on their own, for the tests ----------------------------------
+// Workspace of mrgs_debug_radix_sort_pairs (uint32 words): alternate keys [n64] | alternate values [n64] | DBG_STATE words whose first is
+// the look-back error flag | mrgs_sort_ws_words(n).  Everything from the error flag on is what the sort needs zeroed.
+#define DBG_STATE 16
+static size_t dbg_n64(int64_t n) { return mrgs_align_up((size_t)(n > 0 ? n : 1), 64); }
+
+size_t mrgs_debug_sort_ws_bytes(int64_t n)
+{
+    if (n < 0) return 0;
+    return sizeof(uint32_t) * (2 * dbg_n64(n) + DBG_STATE + mrgs_sort_ws_words(n));
+}
+
+int mrgs_debug_radix_sort_pairs(uint32_t* keys, uint32_t* vals, int64_t n, const uint32_t* n_dev, int32_t bit_lo, int32_t bit_hi, void* ws,
+                                size_t ws_bytes, void* stream_)
+{
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!keys || !vals || !ws || n < 0 || bit_lo < 0 || bit_hi > 32 || (n > 0 && bit_lo >= bit_hi)) return MRGS_E_BAD_ARG;
+    if (n >= (1ll << 30)) return MRGS_E_UNSUPPORTED;   // the status words of the passes carry counts in 30 bits
+    if (ws_bytes < mrgs_debug_sort_ws_bytes(n)) return MRGS_E_WORKSPACE;
+    if (n == 0) return MRGS_OK;
+    uint32_t* w = (uint32_t*)ws;
+    const size_t n64 = dbg_n64(n);
+    uint32_t* key[2] = {keys, w};
+    uint32_t* val[2] = {vals, w + n64};
+    uint32_t* state = w + 2 * n64;
+    MRGS_HIP_TRY(hipMemsetAsync(state, 0, sizeof(uint32_t) * (DBG_STATE + mrgs_sort_ws_words(n)), stream));
+    const int cur = mrgs_radix_sort_pairs(key, val, state + DBG_STATE, state, n, n_dev, bit_lo, bit_hi, stream);
+    if (int rc = MRGS_LAUNCH_STATUS()) return rc;
+    if (cur != 0) {   // an odd number of passes leaves the result in the alternate buffers
+        MRGS_HIP_TRY(hipMemcpyAsync(keys, key[1], sizeof(uint32_t) * n, hipMemcpyDeviceToDevice, stream));
+        MRGS_HIP_TRY(hipMemcpyAsync(vals, val[1], sizeof(uint32_t) * n, hipMemcpyDeviceToDevice, stream));
+    }
+    uint32_t flag = 0;
+    MRGS_HIP_TRY(hipMemcpyAsync(&flag, state, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    MRGS_HIP_TRY(hipStreamSynchronize(stream));
+    return flag != 0 ? MRGS_E_INTERNAL : MRGS_OK;
+}
+
+// Workspace of mrgs_debug_scan_tiles (uint32 words): DBG_STATE words whose first is the error flag | mrgs_scan_ws_words(n), all zeroed here.
+size_t mrgs_debug_scan_ws_bytes(int64_t n)
+{
+    if (n < 0 || n > (1 << 30)) return 0;   // (the scan's index arithmetic is 32-bit)
+    return sizeof(uint32_t) * (DBG_STATE + mrgs_scan_ws_words((int)n));
+}
+
+int mrgs_debug_scan_tiles(const uint32_t* tiles_touched, const uint32_t* order, int32_t n, uint32_t* offsets, uint32_t* total, void* ws,
+                          size_t ws_bytes, void* stream_)
+{
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!tiles_touched || !order || !offsets || !total || !ws || n < 0 || ((uintptr_t)ws & 7u) != 0) return MRGS_E_BAD_ARG;
+    if (n > (1 << 30)) return MRGS_E_UNSUPPORTED;
+    if (ws_bytes < mrgs_debug_scan_ws_bytes(n)) return MRGS_E_WORKSPACE;
+    if (n == 0) {   // no workgroup would run: the total of nothing
+        MRGS_HIP_TRY(hipMemsetAsync(total, 0, sizeof(uint32_t), stream));
+        return MRGS_OK;
+    }
+    uint32_t* state = (uint32_t*)ws;
+    MRGS_HIP_TRY(hipMemsetAsync(state, 0, sizeof(uint32_t) * (DBG_STATE + mrgs_scan_ws_words(n)), stream));
+    mrgs_scan_tiles(tiles_touched, order, offsets, state + DBG_STATE, total, state, n, stream);
+    if (int rc = MRGS_LAUNCH_STATUS()) return rc;
+    uint32_t flag = 0;
+    MRGS_HIP_TRY(hipMemcpyAsync(&flag, state, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    MRGS_HIP_TRY(hipStreamSynchronize(stream));
+    return flag != 0 ? MRGS_E_INTERNAL : MRGS_OK;
+}
+
 int mrgs_set_profiling(int32_t enabled)
 {
     std::lock_guard<std::mutex> lk(g_prof_mutex);

@@ -79,10 +79,13 @@ __device__ __forceinline__ bool os_look_back(const uint32_t* __restrict__ status
     return true;
 }
 
+// digit of the pass at `shift`: 8 bits, fewer in a last pass that ends at bit_hi -- key bits from bit_hi up take no part in the order
+__host__ __device__ __forceinline__ uint32_t digit_mask(int shift, int bit_hi) { return bit_hi - shift >= 8 ? 255u : (1u << (bit_hi - shift)) - 1u; }
+
 // ---- digit totals of every pass in one sweep over the keys ----------------------------------------------
 template <int NPASS>
 __global__ void __launch_bounds__(SORT_THREADS) radix_totals_kernel(const uint32_t* __restrict__ keys, int64_t n_host,
-                                                                    const uint32_t* __restrict__ n_dev, int bit_lo,
+                                                                    const uint32_t* __restrict__ n_dev, int bit_lo, int bit_hi,
                                                                     uint32_t* __restrict__ totals /*[NPASS][256]*/)
 {
     __shared__ uint32_t h[NPASS][256];
@@ -101,7 +104,7 @@ __global__ void __launch_bounds__(SORT_THREADS) radix_totals_kernel(const uint32
         for (int j = 0; j < 8; j++) {
             if (base + j * stride < n) {
 #pragma unroll
-                for (int p = 0; p < NPASS; p++) atomicAdd(&h[p][(k[j] >> (bit_lo + 8 * p)) & 255u], 1u);
+                for (int p = 0; p < NPASS; p++) atomicAdd(&h[p][(k[j] >> (bit_lo + 8 * p)) & digit_mask(bit_lo + 8 * p, bit_hi)], 1u);
             }
         }
     }
@@ -119,7 +122,7 @@ __global__ void __launch_bounds__(SORT_THREADS) radix_onesweep_kernel(const uint
                                                                       uint32_t* __restrict__ kout, uint32_t* __restrict__ vout,
                                                                       const uint32_t* __restrict__ totals, uint32_t* __restrict__ status,
                                                                       uint32_t* __restrict__ ticket, uint32_t* __restrict__ error_flag,
-                                                                      int64_t n_host, const uint32_t* __restrict__ n_dev, int shift)
+                                                                      int64_t n_host, const uint32_t* __restrict__ n_dev, int shift, uint32_t mask)
 {
     __shared__ uint32_t whist[SORT_WAVES][256];
     __shared__ uint32_t start[256];
@@ -157,7 +160,7 @@ __global__ void __launch_bounds__(SORT_THREADS) radix_onesweep_kernel(const uint
 #pragma unroll
     for (int it = 0; it < ITEMS; it++) {
         const bool valid = wbase + it * 64 < n;
-        const uint32_t d = (key[it] >> shift) & 255u;
+        const uint32_t d = (key[it] >> shift) & mask;
         uint64_t peers = __builtin_amdgcn_ballot_w64(valid);
 #pragma unroll
         for (int b = 0; b < 8; b++) {
@@ -210,7 +213,7 @@ __global__ void __launch_bounds__(SORT_THREADS) radix_onesweep_kernel(const uint
 #pragma unroll
     for (int it = 0; it < ITEMS; it++) {
         if (wbase + it * 64 < n) {
-            const uint32_t d = (key[it] >> shift) & 255u;
+            const uint32_t d = (key[it] >> shift) & mask;
             const uint32_t lp = lstart[d] + whist[wave][d] + off[it];
             s_key[lp] = key[it];
             s_val[lp] = val[it];
@@ -222,7 +225,7 @@ __global__ void __launch_bounds__(SORT_THREADS) radix_onesweep_kernel(const uint
         const uint32_t e = (uint32_t)(it * SORT_THREADS + tid);
         if (e < tile_n) {
             const uint32_t k = s_key[e];
-            const uint32_t pos = start[(k >> shift) & 255u] + e;
+            const uint32_t pos = start[(k >> shift) & mask] + e;
             kout[pos] = k;
             vout[pos] = s_val[e];
         }
@@ -255,17 +258,17 @@ int mrgs_radix_sort_pairs(uint32_t* key[2], uint32_t* val[2], uint32_t* ws, uint
     uint32_t* status = totals + 4 * 256;
     const int tblk = (int)((n + 4095) / 4096 < 1024 ? (n + 4095) / 4096 : 1024);
     switch (npass) {
-    case 1: hipLaunchKernelGGL(radix_totals_kernel<1>, dim3(tblk), dim3(SORT_THREADS), 0, stream, key[0], n, n_dev, bit_lo, totals); break;
-    case 2: hipLaunchKernelGGL(radix_totals_kernel<2>, dim3(tblk), dim3(SORT_THREADS), 0, stream, key[0], n, n_dev, bit_lo, totals); break;
-    case 3: hipLaunchKernelGGL(radix_totals_kernel<3>, dim3(tblk), dim3(SORT_THREADS), 0, stream, key[0], n, n_dev, bit_lo, totals); break;
-    default: hipLaunchKernelGGL(radix_totals_kernel<4>, dim3(tblk), dim3(SORT_THREADS), 0, stream, key[0], n, n_dev, bit_lo, totals); break;
+    case 1: hipLaunchKernelGGL(radix_totals_kernel<1>, dim3(tblk), dim3(SORT_THREADS), 0, stream, key[0], n, n_dev, bit_lo, bit_hi, totals); break;
+    case 2: hipLaunchKernelGGL(radix_totals_kernel<2>, dim3(tblk), dim3(SORT_THREADS), 0, stream, key[0], n, n_dev, bit_lo, bit_hi, totals); break;
+    case 3: hipLaunchKernelGGL(radix_totals_kernel<3>, dim3(tblk), dim3(SORT_THREADS), 0, stream, key[0], n, n_dev, bit_lo, bit_hi, totals); break;
+    default: hipLaunchKernelGGL(radix_totals_kernel<4>, dim3(tblk), dim3(SORT_THREADS), 0, stream, key[0], n, n_dev, bit_lo, bit_hi, totals); break;
     }
     for (int p = 0; p < npass; p++) {
         const int shift = bit_lo + 8 * p;
         uint32_t* st = status + (size_t)p * nblk * 256;
 #define OS_LAUNCH(IT)                                                                                                        \
     hipLaunchKernelGGL(radix_onesweep_kernel<IT>, dim3(nblk), dim3(SORT_THREADS), 0, stream, key[cur], val[cur], key[cur ^ 1], \
-                       val[cur ^ 1], totals + p * 256, st, tickets + p, error_flag, n, n_dev, shift)
+                       val[cur ^ 1], totals + p * 256, st, tickets + p, error_flag, n, n_dev, shift, digit_mask(shift, bit_hi))
         if (items == 4) OS_LAUNCH(4);
         else if (items == 8) OS_LAUNCH(8);
         else OS_LAUNCH(16);

@@ -111,6 +111,22 @@ class HipRender:
         return {k: v.grad.detach().cpu().numpy() for k, v in self.leaves.items() if v.grad is not None}
 
 
+# The three instances of radix_onesweep_kernel<ITEMS> and the counts up to which mrgs_sort.hip's sort_items() picks each (keys per
+# thread; a workgroup tile is 256 x ITEMS keys).  Restated here ONCE: the tests that aim at an instance assert it through this table.
+SORT_ITEMS = ((128 << 10, 4), (768 << 10, 8), (None, 16))
+SCAN_TILE = 2048        # elements per workgroup of scan_tiles_kernel (SCAN_THREADS x SCAN_PER_THREAD)
+BIN_MAX_TILES = 16384   # mrgs_bin_supported: images with more tiles bin through the radix sort
+
+
+def sort_items(n):
+    """Keys per thread of the radix pass instance a sort of n keys runs (sort_items of mrgs_sort.hip)."""
+    return next(items for upto, items in SORT_ITEMS if upto is None or n <= upto)
+
+
+def scan_workgroups(n):
+    return (n + SCAN_TILE - 1) // SCAN_TILE
+
+
 def rel_err(a, b):
     """max |a-b| / max |b| (the tensor-level relative error of BASELINE.json's 'grad max-rel-err')."""
     a = np.asarray(a, dtype=np.float64)

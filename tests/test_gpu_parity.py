@@ -237,20 +237,25 @@ def test_untouched_pixels_ignore_their_upstream_gradients(gpu_device):
         assert rel_err(poisoned[k], clean[k]) <= 1e-5, k   # atomics: summation order differs between runs
 
 
-def test_forward_on_a_capacity_guess_matches_the_two_phase_forward(gpu_device):
+@pytest.mark.parametrize("P,H,W,rpx", [(3000, 160, 120, 6.0),         # the tile path (mrgs_binning.hip)
+                                       (20000, 2064, 2064, 12.0)])    # the radix path: mrgs_count and the n_dev / R_dev arguments of mrgs_sort.hip
+def test_forward_on_a_capacity_guess_matches_the_two_phase_forward(gpu_device, P, H, W, rpx):
     """mrgs_rasterize_forward (no host round trip, binning workspace sized from a guess, pair count read on the device) against
-    the two-phase path; a guess that is too small must fall back transparently."""
+    the two-phase path; a guess that is too small must fall back transparently.  On the radix path (more than 16 384 tiles) the sort of
+    the pairs, duplicate_kernel and tile_ranges_kernel are launched for the capacity and read the count on the device."""
     from materialrefgs_amd import rasterizer as rz
-    S, H, W = 4, 160, 120
-    scene = make_shell_scene(3000, S=S, seed=9, radius_px=6.0, image_size=160)
+    S = 4
+    assert (((H + 15) // 16) * ((W + 15) // 16) > 16384) == (H > 2048)
+    scene = make_shell_scene(P, S=S, seed=9, radius_px=rpx, image_size=max(H, W))
     cam = orbit_camera(3, H, W)
     grads = upstream_grads(S, H, W)
     results = []
-    key = (gpu_device.index, 3000, H, W)                       # the guess is kept per (device, P, H, W)
+    key = (gpu_device.index, P, H, W)                          # the guess is kept per (device, P, H, W)
     paths = []
     for guess in (None, 10, "half", 10_000_000, "exact"):      # too small (twice), far too large, exact
         if guess is None:
-            rz._PAIR_GUESS.pop(key, None)
+            for k in [k for k in rz._PAIR_GUESS if (k[0], k[2], k[3]) == (key[0], H, W)]:
+                rz._PAIR_GUESS.pop(k, None)                    # (no guess scaled from another surfel count at this image size either)
         else:
             rz._PAIR_GUESS[key] = results[0][0] if guess == "exact" else results[0][0] // 2 if guess == "half" else guess
         hr = HipRender(scene, cam, gpu_device)
@@ -583,7 +588,7 @@ def test_dense_tiles_take_the_big_sort_path(gpu_device, P, H, W, rpx):
 
 
 def test_image_with_more_tiles_than_the_slice_histograms_hold(gpu_device):
-    """Above 20 480 tiles (here 3 200 x 3 200 px = 40 000) the binning falls back to the global radix path of mrgs_sort.hip:
+    """Above 16 384 tiles (mrgs_bin_supported; here 3 200 x 3 200 px = 40 000) the binning falls back to the global radix path of mrgs_sort.hip:
     same bit-exact binning state."""
     H = W = 3200
     scene = make_shell_scene(3000, S=0, seed=5, radius_px=30.0, image_size=W)
