@@ -1011,6 +1011,43 @@ typedef struct MrgsTsdfConfig {
 } MrgsTsdfConfig;
 int mrgs_tsdf_fuse(const MrgsTsdfConfig* cfg, const MrgsTsdfView* views_dev, float* field, float* weight_debug, void* stream);
 
+/* mrgs_vertex_fuse: colour and material maps fused onto points (mesh vertices) -- the "texturing" pass of extract_mesh_unbounded,
+ * compute_unbounded_tsdf(..., return_rgb=True) over compute_sdf_perframe (:322-373, called at :402).  Per point x (fp32, as given):
+ * a[c] = 0 for every channel c < channels, w = w0.  For each view in table order the acceptance is exactly mrgs_tsdf_fuse's: clip =
+ * [x, 1] @ proj, z = clip.w, ndc = clip.xy / z; accepted only if -1 < ndc.x, ndc.y < 1 and z > 0; tap position p = clamp((ndc + 1) / 2 *
+ * (S - 1), 0, S - 1) (S = W for x, H for y), its four corners under border padding; with depth_trunc > 0 all four depth texels must lie in
+ * (0, depth_trunc]; the weights w00 = (1-tx)(1-ty), w01 = tx(1-ty), w10 = (1-tx)ty, w11 = tx ty are formed once, d = d00 w00 + d01 w01 +
+ * d10 w10 + d11 w11, sdf = d - z, accepted only if sdf > -trunc.  If accepted, for every channel s[c] = a00 w00 + a01 w01 + a10 w10 +
+ * a11 w11 (the same four weights, in that order) and a[c] = (a[c] w + s[c]) / (w + 1); after all channels w += 1.  A point in front of the
+ * seen surface (large positive sdf) contributes, as in the reference: there is no other occlusion test.
+ * w0 = 1 is the reference's texturing rule (its weights start at 1 and its rgbs at 0: after k accepted views the value is sum / (k + 1));
+ * w0 = 0 is the plain mean, 0 where no view accepts (the bounded mode, where the reference delegates to Open3D: parity unpinned).  No
+ * other w0 is served.  out [n_points, channels] holds a, weight [n_points] (or NULL) the final w.
+ * The attribute maps are channel-last fp32 [H, W, channels], channels a multiple of 4 (pad with anything: channels do not mix), and
+ * 16-byte aligned.  Those pointers live in device memory where this call cannot see them: the caller guarantees the alignment (the
+ * Python layer does; a misaligned map faults).  ONE launch per call, whatever the number of views; no atomics: bitwise repeatable.
+ * Codes, before any HIP call: MRGS_E_BAD_ARG for a wrong struct_size, channels not in {4, 8, 12, 16}, w0 not in {0, 1}, trunc not > 0,
+ * n_views < 0, n_points < 0, NULL points or out with n_points > 0, a NULL table with n_views > 0, out not 16-byte aligned;
+ * MRGS_E_UNSUPPORTED for 2^39 points or more (the launch's grid, as mrgs_tsdf_fuse).  n_points = 0 returns MRGS_OK and launches nothing.
+ * n_views = 0 is served: out is 0 and weight is w0. */
+typedef struct MrgsAttrView {
+    float proj[16];          /* full_proj_transform, row-major */
+    const float* depth;      /* device fp32 [H, W] */
+    const float* attr;       /* device fp32 [H, W, channels], channel-last, 16-byte aligned */
+    int32_t H, W;
+} MrgsAttrView;
+typedef struct MrgsVertexFuseConfig {
+    uint32_t struct_size;    /* = sizeof(MrgsVertexFuseConfig) */
+    int32_t n_views;
+    int64_t n_points;
+    int32_t channels;        /* 4, 8, 12 or 16 */
+    int32_t w0;              /* 0 or 1 */
+    float trunc;
+    float depth_trunc;       /* > 0: texel validity as above; <= 0: off */
+} MrgsVertexFuseConfig;
+int mrgs_vertex_fuse(const MrgsVertexFuseConfig* cfg, const MrgsAttrView* views_dev, const float* points, float* out, float* weight,
+                     void* stream);
+
 /* Marching tetrahedra over the lattice of `field` [n0, n1, n2] (index (i0 n1 + i1) n2 + i2, point origin + spacing * (i0, i1, i2)).
  * Every cube is cut into the six Kuhn tetrahedra (c, c+e_a, c+e_a+e_b, c+e_a+e_b+e_c); a point is inside iff F < level; a vertex sits on
  * every lattice edge (3 axes, 3 face diagonals, the body diagonal) whose ends differ, at p_a + (level - F_a) / (F_b - F_a) (p_b - p_a) with

@@ -168,6 +168,15 @@ class MrgsTsdfConfig(_Sized):
                 ("trunc", c_float), ("depth_trunc", c_float), ("points", c_void_p)]
 
 
+class MrgsAttrView(ctypes.Structure):
+    _fields_ = [("proj", c_float * 16), ("depth", c_void_p), ("attr", c_void_p), ("H", c_int32), ("W", c_int32)]
+
+
+class MrgsVertexFuseConfig(_Sized):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("n_views", c_int32), ("n_points", c_int64), ("channels", c_int32), ("w0", c_int32),
+                ("trunc", c_float), ("depth_trunc", c_float)]
+
+
 class MrgsMeshConfig(_Sized):
     _fields_ = [("struct_size", ctypes.c_uint32), ("n0", c_int32), ("n1", c_int32), ("n2", c_int32), ("slab_planes", c_int32),
                 ("contracted", c_int32), ("level", c_float), ("origin", c_float * 3), ("spacing", c_float * 3), ("center", c_float * 3),
@@ -304,6 +313,7 @@ SYMBOLS = {
     "mrgs_env_select": (ctypes.c_int, [c_int64, c_void_p, c_int64, c_void_p, c_size_t, c_void_p, c_void_p]),
     "mrgs_env_densify_stats": (ctypes.c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "mrgs_tsdf_fuse": (ctypes.c_int, [ctypes.POINTER(MrgsTsdfConfig), c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mrgs_vertex_fuse": (ctypes.c_int, [ctypes.POINTER(MrgsVertexFuseConfig), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "mrgs_mesh_ws_bytes": (c_size_t, [ctypes.POINTER(MrgsMeshConfig)]),
     "mrgs_mesh_count": (ctypes.c_int, [ctypes.POINTER(MrgsMeshConfig), c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
     "mrgs_mesh_emit": (ctypes.c_int, [ctypes.POINTER(MrgsMeshConfig), c_void_p, c_void_p, c_size_t, ctypes.POINTER(c_int64), c_void_p, c_void_p,

@@ -7,6 +7,7 @@
 //   fuse      one thread per sample, neighbouring lanes neighbouring lattice points along the fastest axis; the view loop runs inside the
 //             kernel with tsdf and w in registers, the views come from a device table (wave-uniform reads), the field is written once.
 //             Algorithmic bytes: 4 per sample written, the depth maps through L2 (their taps are neighbours where the lanes are).
+//   attributes  the texturing pass: vertex_fuse_kernel below, a sibling of the fusion with CP channel accumulators per point.
 //   count     per slab of planes along the slowest axis, one thread per lattice point: the 7-bit mask of its crossing edges (an edge is
 //             owned by its lower end), the triangles of the cube above it, an in-block scan; one word per point, three sums per block,
 //             then one workgroup scans the three rows of sums (block_counts_exclusive_scan, mrgs_wave.h) into block offsets and the running totals.  The host reads 16 bytes.
@@ -89,6 +90,88 @@ __global__ __launch_bounds__(256) void tsdf_fuse_kernel(FuseArgs a, const MrgsTs
         w += 1.0f;
     }
     field[idx] = tsdf;
+    if (weight) weight[idx] = w;
+}
+
+// ---- vertex attributes -----------------------------------------------------------------------------------------------------------
+// The "texturing" pass (compute_unbounded_tsdf(..., return_rgb=True), utils/mesh_utils.py:322-373, called at :402): per point the running
+// mean of CP attribute channels over the views that accept it, acceptance exactly tsdf_fuse_kernel's.  One thread per point, the view
+// loop inside the kernel with a[CP] and w in registers (CP is a template parameter: the accumulators are never indexed dynamically),
+// the table read wave-uniformly, one launch per call.  The maps are channel-last, so a corner is CP / 4 16-byte loads, and those sit
+// behind the acceptance branch: a rejected view costs its four depth texels and nothing else.  No atomics, no LDS: bitwise repeatable.
+// Mesh vertices arrive ordered by owning lattice point (mrgs_mesh_emit), so neighbouring lanes tap neighbouring texels.
+// Algorithmic bytes: 12 read and 4 CP (+ 4) written per point; per accepted (point, view) pair 16 B of depth and 16 CP B of attributes
+// pass through L2.
+// The map pointers come out of the device table, where the compiler cannot see their address space: named global here, so that the taps
+// are global loads with counted waits, not flat ones that wait for everything.
+typedef float Float4 __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(1))) float GlobalF;
+typedef __attribute__((address_space(1))) Float4 GlobalF4;
+struct VertexFuseArgs {
+    int n_views;
+    long long n;
+    float w0, trunc, depth_trunc;
+};
+
+// Above CP = 4 the occupancy target is 4 waves per SIMD: at the default target the scheduler keeps 7 by holding the 4 (CP / 4) corner loads
+// of a view back to two to four in flight (66-68 VGPRs); with the target lowered it issues all of them before the first use.
+template <int CP>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, CP > 4 ? 4 : 8)))
+void vertex_fuse_kernel(VertexFuseArgs a, const MrgsAttrView* __restrict__ views, const float* __restrict__ points, float* __restrict__ out,
+                        float* __restrict__ weight)
+{
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= a.n) return;
+    const float x = points[3 * idx], y = points[3 * idx + 1], z = points[3 * idx + 2], trunc = a.trunc;
+    float acc[CP];
+#pragma unroll
+    for (int c = 0; c < CP; ++c) acc[c] = 0.0f;
+    float w = a.w0;
+    for (int v = 0; v < a.n_views; ++v) {
+        const MrgsAttrView& vw = views[v];
+        const float* m = vw.proj;
+        const float cx = x * m[0] + y * m[4] + z * m[8] + m[12];
+        const float cy = x * m[1] + y * m[5] + z * m[9] + m[13];
+        const float cw = x * m[3] + y * m[7] + z * m[11] + m[15];
+        const float nx = cx / cw, ny = cy / cw;
+        const int H = vw.H, W = vw.W;
+        if (!(nx > -1.0f && nx < 1.0f && ny > -1.0f && ny < 1.0f && cw > 0.0f) || H < 1 || W < 1) continue;
+        const float px = fminf(fmaxf((nx + 1.0f) * 0.5f * (float)(W - 1), 0.0f), (float)(W - 1));
+        const float py = fminf(fmaxf((ny + 1.0f) * 0.5f * (float)(H - 1), 0.0f), (float)(H - 1));
+        const float fx = floorf(px), fy = floorf(py);
+        const int x0 = (int)fx, y0 = (int)fy, x1 = min(x0 + 1, W - 1), y1 = min(y0 + 1, H - 1);
+        const float tx = px - fx, ty = py - fy;
+        const GlobalF* __restrict__ dm = (const GlobalF*)vw.depth;
+        const size_t i00 = (size_t)y0 * W + x0, i01 = (size_t)y0 * W + x1, i10 = (size_t)y1 * W + x0, i11 = (size_t)y1 * W + x1;
+        const float d00 = dm[i00], d01 = dm[i01], d10 = dm[i10], d11 = dm[i11];
+        if (a.depth_trunc > 0.0f) {
+            const float lo = fminf(fminf(d00, d01), fminf(d10, d11)), hi = fmaxf(fmaxf(d00, d01), fmaxf(d10, d11));
+            if (!(lo > 0.0f && hi <= a.depth_trunc)) continue;
+        }
+        const float w00 = (1.0f - tx) * (1.0f - ty), w01 = tx * (1.0f - ty), w10 = (1.0f - tx) * ty, w11 = tx * ty;
+        const float d = d00 * w00 + d01 * w01 + d10 * w10 + d11 * w11;
+        const float sdf = d - cw;
+        if (!(sdf > -trunc)) continue;
+        const GlobalF4* __restrict__ am = (const GlobalF4*)vw.attr;
+        const float wp = w + 1.0f;
+        Float4 t00[CP / 4], t01[CP / 4], t10[CP / 4], t11[CP / 4];      // every load of the view before the first use
+#pragma unroll
+        for (int q = 0; q < CP / 4; ++q) {
+            t00[q] = am[i00 * (CP / 4) + q]; t01[q] = am[i01 * (CP / 4) + q]; t10[q] = am[i10 * (CP / 4) + q]; t11[q] = am[i11 * (CP / 4) + q];
+        }
+#pragma unroll
+        for (int q = 0; q < CP / 4; ++q) {
+            const Float4 a00 = t00[q], a01 = t01[q], a10 = t10[q], a11 = t11[q];
+            acc[4 * q] = (acc[4 * q] * w + (a00.x * w00 + a01.x * w01 + a10.x * w10 + a11.x * w11)) / wp;
+            acc[4 * q + 1] = (acc[4 * q + 1] * w + (a00.y * w00 + a01.y * w01 + a10.y * w10 + a11.y * w11)) / wp;
+            acc[4 * q + 2] = (acc[4 * q + 2] * w + (a00.z * w00 + a01.z * w01 + a10.z * w10 + a11.z * w11)) / wp;
+            acc[4 * q + 3] = (acc[4 * q + 3] * w + (a00.w * w00 + a01.w * w01 + a10.w * w10 + a11.w * w11)) / wp;
+        }
+        w = wp;
+    }
+    float4* __restrict__ o = (float4*)out + (size_t)idx * (CP / 4);
+#pragma unroll
+    for (int q = 0; q < CP / 4; ++q) o[q] = make_float4(acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]);
     if (weight) weight[idx] = w;
 }
 
@@ -414,6 +497,30 @@ extern "C" int mrgs_tsdf_fuse(const MrgsTsdfConfig* cfg, const MrgsTsdfView* vie
     for (int ax = 0; ax < 3; ++ax) { a.origin[ax] = cfg->origin[ax]; a.spacing[ax] = cfg->spacing[ax]; a.center[ax] = cfg->center[ax]; }
     a.radius = cfg->radius; a.trunc = cfg->trunc; a.depth_trunc = cfg->depth_trunc; a.points = cfg->points;
     tsdf_fuse_kernel<<<dim3(blocks256(n)), 256, 0, (hipStream_t)stream>>>(a, views, field, weight_debug);
+    return MRGS_LAUNCH_STATUS();
+}
+
+extern "C" int mrgs_vertex_fuse(const MrgsVertexFuseConfig* cfg, const MrgsAttrView* views, const float* points, float* out, float* weight,
+                                void* stream)
+{
+    if (!cfg || cfg->struct_size != sizeof(MrgsVertexFuseConfig)) return MRGS_E_BAD_ARG;
+    const int cp = cfg->channels;
+    if ((cp != 4 && cp != 8 && cp != 12 && cp != 16) || (cfg->w0 != 0 && cfg->w0 != 1) || !(cfg->trunc > 0.0f)) return MRGS_E_BAD_ARG;
+    if (cfg->n_views < 0 || cfg->n_points < 0) return MRGS_E_BAD_ARG;
+    const long long n = cfg->n_points;
+    if (n >= (1ll << 31) * 256) return MRGS_E_UNSUPPORTED;
+    if (n == 0) return MRGS_OK;
+    if (!points || !out || ((uintptr_t)out & 15) || (cfg->n_views > 0 && !views)) return MRGS_E_BAD_ARG;
+    VertexFuseArgs a;
+    a.n_views = cfg->n_views; a.n = n; a.w0 = (float)cfg->w0; a.trunc = cfg->trunc; a.depth_trunc = cfg->depth_trunc;
+    const dim3 grid(blocks256(n));
+    hipStream_t st = (hipStream_t)stream;
+    switch (cp) {
+    case 4: vertex_fuse_kernel<4><<<grid, 256, 0, st>>>(a, views, points, out, weight); break;
+    case 8: vertex_fuse_kernel<8><<<grid, 256, 0, st>>>(a, views, points, out, weight); break;
+    case 12: vertex_fuse_kernel<12><<<grid, 256, 0, st>>>(a, views, points, out, weight); break;
+    default: vertex_fuse_kernel<16><<<grid, 256, 0, st>>>(a, views, points, out, weight); break;
+    }
     return MRGS_LAUNCH_STATUS();
 }
 

@@ -96,19 +96,93 @@ def read_ply_vertices(path: str):
 def save_mesh_ply(path: str, mesh_or_vertices, triangles=None):
     """Triangle mesh as a binary little-endian PLY: `vertex` with float x, y, z and `face` with `list uchar int vertex_indices` -- the layout
     of o3d.io.write_triangle_mesh for a mesh without colours or normals (train_refnerf.py:1468), read back by load_mesh_ply and by the
-    reference's load_mesh_from_ply.  Takes a mesh (`.vertices`, `.triangles`) or the two arrays."""
+    reference's load_mesh_from_ply.  Takes a mesh (`.vertices`, `.triangles`) or the two arrays.  A mesh that carries an "rgb" attribute
+    group (mesh.TriangleMesh) is written with `uchar red green blue` after x, y, z, round(clip(c, 0, 1) * 255), as
+    o3d.io.write_triangle_mesh writes a coloured mesh; without the group the bytes are those of the two arrays."""
     v, t = (mesh_or_vertices.vertices, mesh_or_vertices.triangles) if triangles is None else (mesh_or_vertices, triangles)
     v = np.ascontiguousarray(np.asarray(v), dtype="<f4").reshape(-1, 3)
     t = np.ascontiguousarray(np.asarray(t), dtype="<i4").reshape(-1, 3)
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-    header = ["ply", "format binary_little_endian 1.0", f"element vertex {v.shape[0]}", "property float x", "property float y", "property float z",
-              f"element face {t.shape[0]}", "property list uchar int vertex_indices", "end_header"]
+    coloured = triangles is None and "rgb" in (getattr(mesh_or_vertices, "layout", None) or {})
+    header = ["ply", "format binary_little_endian 1.0", f"element vertex {v.shape[0]}", "property float x", "property float y", "property float z"]
+    rows = v
+    if coloured:
+        header += ["property uchar red", "property uchar green", "property uchar blue"]
+        rows = np.empty(v.shape[0], dtype=[("xyz", "<f4", (3,)), ("rgb", "u1", (3,))])
+        rows["xyz"] = v
+        rows["rgb"] = np.round(np.clip(np.asarray(mesh_or_vertices.vertex_colors, dtype=np.float64).reshape(-1, 3), 0.0, 1.0) * 255.0).astype(np.uint8)
+    header += [f"element face {t.shape[0]}", "property list uchar int vertex_indices", "end_header"]
     faces = np.empty(t.shape[0], dtype=[("n", "u1"), ("idx", "<i4", (3,))])
     faces["n"], faces["idx"] = 3, t
     with open(path, "wb") as f:
         f.write(("\n".join(header) + "\n").encode("ascii"))
-        f.write(v.tobytes())
+        f.write(rows.tobytes())
         f.write(faces.tobytes())
+
+
+MATERIAL_PLY_PROPERTIES = ("x", "y", "z", "red", "green", "blue", "normal_x", "normal_y", "normal_z", "diffuse_r", "diffuse_g", "diffuse_b",
+                           "albedo_r", "albedo_g", "albedo_b", "metallic_0", "roughness_0")
+# (attribute group of the mesh, its channels in the file), in file order after x, y, z
+_MATERIAL_GROUPS = (("rgb", 3), ("normal", 3), ("diffuse", 3), ("base_color", 3), ("metallic", 1), ("roughness", 1))
+
+
+def save_material_ply(path: str, mesh):
+    """The material mesh of extract_mesh_bouned_with_material (utils/mesh_utils.py:278-306) as a binary little-endian PLY: `vertex` with
+    the double properties MATERIAL_PLY_PROPERTIES in that order, `face` with `list uchar int vertex_indices`.  `mesh` carries the groups
+    rgb, normal, diffuse, base_color (albedo_*), metallic and roughness (mesh.TriangleMesh.attribute); of a group wider than the file's
+    columns the first ones are taken.  Values are the fp32 attributes widened, normals stored as they are: the reference passes them through
+    8-bit colour and `* 2 - 1`, this does not quantise."""
+    v = np.asarray(mesh.vertices, dtype=np.float64).reshape(-1, 3)
+    t = np.ascontiguousarray(np.asarray(mesh.triangles), dtype="<i4").reshape(-1, 3)
+    cols = [v]
+    for group, width in _MATERIAL_GROUPS:
+        a = mesh.attribute(group)
+        a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        if a.shape[0] != v.shape[0] or a.shape[1] < width:
+            raise ValueError(f"attribute group {group!r} must be [V,{width}]")
+        cols.append(a[:, :width].astype(np.float64))
+    data = np.ascontiguousarray(np.concatenate(cols, axis=1), dtype="<f8")
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    header = ["ply", "format binary_little_endian 1.0", f"element vertex {v.shape[0]}"] + [f"property double {p}" for p in MATERIAL_PLY_PROPERTIES] + \
+             [f"element face {t.shape[0]}", "property list uchar int vertex_indices", "end_header"]
+    faces = np.empty(t.shape[0], dtype=[("n", "u1"), ("idx", "<i4", (3,))])
+    faces["n"], faces["idx"] = 3, t
+    with open(path, "wb") as f:
+        f.write(("\n".join(header) + "\n").encode("ascii"))
+        f.write(data.tobytes())
+        f.write(faces.tobytes())
+
+
+def load_material_ply(path: str):
+    """What save_material_ply wrote: dict(vertices float64 [V,3], triangles int32 [T,3], rgb, normal, diffuse, base_color [V,3], metallic,
+    roughness [V,1], all float64)."""
+    with open(path, "rb") as f:
+        head = b""
+        while not head.endswith(b"end_header\n"):
+            line = f.readline()
+            if not line:
+                raise ValueError("PLY header not terminated")
+            head += line
+        lines = [ln.split() for ln in head.decode("ascii").splitlines()]
+        if lines[0] != ["ply"] or ["format", "binary_little_endian", "1.0"] not in lines:
+            raise ValueError("not a binary little-endian PLY file")
+        elements = [ln for ln in lines if ln and ln[0] == "element"]
+        props = [ln[1:] for ln in lines if ln and ln[0] == "property"]
+        if [e[1] for e in elements] != ["vertex", "face"] or props[:-1] != [["double", p] for p in MATERIAL_PLY_PROPERTIES] or \
+                props[-1] != ["list", "uchar", "int", "vertex_indices"]:
+            raise ValueError("not a material PLY: expected the double vertex properties " + " ".join(MATERIAL_PLY_PROPERTIES))
+        nv, nf = int(elements[0][2]), int(elements[1][2])
+        ncol = len(MATERIAL_PLY_PROPERTIES)
+        data = np.frombuffer(f.read(nv * ncol * 8), dtype="<f8").reshape(nv, ncol).astype(np.float64)
+        faces = np.frombuffer(f.read(nf * 13), dtype=[("n", "u1"), ("idx", "<i4", (3,))])
+        if len(faces) != nf or (faces["n"] != 3).any():
+            raise ValueError("only triangle faces are read")
+    out = dict(vertices=data[:, :3].copy(), triangles=np.ascontiguousarray(faces["idx"], dtype=np.int32))
+    at = 3
+    for group, width in _MATERIAL_GROUPS:
+        out[group] = data[:, at:at + width].copy()
+        at += width
+    return out
 
 
 def load_mesh_ply(path: str):

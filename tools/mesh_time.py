@@ -4,6 +4,12 @@ device), then on plain lattices of 256^3 and 512^3 points over the cube [-1.25, 
   fusion          mrgs_tsdf_fuse, one launch over all views
   count + emit    marching tetrahedra (the 16-byte host read of V and T lies inside the window), with V and T
   clusters        mrgs_mesh_clusters (hooking, pointer jumping, per-label counts); post_process_mesh as a whole beside it
+  texturing       mrgs_vertex_fuse (fuse_vertex_attributes) on the vertices of that lattice's mesh, all 120 views, CP = 4 and CP = 16
+                  channels; the attribute maps are uniform noise made on the device (the kernel's traffic does not depend on their
+                  values).  Beside each, in the same run: the fp32 torch form of the same rule, the grid_sample loop of
+                  compute_unbounded_tsdf(..., return_rgb=True) (utils/mesh_utils.py:352-368) with the maps already on the device
+                  (channel-first, as grid_sample takes them) -- the best a ROCm user has without this kernel -- and the largest
+                  difference of the two results over the vertices on which both count the same views.
 Beside the fusion at 256^3: the fp32 torch form of the same rule, the reference's own loop (compute_unbounded_tsdf /
 compute_sdf_perframe, utils/mesh_utils.py:322-373) restated, in the same run, and the largest difference of the two fields.
 Each figure is the time between two device events around a batch of 4 calls, divided by 4, after a warm-up call: the minimum of 5
@@ -61,6 +67,49 @@ def torch_fuse(views, points, trunc):
     return tsdfs
 
 
+def torch_texture(views, points, trunc):
+    """compute_unbounded_tsdf(..., return_rgb=True) without contraction, fp32 on the device; views are (proj, depth [1,H,W], maps [C,H,W])."""
+    tsdfs, weights = torch.ones_like(points[:, 0]), torch.ones_like(points[:, 0])
+    rgbs = torch.zeros((points.shape[0], views[0][2].shape[0]), device=points.device)
+    for proj, depth, amap in views:
+        new_points = torch.cat([points, torch.ones_like(points[..., :1])], dim=-1) @ proj
+        z = new_points[..., -1:]
+        pix = new_points[..., :2] / new_points[..., -1:]
+        mask = ((pix > -1.0) & (pix < 1.0) & (z > 0)).all(dim=-1)
+        sampled = torch.nn.functional.grid_sample(depth[None], pix[None, None], mode="bilinear", padding_mode="border", align_corners=True).reshape(-1, 1)
+        rgb = torch.nn.functional.grid_sample(amap[None], pix[None, None], mode="bilinear", padding_mode="border", align_corners=True).reshape(amap.shape[0], -1).T
+        sdf = (sampled - z).flatten()
+        mask = mask & (sdf > -trunc)
+        sdf = torch.clamp(sdf / trunc, min=-1.0, max=1.0)[mask]
+        w = weights[mask]
+        wp = w + 1
+        tsdfs[mask] = (tsdfs[mask] * w + sdf) / wp
+        rgbs[mask] = (rgbs[mask] * w[:, None] + rgb[mask]) / wp[:, None]
+        weights[mask] = wp
+    return rgbs, weights
+
+
+def time_texturing(n, m, cams, depthmaps, trunc, fmt):
+    dev = m.vertices_device.device
+    V = m.vertices_device.shape[0]
+    for cp in (4, 16):
+        gen = torch.Generator(device=dev).manual_seed(cp)
+        packed = [torch.rand(SIZE, SIZE, cp, device=dev, generator=gen) for _ in cams]
+        views = [(c.full_proj_transform, d, a) for c, d, a in zip(cams, depthmaps, packed)]
+        t_k, (out, w) = event_ms(lambda: mesh.fuse_vertex_attributes(m.vertices_device, views, trunc, return_weight=True))
+        pairs = float((w - 1).sum())
+        print(f"lattice {n}^3: texturing V {V}, CP {cp}: {min(t_k):.3f} ms (batches {fmt(t_k)}); {pairs / V:.1f} accepted views per vertex, "
+              f"{pairs * 16 * (cp + 1) / 2 ** 30:.2f} GiB of taps, maps {len(cams) * SIZE * SIZE * cp * 4 / 2 ** 30:.2f} GiB", flush=True)
+        first = [(c.full_proj_transform, d, a.permute(2, 0, 1).contiguous()) for c, d, a in zip(cams, depthmaps, packed)]
+        t_t, (ref, ref_w) = event_ms(lambda: torch_texture(first, m.vertices_device, trunc))
+        same = ref_w == w
+        print(f"lattice {n}^3: torch form of the texturing, CP {cp}: {min(t_t):.3f} ms (batches {fmt(t_t)}), ratio {min(t_t) / min(t_k):.1f}x; "
+              f"{int((~same).sum())} of {V} vertices count other views (a decision at a threshold), the others differ by at most "
+              f"{float((ref - out)[same].abs().max()):.3e}", flush=True)
+        del packed, views, first, out, w, ref, ref_w
+        torch.cuda.empty_cache()
+
+
 def main():
     from materialrefgs_amd.renderer import render_surfel
     dev = torch.device("cuda:0")
@@ -98,7 +147,9 @@ def main():
         t_pp, kept = event_ms(lambda: mesh.post_process_mesh(m, 50))
         print(f"lattice {n}^3: clusters {min(t_cl):.3f} ms (batches {fmt(t_cl)}); post_process_mesh(50) {min(t_pp):.3f} ms (batches {fmt(t_pp)}) "
               f"-> V {kept.vertices_device.shape[0]}, T {kept.triangles_device.shape[0]}", flush=True)
-        del field, m, kept
+        del field, kept
+        time_texturing(n, m, cams, ex.depthmaps, trunc, fmt)
+        del m
         torch.cuda.empty_cache()
 
 
