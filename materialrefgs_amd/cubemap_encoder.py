@@ -96,8 +96,15 @@ class CubemapEncoder(_CubeModule):
 
 
 def mip_resolutions(num_levels, base_resolution, per_level_scale):
-    """Side lengths of the levels: ceil(base * scale^i), i = 0 .. num_levels-1 (default 4, 16, 64, 256)."""
-    return [int(np.ceil(float(base_resolution) * float(per_level_scale) ** i)) for i in range(num_levels)]
+    """Side lengths of the levels (default 4, 16, 64, 256): the reference's recurrence (:126-133) -- a running float L = base, per
+    level ceil(L), then L *= scale.  Not ceil(base * scale^i): for a non-integer scale the running product rounds differently
+    (base 1, scale 2^(1/3): the running product reaches 4.0 at level 6, where the power gives ceil(4.000000000000001) = 5), and
+    the level sizes are the parameter shapes a checkpoint is loaded into."""
+    sizes, L = [], float(base_resolution)
+    for _ in range(num_levels):
+        sizes.append(int(np.ceil(L)))
+        L = L * per_level_scale
+    return sizes
 
 
 class MipCubemapEncoder(_CubeModule):

@@ -11,7 +11,8 @@ Layouts: inputs [B,3], cubemap [6,C,L,L], fail_value [C], outputs [C,B] (cubemap
 PARITY: the CUDA extension cannot be built in this image and ships no test vectors, so this restatement is unpinned against its
 binary; it is float64 numpy written line by line from the cited source, and the HIP kernels are compared with it.  (The reference
 builds with -use_fast_math, setup.py:10: its own divisions and the floor are approximate, so its fp32 results carry ~1e-6 relative
-noise of their own.)
+noise of their own.)  What the geometry of a cube fixes -- which texel lies across each edge and at each vertex, the weights, the
+gradient's signs -- is checked on this restatement and on the HIP kernels alike by tests/test_cubemap_seams.py.
 """
 import numpy as np
 
@@ -40,6 +41,28 @@ def compute_uv(d):
         p = s & (z >= 0); face[p] = 4; v[p] = -v[p]
         n = s & ~(z >= 0); face[n] = 5
     return face, np.stack([u, v], 1)
+
+
+def pixel_coords(d, L):
+    """Pixel coordinates (pu, pv) [B] each, float64, of the directions on their faces: the numbers every fetch floors or truncates
+    (:357-362, :407-411).  Tests use them to tell which samples sit within rounding of a texel boundary."""
+    _, uv = compute_uv(np.asarray(d, np.float64))
+    return (uv[:, 0] * 0.5 + 0.5) * L, (-uv[:, 1] * 0.5 + 0.5) * L
+
+
+def face_dir(f, u, v):
+    """Inverse of compute_uv: the direction on the unit cube with face coordinates (u, v) on face f (scalars or arrays)."""
+    one = np.ones_like(np.asarray(u, np.float64))
+    x, y, z = {0: (one, -v, -u), 1: (-one, -v, u), 2: (u, one, v), 3: (u, -one, v), 4: (u, -v, one), 5: (-u, -v, -one)}[f]
+    return np.stack(np.broadcast_arrays(x, y, z), -1).astype(np.float64)
+
+
+def texel_centre_dirs(L):
+    """[6 * L * L, 3] directions through the texel centres, in the order of cubemap[f, :, y, x] flattened over (f, y, x)."""
+    c = (np.arange(L) + 0.5) / L * 2 - 1
+    ys, xs = np.meshgrid(np.arange(L), np.arange(L), indexing="ij")
+    u, v = c[xs], -c[ys]                                       # pixel row = (-v * .5 + .5) L
+    return np.concatenate([face_dir(f, u, v).reshape(-1, 3) for f in range(6)])
 
 
 def edge_table(L, flag, face, x, y):
