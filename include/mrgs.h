@@ -1090,6 +1090,31 @@ int mrgs_mesh_select(int64_t V, int64_t T, const int32_t* triangles, const int32
 int mrgs_mesh_reindex(int64_t V_old, int64_t V_new, const int32_t* new_to_old, int32_t* remap_ws, int64_t T, int32_t* triangles,
                       void* stream);
 
+/* The edge mask of the multi-view loss (dilated_edges_imgs, utils/image_utils.py:109-116: cv2.Canny + cv2.dilate on the 8-bit normal map),
+ * defined here in integers -- parity with a particular OpenCV build is not claimed:
+ *   1 quantise  v = img * 255 (one fp32 multiply), u = trunc(v) as int32, & 255 (negative values wrap: -0.5 -> -127 -> 129); a v that is
+ *               not finite or has |v| >= 2^31 gives 0
+ *   2 grey      g = (9798 R + 19235 G + 3735 B + 16384) >> 15
+ *   3 Sobel     3 x 3, replicate border on g: dx = (g[y-1,x+1] + 2 g[y,x+1] + g[y+1,x+1]) - (the same at x-1), dy = (row y+1: g[x-1] +
+ *               2 g[x] + g[x+1]) - (row y-1); m = |dx| + |dy|, 0 outside the image
+ *   4 thresholds  low = floor(min(thres1, thres2)), high = floor(max(thres1, thres2))
+ *   5 non-maximum suppression  ax = |dx|, ay = |dy| << 15, t22 = ax * 13573, t67 = t22 + (ax << 16); a pixel with m > low is a CANDIDATE
+ *               if ay < t22: m > m[y,x-1] and m >= m[y,x+1]; else if ay > t67: m > m[y-1,x] and m >= m[y+1,x]; else, with s = -1 where
+ *               dx and dy differ in sign and +1 otherwise: m > m[y-1,x-s] and m > m[y+1,x+s].  A candidate with m > high is STRONG
+ *   6 hysteresis  a candidate is an edge exactly if its 8-connected component of candidates holds a strong pixel
+ *   7 dilate    a = dilate_size / 2; out[y,x] = OR of edge[y+oy, x+ox] over oy, ox in [-a, dilate_size - 1 - a], positions outside the
+ *               image ignored
+ *   8 result    out as 0 / 1; with invert, 1 - out (the loss's keep mask)
+ * img [3,H,W] fp32, out [H,W] bytes, classes_out (nullable) [H,W] bytes: 0 none, 1 candidate, 2 strong.  Device pointers, the caller's
+ * workspace (mrgs_edges_ws_bytes, 256-byte aligned; its contents are scratch) and stream: four launches, nothing is allocated or read
+ * back and the call does not synchronise, so it may be captured into a graph.  The result is a set: no value depends on the order of
+ * the atomics of the component labelling.
+ * Codes, before any HIP call: MRGS_E_BAD_ARG for H or W <= 0, dilate_size outside 1..31, a NaN threshold, a NULL img, out or ws;
+ * MRGS_E_UNSUPPORTED for H W >= 2^31; MRGS_E_WORKSPACE for ws_bytes below the size query's answer (0 for sizes the call refuses). */
+size_t mrgs_edges_ws_bytes(int32_t H, int32_t W);
+int mrgs_edge_mask(const float* img, int32_t H, int32_t W, int32_t dilate_size, float thres1, float thres2, int32_t invert, uint8_t* out,
+                   uint8_t* classes_out, void* ws, size_t ws_bytes, void* stream);
+
 /* Introspection used by the parity tests: copies of internal state in the reference's layouts.
  * which: 0 depths f32[P], 1 means2D f32[P,2], 2 transMat f32[P,9], 3 normal_opacity f32[P,4], 4 rgb f32[P,3],
  * 5 tiles_touched u32[P], 6 clamped u8[P,3], 7 point_list u32[R], 8 ranges u32[tiles,2], 9 final_T f32[3,H,W],

@@ -321,6 +321,9 @@ SYMBOLS = {
     "mrgs_mesh_clusters": (ctypes.c_int, [c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "mrgs_mesh_select": (ctypes.c_int, [c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
     "mrgs_mesh_reindex": (ctypes.c_int, [c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "mrgs_edges_ws_bytes": (c_size_t, [c_int32, c_int32]),
+    "mrgs_edge_mask": (ctypes.c_int, [c_void_p, c_int32, c_int32, c_int32, c_float, c_float, c_int32, c_void_p, c_void_p, c_void_p, c_size_t,
+                                      c_void_p]),
     "mrgs_knn_ws_bytes": (c_size_t, [c_int64]),
     "mrgs_knn_mean_dist2": (ctypes.c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
     "mrgs_mark_visible": (ctypes.c_int, [c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -20,6 +20,7 @@
 // sets, an edge's owner is its smaller set and its kind the set difference, and the winding follows from two parities -- no table.
 #include "mrgs_internal.h"
 #include "mrgs_wave.h"
+#include "mrgs_cc.h"
 
 namespace {
 
@@ -348,24 +349,7 @@ __global__ __launch_bounds__(256) void mesh_emit_kernel(MeshArgs a, const float*
 }
 
 // ---- clusters --------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int cc_find(int* parent, int v)
-{
-    for (;;) {                                                          // links only ever point to a smaller index: the walk ends
-        const int p = __hip_atomic_load(parent + v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (p == v) return v;
-        v = p;
-    }
-}
-__device__ __forceinline__ void cc_union(int* parent, int x, int y)
-{
-    for (;;) {
-        x = cc_find(parent, x); y = cc_find(parent, y);
-        if (x == y) return;
-        if (x < y) { const int s = x; x = y; y = s; }                   // hook the larger root under the smaller
-        if (atomicCAS(parent + x, x, y) == x) return;                   // lost: x is no root any more, someone else made progress
-    }
-}
-
+// cc_find / cc_union: mrgs_cc.h
 __global__ __launch_bounds__(256) void cc_init_kernel(long long V, int* __restrict__ parent, int* __restrict__ counts)
 {
     const long long v = (long long)blockIdx.x * 256 + threadIdx.x;

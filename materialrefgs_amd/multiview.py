@@ -7,7 +7,8 @@ Differences a caller sees:
   * where no pixel passes the geometric check the reference returns None for every term; here the terms are 0 with zero gradient
     (deciding on the host would cost a synchronisation).  `original_weight` is the all-zero map in both.
   * the sample draw is the device sampler's (uniform, seeded from numpy's global generator), not np.random.choice's.
-  * the edge mask comes from the caller's `edges_fn` (the reference's `dilated_edges_imgs`, cv2 Canny + dilation).
+  * the edge mask (the reference's `dilated_edges_imgs`, cv2 Canny + dilation on the host) is computed on the device by
+    materialrefgs_amd.edges, whose definition is this library's own; a caller's `edges_fn` still takes its place.
   * use_virtul_cam, ncc_scale != 1, wo_use_geo_occ_aware and (train_refreal.py) directional_rghmtl_warp_alignment = False raise
     NotImplementedError; all four are off by default.
   * the grey-image NCC (get_consistency_loss2) is a second autograd node, `_WarpNcc`, that follows the first on the same draw and
@@ -22,7 +23,7 @@ import random
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, edges
 
 
 _p = _lib.ptr
@@ -208,7 +209,8 @@ def warp_consistency_loss(view_cam, view_pkg, nearest_cam, nearest_pkg, fg_mask,
     `nearest_cam` / `nearest_pkg`.  Returns (geo, base_colour, metallic, roughness, weight_map, n_valid): 0-d device tensors for the
     terms (weights a(it) * multi_view_ncc_weight and b(it) * metallic / roughness weight applied; 0 where a term is switched off),
     the detached [H,W] weight map and n_valid as a 0-d int32 device tensor.  The material terms run when iteration > 10000.
-    fg_mask: [H,W] foreground of the view; keep_mask: [H,W] bool, False on an edge (None: keep all).  `samples`: int32 pixel indices
+    fg_mask: [H,W] foreground of the view; keep_mask: [H,W] bool (or 0 / 1 bytes, which are used as they are), False on an edge (None:
+    keep all).  `samples`: int32 pixel indices
     (y * W + x) to use instead of the device draw (tests replay a recorded draw); `out_samples`: int32 [sample_num] device tensor that
     receives the draw.  No host read.
     grey_v / grey_n ([H,W] or [1,H,W] device tensors, both or neither): the grey photographs of the two cameras.  With them the call
@@ -299,11 +301,13 @@ def _drop_in(viewpoint_cam, scene, opt, gaussians, pipe, render, render_pkg, mas
         raise RuntimeError("materialrefgs_amd.multiview needs device tensors (libmrgs.so has no CPU path)")
     keep = None
     if getattr(opt, "edge_aware_in_warp", False):
-        if edges_fn is None:
-            raise ValueError("calc_warp_loss: opt.edge_aware_in_warp is set, pass edges_fn= (the reference's dilated_edges_imgs)")
         with torch.no_grad():
-            H, W = render_pkg["surf_depth"].shape[-2:]
-            keep = ~torch.as_tensor(edges_fn(render_pkg["rend_normal"], dilate_size=7)).reshape(H, W).bool()
+            if edges_fn is None:
+                # the kernel's bytes as they are: _WarpLoss takes a uint8 map without a conversion launch
+                keep = edges.edge_mask(render_pkg["rend_normal"], dilate_size=7, invert=True).view(torch.uint8)
+            else:
+                H, W = render_pkg["surf_depth"].shape[-2:]
+                keep = ~torch.as_tensor(edges_fn(render_pkg["rend_normal"], dilate_size=7)).reshape(H, W).bool()
     if len(viewpoint_cam.nearest_id) == 0:
         return None
     nearest_cam = scene.getTrainCameras()[random.sample(viewpoint_cam.nearest_id, 1)[0]]
@@ -334,7 +338,8 @@ def _drop_in(viewpoint_cam, scene, opt, gaussians, pipe, render, render_pkg, mas
 def calc_warp_loss(viewpoint_cam, scene, opt, gaussians, dataset, pipe, render, render_pkg, albeldo_images, mtl_images, rgh_images, mask_images,
                    iteration, debug_path, bg, use_metallic_warp=False, use_roughness_warp=False, *, edges_fn=None, samples=None):
     """train_refnerf.py:414-739 / train_glossy.py:442-772: (None, None, base_color_loss, metallic_warp_loss, roughness_warp_loss,
-    original_weight, None, None).  `edges_fn`: the reference's dilated_edges_imgs (utils), required when opt.edge_aware_in_warp.
+    original_weight, None, None).  `edges_fn`: a replacement for the device edge mask of opt.edge_aware_in_warp, called as the reference's
+    dilated_edges_imgs is (rend_normal, dilate_size=7).
     `samples`: int32 pixel indices replacing the device draw (replays a recorded np.random.choice draw; tests)."""
     r = _drop_in(viewpoint_cam, scene, opt, gaussians, pipe, render, render_pkg, mask_images, iteration, bg, use_metallic_warp,
                  use_roughness_warp, edges_fn, False, samples)
