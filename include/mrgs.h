@@ -533,6 +533,45 @@ int mrgs_prior_terms_backward(const MrgsPriorConfig* cfg, const float* Rt, const
                               const float* rough, const uint8_t* ref_score, const float* fwd_terms, const float* const* g_terms,
                               float* g_surf_normal, float* g_rend_normal, float* g_alpha, float* g_refl, float* g_rough, void* stream);
 
+/* ---- Sobel smoothness terms of one view (fused) ----------------------------------------------------------------------------------
+ * smooth_loss (utils/loss_utils.py:124-125; train_refreal.py:1261 on base_color_map * ref_score_image) and first_order_edge_aware_loss
+ * (:121-122; calculate_loss :185-197 on rend_normal and surf_depth).  One call evaluates 1..MRGS_SMOOTH_MAX_ITEMS items over the same
+ * H x W; all maps contiguous, device pointers.  For a map x [H,W], G_x and G_y are the 3 x 3 Sobel pair divided by 8 with a replicate
+ * border (kornia's spatial_gradient, mode "sobel", normalized); only |G| is used.  An item:
+ *   data [C,H,W] fp32; mask [H W] uint8 or NULL: a zero entry sets the pixel of every channel to 0 BEFORE the stencil, and the gradient
+ *   passes where the entry is nonzero; edge_aware 0 or 1.
+ *   plain (edge_aware = 0, C in 1..4):       term = 1 / (C H W) sum_c sum_dir sum_p |G_dir(data_c)(p)|
+ *   edge-aware (edge_aware = 1, C in {1, 3}): term = 1 / (3 H W) sum_{c<3} sum_dir sum_p |G_dir(data_c')(p)| exp(-|G_dir(img_c)(p)|), with
+ *     img [3,H,W] fp32, given once per call and shared by every edge-aware item; c' = c for C = 3 and 0 for C = 1 (torch's broadcast of the
+ *     one map against the image's three channels: the mean runs over 3 H W either way).
+ * d|G|/dG = sign(G) with sign(0) = 0: a flat region gets an exactly zero gradient.  Nothing reaches img or the masks.
+ * out_terms [n_items] (device).  Sums are reduced in a fixed order (no atomics): both calls are bitwise repeatable.  Forward: two
+ * launches; backward: one.  No host synchronisation in either call.
+ * Backward: g_terms = HOST table of n_items device scalars, the upstream gradients of out_terms (NULL = 0).  Every non-NULL g_data
+ * [C,H,W] is written in full: the adjoint of the clamped stencil, the taps of the padded ring folded into the border texels; zeros for an
+ * item whose upstream gradient is NULL, without reading its inputs.  With no g_data at all nothing is launched.
+ * MRGS_E_BAD_ARG before anything is read: wrong struct_size, H or W <= 0, flags != 0, n_items outside 1..MRGS_SMOOTH_MAX_ITEMS, an item
+ * without data, edge_aware other than 0 / 1, C outside the range of the item's kind, an edge-aware item without img, a missing or
+ * misaligned (16 bytes) or too small workspace, no out_terms; in backward no g_terms, or an upstream gradient for an item without g_data. */
+#define MRGS_SMOOTH_MAX_ITEMS 4
+typedef struct MrgsSmoothConfig {
+    uint32_t struct_size;           /* = sizeof(MrgsSmoothConfig) */
+    int32_t H, W;
+    uint32_t flags;                 /* reserved: 0 */
+} MrgsSmoothConfig;
+typedef struct MrgsSmoothItem {
+    const float* data;
+    const uint8_t* mask;            /* nullable */
+    float* g_data;                  /* backward only; nullable */
+    int32_t C;
+    int32_t edge_aware;
+} MrgsSmoothItem;
+size_t mrgs_smooth_ws_bytes(int32_t H, int32_t W);         /* 0 for sizes the calls refuse */
+int mrgs_smooth_terms_forward(const MrgsSmoothConfig* cfg, const float* img, const MrgsSmoothItem* items, int32_t n_items, void* ws,
+                              size_t ws_bytes, float* out_terms, void* stream);
+int mrgs_smooth_terms_backward(const MrgsSmoothConfig* cfg, const float* img, const MrgsSmoothItem* items, int32_t n_items,
+                               const float* const* g_terms, void* stream);
+
 /* ---- multi-view material consistency loss (calc_warp_loss, train_refnerf.py:414-739, train_refreal.py:405-729) ------------------
  * View v and neighbour n, both H x W.  Geometry: every pixel p of v is back-projected through depth_v, projected into n, looked up in
  * depth_n (bilinear, border, align_corners), back-projected and re-projected into v; e = |p' - p|.  valid = inside n (strict bounds,

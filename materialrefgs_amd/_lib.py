@@ -99,6 +99,17 @@ class MrgsPriorConfig(_Sized):
     _fields_ = [("struct_size", ctypes.c_uint32), ("H", c_int32), ("W", c_int32), ("flags", ctypes.c_uint32)]
 
 
+MRGS_SMOOTH_MAX_ITEMS = 4
+
+
+class MrgsSmoothConfig(_Sized):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("H", c_int32), ("W", c_int32), ("flags", ctypes.c_uint32)]
+
+
+class MrgsSmoothItem(ctypes.Structure):
+    _fields_ = [("data", c_void_p), ("mask", c_void_p), ("g_data", c_void_p), ("C", c_int32), ("edge_aware", c_int32)]
+
+
 MRGS_WARP_GEO, MRGS_WARP_MATERIAL, MRGS_WARP_METALLIC, MRGS_WARP_ROUGHNESS = 1, 2, 4, 8
 
 
@@ -244,6 +255,11 @@ SYMBOLS = {
                                                                                                                           c_void_p]),
     "mrgs_prior_terms_backward": (ctypes.c_int, [ctypes.POINTER(MrgsPriorConfig), ctypes.POINTER(c_float)] + [c_void_p] * 10 +
                                   [ctypes.POINTER(c_void_p)] + [c_void_p] * 6),
+    "mrgs_smooth_ws_bytes": (c_size_t, [c_int32, c_int32]),
+    "mrgs_smooth_terms_forward": (ctypes.c_int, [ctypes.POINTER(MrgsSmoothConfig), c_void_p, ctypes.POINTER(MrgsSmoothItem), c_int32, c_void_p,
+                                                 c_size_t, c_void_p, c_void_p]),
+    "mrgs_smooth_terms_backward": (ctypes.c_int, [ctypes.POINTER(MrgsSmoothConfig), c_void_p, ctypes.POINTER(MrgsSmoothItem), c_int32,
+                                                  ctypes.POINTER(c_void_p), c_void_p]),
     "mrgs_warp_loss_ws_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32]),
     "mrgs_warp_loss_forward": (ctypes.c_int, [ctypes.POINTER(MrgsWarpConfig), ctypes.POINTER(MrgsWarpMaps), c_void_p, c_void_p, c_size_t,
                                               c_void_p, c_void_p, c_void_p, c_void_p]),

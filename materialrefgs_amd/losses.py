@@ -5,9 +5,10 @@ elementwise kernels and their autograd mirror); there is no torch fallback -- CP
 
 Differences a caller sees: the entries of `tb_dict` are 0-d device tensors instead of python floats (the reference calls
 `.item()` five times per iteration, each a host sync; `float(x)` still works), only the first image is differentiated (a second
-image that requires grad raises ValueError while grad mode is on), and the terms the vendored tree cannot run here
-(`first_order_edge_aware_loss` needs kornia, `lpips_loss` needs network weights; both default to off before iteration 18 000,
-arguments/__init__.py:142-143,223-225) raise NotImplementedError when enabled.
+image that requires grad raises ValueError while grad mode is on), `lpips_loss` needs network weights that are not part of this build
+(it raises NotImplementedError when enabled and no network is registered), and the two Sobel smoothness terms
+(`first_order_edge_aware_loss`, `smooth_loss`; kornia is not needed) run in libmrgs.so too for fp32 device tensors
+(materialrefgs_amd.smoothness, csrc/mrgs_smooth.hip) and as kornia's Sobel restated in torch for every other input.
 """
 import ctypes
 
@@ -135,13 +136,26 @@ def spatial_gradient(x):
     return torch.nn.functional.conv2d(xp, k).reshape(B, C, 2, H, W)
 
 
+def _fp32_on_device(*ts):
+    return all(torch.is_tensor(t) and t.is_cuda and t.dtype is torch.float32 for t in ts)
+
+
 def first_order_edge_aware_loss(data, img):
-    """utils/loss_utils.py:121-122: |grad data| damped by exp(-|grad img|), summed over the two directions, mean."""
+    """utils/loss_utils.py:121-122: |grad data| damped by exp(-|grad img|), summed over the two directions, mean.  fp32 device tensors go
+    to the native node (materialrefgs_amd.smoothness, csrc/mrgs_smooth.hip: only `data` is differentiated); every other input is the
+    torch statement below."""
+    if _fp32_on_device(data, img):
+        from . import smoothness
+        return smoothness.first_order_edge_aware_loss(data, img)
     return (spatial_gradient(data[None])[0].abs() * torch.exp(-spatial_gradient(img[None])[0].abs())).sum(1).mean()
 
 
 def smooth_loss(data):
-    """utils/loss_utils.py:124-125."""
+    """utils/loss_utils.py:124-125; fp32 device tensors go to the native node, as above (smoothness.albedo_smooth_loss is the masked form
+    train_refreal.py:1261 uses)."""
+    if _fp32_on_device(data):
+        from . import smoothness
+        return smoothness.smooth_loss(data)
     return spatial_gradient(data[None])[0].abs().sum(1).mean()
 
 
@@ -217,12 +231,20 @@ def calculate_loss(viewpoint_camera, pc, render_pkg, opt, iteration, image_weigh
         "loss_normal_smooth": zero, "loss_depth_smooth": zero,
         "loss": terms[0],
     }
-    # the two edge-aware smoothness terms (:185-197; lambda = 0 in the reference's defaults): torch ops on top of the fused loss
+    # the two edge-aware smoothness terms (:185-197; lambda = 0 in the reference's defaults).  Both active: one native call with both maps,
+    # so that the Sobel weights of gt_image are formed once (smoothness.view_smooth_terms); one alone goes through its name
+    if use_nsmooth and use_dsmooth and _fp32_on_device(render_pkg["rend_normal"], render_pkg["surf_depth"], gt_image):
+        from . import smoothness
+        tb_dict["loss_normal_smooth"], tb_dict["loss_depth_smooth"] = smoothness.view_smooth_terms(
+            gt_image, (smoothness.SmoothItem(render_pkg["rend_normal"], None, True), smoothness.SmoothItem(render_pkg["surf_depth"], None, True)))
+    else:
+        if use_nsmooth:
+            tb_dict["loss_normal_smooth"] = first_order_edge_aware_loss(render_pkg["rend_normal"], gt_image)
+        if use_dsmooth:
+            tb_dict["loss_depth_smooth"] = first_order_edge_aware_loss(render_pkg["surf_depth"], gt_image)
     if use_nsmooth:
-        tb_dict["loss_normal_smooth"] = first_order_edge_aware_loss(render_pkg["rend_normal"], gt_image)
         loss = loss + opt.lambda_normal_smooth * tb_dict["loss_normal_smooth"]
     if use_dsmooth:
-        tb_dict["loss_depth_smooth"] = first_order_edge_aware_loss(render_pkg["surf_depth"], gt_image)
         loss = loss + opt.lambda_depth_smooth * tb_dict["loss_depth_smooth"]
     if use_perc and iteration > opt.perceptual_loss_start_iter:                         # :212-215
         perc_loss = lpips_loss(image.unsqueeze(0), gt_image.unsqueeze(0))
