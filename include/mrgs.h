@@ -294,6 +294,41 @@ int mrgs_surfel_shade_composite_backward(const MrgsEnvMips* mips, const MrgsShad
                                          const float* g_specular_extra, const float* g_direct_light, const float* g_specular_weight,
                                          float* g_base, float* g_normal, float* g_features, float* g_alpha, void* stream);
 
+/* ---- one-bounce light from the material mesh: RayTracer.secondary_indirect_color (raytracing_brdf/raytracer.py:218-271) -------------
+ * One launch, one ray per lane, over the outputs of mrgs_bvh_trace.  Per ray i:
+ *   active != NULL and active[i] == 0                          -> out = 0
+ *   depth[i] >= 10 (a miss)                                    -> out = sigmoid(level-0 fetch of `base` along -rays_v[i])   (mode="pure_env")
+ *   otherwise, with (a, b, c) = the vertices of triangle face_ids[i] and p = hit_pos[i]:
+ *     weights  area(p,b,c), area(p,c,a), area(p,a,b) over area(a,b,c), areas of the xy-PROJECTION, absolute values (barycentric_interpolation,
+ *              :209-216; evaluated from differences to a); they need not sum to one
+ *     diffuse, albedo, metallic m, roughness r, normal n = the weighted rows of `table` (n is NOT normalised)
+ *     NdotV = n . v,  l = safe_normalize(2 n NdotV - v),  fg = FG table at clamp((NdotV, r), 0, 1)       -- every ray its OWN pair
+ *     light = sigmoid(trilinear fetch of `mips` at get_mip(r) along l)
+ *     out   = (1 - m) diffuse + ((0.04 (1 - m) + albedo m) fg0 + fg1) light
+ *   a hit whose projected triangle area is exactly 0, or whose face id / vertex ids lie outside the mesh -> out = 0, no gradient.
+ * table [n_vertices,12] fp32, 16-byte aligned: diffuse 3, albedo 3, metallic, roughness, normal 3 (decoded: the kernel applies nothing), pad.
+ * base [6,base_res,base_res,3]: the un-filtered level EnvLight.base; mips: the prefiltered chain EnvLight.specular.
+ * MRGS_E_BAD_ARG before any launch: a wrong struct_size, flags != 0, a negative count, a resolution < 1, and with n_rays > 0 a NULL pointer
+ * (only `active` is optional), a mis-aligned table, or n_vertices / n_triangles == 0.  n_rays == 0 -> MRGS_OK, nothing is launched. */
+typedef struct MrgsBounceConfig {
+    uint32_t struct_size;    /* = sizeof(MrgsBounceConfig); checked like MrgsRasterConfig::struct_size */
+    uint32_t flags;          /* 0 */
+    int64_t n_rays, n_vertices, n_triangles;
+    int32_t base_res, lut_res;
+} MrgsBounceConfig;
+int mrgs_bounce_shade_forward(const MrgsBounceConfig* cfg, const MrgsEnvMips* mips, const float* base, const float* hit_pos /*[N,3]*/,
+                              const float* rays_v /*[N,3]*/, const int32_t* face_ids /*[N]*/, const float* depth /*[N]*/,
+                              const uint8_t* active /*[N] or NULL*/, const float* vertices /*[V,3]*/, const int32_t* triangles /*[T,3]*/,
+                              const float* table, const float* lut /*[lut_res,lut_res,2]*/, float* out /*[N,3]*/, void* stream);
+/* The backward, one launch; it recomputes the gather from the same inputs.  g_out [N,3].  ACCUMULATED by float atomics into buffers the
+ * caller zero-fills (each may be NULL = not wanted): g_base (one copy of `base`, miss rays), mips->grad (every level of the chain, hit rays),
+ * g_table [n_vertices,8] = diffuse 3, albedo 3, metallic, roughness on the three vertices of the hit triangle (roughness through both the
+ * FG table's v coordinate and the mip level).  Nothing flows to positions, directions or the normal attribute. */
+int mrgs_bounce_shade_backward(const MrgsBounceConfig* cfg, const MrgsEnvMips* mips, const float* base, float* g_base, const float* hit_pos,
+                               const float* rays_v, const int32_t* face_ids, const float* depth, const uint8_t* active, const float* vertices,
+                               const int32_t* triangles, const float* table, const float* lut, const float* g_out, float* g_table,
+                               void* stream);
+
 /* ---- environment prefilter: EnvLight.build_mips (scene/light.py:72-86) ------------------------------------------------
  * renderutils' specular_cubemap / diffuse_cubemap (scene/renderutils/c_src/cubemap.cu:110-354, ops.py:390-459) are fixed linear
  * operators for a given (resolution, roughness, cos_cutoff): out[t] = sum_s w(t,s) cube[s] / sum_s w(t,s).  They are built

@@ -64,6 +64,11 @@ class MrgsShadeFrame(ctypes.Structure):
                 ("roughness", MrgsStridedMap), ("lut", c_void_p), ("lut_res", c_int32)]
 
 
+class MrgsBounceConfig(_Sized):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("n_rays", c_int64), ("n_vertices", c_int64),
+                ("n_triangles", c_int64), ("base_res", c_int32), ("lut_res", c_int32)]
+
+
 class MrgsRasterTicket(ctypes.Structure):
     _fields_ = [("device", c_int32), ("slot", c_int32), ("seq", ctypes.c_uint64), ("capacity_pairs", c_int64)]
 
@@ -353,6 +358,8 @@ SYMBOLS = {
     "mrgs_shade_specular_backward": (ctypes.c_int, [ctypes.POINTER(MrgsEnvMips), ctypes.POINTER(MrgsShadeFrame), c_void_p, c_void_p,
                                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "mrgs_surfel_shade_composite_backward": (ctypes.c_int, [ctypes.POINTER(MrgsEnvMips), ctypes.POINTER(MrgsShadeFrame), c_int32] + [c_void_p] * 13),
+    "mrgs_bounce_shade_forward": (ctypes.c_int, [ctypes.POINTER(MrgsBounceConfig), ctypes.POINTER(MrgsEnvMips)] + [c_void_p] * 12),
+    "mrgs_bounce_shade_backward": (ctypes.c_int, [ctypes.POINTER(MrgsBounceConfig), ctypes.POINTER(MrgsEnvMips)] + [c_void_p] * 14),
     "mrgs_debug_export": (ctypes.c_int, [ctypes.POINTER(MrgsRasterConfig), c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p,
                                          c_void_p]),
     "mrgs_debug_sort_ws_bytes": (c_size_t, [c_int64]),
