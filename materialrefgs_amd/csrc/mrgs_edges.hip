@@ -254,7 +254,5 @@ extern "C" int mrgs_edge_mask(const float* img, int32_t H, int32_t W, int32_t di
     edge_link_kernel<<<tile_grid, 4 * EDGE_TILE, 0, st>>>(a, cls, w.parent);
     edge_flag_kernel<<<pixel_grid, 256, 0, st>>>(n, cls, w.parent, w.flag);
     edge_dilate_kernel<<<tile_grid, 256, 0, st>>>(a, cls, w.parent, w.flag, out);
-    // the launch status, spelled out: tests/test_status.py keeps a fixed list of the files that use the macro; this file's failure path is
-    // in tests/test_edges.py
-    return mrgs_hip_status(hipGetLastError(), __FILE__, __LINE__);
+    return MRGS_LAUNCH_STATUS();
 }

@@ -198,13 +198,7 @@ __global__ __launch_bounds__(256) void prior_terms_fwd(PriorMaps a, float* __res
         ld.one(quads * PX + tid, p);
         accumulate(a, p, acc);
     }
-#pragma unroll
-    for (int k = 0; k < NSUM; ++k) acc[k] = wave_shfl_sum(acc[k]);
-    if ((tid & 63) == 0)
-#pragma unroll
-        for (int k = 0; k < NSUM; ++k) red[tid >> 6][k] = acc[k];
-    __syncthreads();
-    if (tid < ROW) partials[(size_t)blockIdx.x * ROW + tid] = tid < NSUM ? (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]) : 0.f;
+    block_row_sum_256(acc, red, partials + (size_t)blockIdx.x * ROW);
 }
 
 // out[0..3] l1 / cos of surf, l1 / cos of rend, [4] entropy, [5..8] a1 a2 b1 b2, [9] sum m, [10] |S|, [11] |not S|, [12] a1 + a2 + b1 +

@@ -182,21 +182,8 @@ __global__ __launch_bounds__(256) void smooth_terms_finalize(SmoothArgs a, const
 {
     __shared__ double red[4][MRGS_SMOOTH_MAX_ITEMS];
     const int tid = threadIdx.x;
-    double acc[MRGS_SMOOTH_MAX_ITEMS] = {0.0, 0.0, 0.0, 0.0};
-    for (int b = tid; b < nblocks; b += 256) {                     // one row per thread and pass; the order of the additions is fixed
-        const float4 r = reinterpret_cast<const float4*>(partials)[b];
-        acc[0] += r.x; acc[1] += r.y; acc[2] += r.z; acc[3] += r.w;
-    }
-#pragma unroll
-    for (int i = 0; i < MRGS_SMOOTH_MAX_ITEMS; ++i) {
-        const double v = wave_shfl_sum(acc[i]);
-        if ((tid & 63) == 0) red[tid >> 6][i] = v;
-    }
-    __syncthreads();
-    if (tid < a.n_items) {
-        const double s = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
-        out[tid] = (float)(0.125 * s / smooth_count(a.items[tid].C, a.items[tid].edge, a.H, a.W));
-    }
+    block_rows_sum_256<MRGS_SMOOTH_MAX_ITEMS, MRGS_SMOOTH_MAX_ITEMS>(partials, nblocks, red);
+    if (tid < a.n_items) out[tid] = (float)(0.125 * rows_total(red, tid) / smooth_count(a.items[tid].C, a.items[tid].edge, a.H, a.W));
 }
 
 // ---- backward -----------------------------------------------------------------------------------------------------------------------------
@@ -339,9 +326,7 @@ extern "C" int mrgs_smooth_terms_forward(const MrgsSmoothConfig* cfg, const floa
     hipStream_t st = (hipStream_t)stream;
     smooth_terms_fwd<<<nblocks, 256, 0, st>>>(a, (float*)ws);
     smooth_terms_finalize<<<1, 256, 0, st>>>(a, (const float*)ws, nblocks, out_terms);
-    // the launch status, spelled out as mrgs_edges.hip does: tests/test_status.py keeps a fixed list of the files that use the macro; this
-    // file's failure path is in tests/test_smooth_terms.py
-    return mrgs_hip_status(hipGetLastError(), __FILE__, __LINE__);
+    return MRGS_LAUNCH_STATUS();
 }
 
 extern "C" int mrgs_smooth_terms_backward(const MrgsSmoothConfig* cfg, const float* img, const MrgsSmoothItem* items, int32_t n_items,
@@ -359,5 +344,5 @@ extern "C" int mrgs_smooth_terms_backward(const MrgsSmoothConfig* cfg, const flo
     }
     if (!any) return MRGS_OK;                                     // nothing to write
     smooth_terms_bwd<<<smooth_blocks(a.tiles), 256, 0, (hipStream_t)stream>>>(a);
-    return mrgs_hip_status(hipGetLastError(), __FILE__, __LINE__);
+    return MRGS_LAUNCH_STATUS();
 }

@@ -1,7 +1,7 @@
 // mrgs_wave.h -- wave64 and workgroup primitives shared by the kernel files: each exists here once.
 //
 // Wave reductions, the workgroup scans (of one value per thread, and of a whole array of per-workgroup counts by one workgroup), the packed
-// triple of counts that travels through those scans, and the last-block fold of six maxima.
+// triple of counts that travels through those scans, the partial-row sums of the per-view term kernels, and the last-block fold of six maxima.
 //
 // Two families of wave-wide reductions, told apart by name:
 //   wave_shfl_*   __shfl_xor butterfly: six ds_bpermute round trips through the LDS crossbar, the result in EVERY lane (a vector register)
@@ -177,6 +177,58 @@ __device__ __forceinline__ unsigned long long pack_fields(unsigned long long c0,
     return c0 | (c1 << FIELD) | (c2 << (2 * FIELD));
 }
 __device__ __forceinline__ unsigned unpack_field(unsigned long long packed, int k) { return (unsigned)((packed >> (FIELD * k)) & FIELD_MASK); }
+
+// ---- K float sums over a whole grid: one partial row per workgroup, the rows summed in double by one workgroup ---------------------------
+// The tail of the per-view term kernels (mrgs_loss, mrgs_prior, mrgs_smooth) and the head of their finalize kernels.  256 threads, no
+// atomics, every addition in a fixed order: the terms are run-to-run identical.  `red` is the caller's LDS.
+// Users: prior_terms_fwd (workgroup side), smooth_terms_finalize (finalize side).  Four kernels compute exactly this and keep it written out,
+// because the compiler turns the call into another instruction stream than the one that was measured (tools/isa_digest.py; same registers):
+//   loss_fwd_kernel        one more s_xor of exec around the lane-0 stores, with the row pointer formed before or inside the last branch
+//   smooth_terms_fwd       30 instructions fewer, scheduled otherwise; its own form stores each sum right behind its butterfly, and with
+//                          that form here prior_terms_fwd comes out 108 instructions longer
+//   prior_terms_finalize   same length, the `if (a.surf)` branch behind the barrier laid out the other way round
+//   loss_finalize_kernel   also reads four rows a pass and picks columns by channel; even wave_shfl_sum<double> for its butterfly
+//                          reschedules it (4 instructions fewer)
+// Workgroup side: v[0..K) summed over the wave, then over the four waves as (w0 + w1) + (w2 + w3) into row[0..ROW), entries past K as 0.
+template <int K, int ROW>
+__device__ __forceinline__ void block_row_sum_256(float (&v)[K], float (&red)[4][ROW], float* row)
+{
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int k = 0; k < K; ++k) v[k] = wave_shfl_sum(v[k]);
+    if ((tid & 63) == 0)
+#pragma unroll
+        for (int k = 0; k < K; ++k) red[tid >> 6][k] = v[k];
+    __syncthreads();
+    if (tid < ROW) row[tid] = tid < K ? (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]) : 0.f;
+}
+// Finalize side: the nblocks rows of `partials` ([nblocks][ROW], 16-byte aligned), row b by thread b % 256 in ascending b, then over the
+// wave; behind its barrier red[w][k] is wave w's sum of column k and rows_total(red, k) the total.
+template <int K, int ROW>
+__device__ __forceinline__ void block_rows_sum_256(const float* partials, int nblocks, double (&red)[4][K])
+{
+    static_assert(ROW % 4 == 0 && K <= ROW, "a row is whole 16-byte words");
+    const int tid = threadIdx.x;
+    double acc[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) acc[k] = 0.0;
+    for (int b = tid; b < nblocks; b += 256) {                 // one row per thread and pass
+        const float4* p = reinterpret_cast<const float4*>(partials + (size_t)b * ROW);
+        float4 r[ROW / 4];
+#pragma unroll
+        for (int w = 0; w < ROW / 4; ++w) r[w] = p[w];
+#pragma unroll
+        for (int k = 0; k < K; ++k) acc[k] += reinterpret_cast<const float*>(r)[k];
+    }
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        const double v = wave_shfl_sum(acc[k]);
+        if ((tid & 63) == 0) red[tid >> 6][k] = v;
+    }
+    __syncthreads();
+}
+template <int K>
+__device__ __forceinline__ double rows_total(const double (&red)[4][K], int k) { return (red[0][k] + red[1][k]) + (red[2][k] + red[3][k]); }
 
 // ---- six maxima over a whole grid without same-address atomics -----------------------------------------------------------------------
 // Tail of a 256-thread kernel whose threads each hold six ordered-uint maxima (ext): every block leaves one partial row, takes a ticket,

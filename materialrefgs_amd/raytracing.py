@@ -7,7 +7,7 @@ on the GPU (`mrgs_bvh_trace`); depth = 10 marks a miss (utils/refl_utils.py:390-
 happens inside the kernel).
 
 A tracer built from a material mesh (`ply_path=...`, a file of io.save_material_ply, or `RayTracer.from_mesh`) also carries the
-per-vertex material `vertex_attrs` and shades one mirror bounce with it: `mrgs_bounce_shade_forward / _backward` (csrc/mrgs_shade.hip;
+per-vertex material `vertex_attrs` and shades one mirror bounce with it: `mrgs_bounce_shade_forward / _backward` (csrc/mrgs_bounce.hip;
 the contract and the three places where this differs from the reference's text on purpose are in include/mrgs.h and INTEGRATION.md)."""
 import ctypes
 

@@ -9,7 +9,8 @@ PARITY UNPINNED for the texture lookups: the reference performs them with nvdiff
 sampling rules are therefore restated from nvdiffrast's documented behaviour (texel centres at (i+0.5)/res, bilinear,
 `clamp` boundary for the 2D LUT, seamless cube edges, trilinear between integer mip levels at LOD = mip_level_bias); the
 cube face/orientation convention IS pinned in-tree by cube_to_dir (scene/light_utils.py:24-31) and checked by the
-known-answer test "a lookup at cube_to_dir(texel centre) returns that texel" (tests/test_shading.py).
+known-answer test "a lookup at cube_to_dir(texel centre) returns that texel" (tests/test_shading.py).  The kernels' statement of the
+same rules is csrc/mrgs_envmap.h, which the lookups and the shading (mrgs_shade.hip) and the one-bounce light (mrgs_bounce.hip) share.
 Everything else (ray set-up, mirror direction, Fresnel-style weight, compositing) is elementwise arithmetic restated literally.
 """
 import numpy as np

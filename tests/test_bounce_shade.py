@@ -1,4 +1,4 @@
-"""RayTracer.shade / secondary_indirect_color (mrgs_bounce_shade_forward / _backward, csrc/mrgs_shade.hip) against the float64 statement
+"""RayTracer.shade / secondary_indirect_color (mrgs_bounce_shade_forward / _backward, csrc/mrgs_bounce.hip) against the float64 statement
 of tests/bounce_statement.py, and that statement against the reference's own recorded output (tests/golden/reference_bounce.npz,
 written by tests/golden/gen_reference_bounce_vectors.py).
 

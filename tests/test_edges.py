@@ -132,19 +132,6 @@ def test_abi_argument_checks_without_gpu():
     assert call(n=need - 1) == _lib.MRGS_E_WORKSPACE
 
 
-@pytest.mark.skipif(torch.cuda.device_count() != 0, reason="host addresses as arguments: only for a machine without a device")
-def test_hip_failure_names_the_file():
-    """Without a device the launches fail and nothing runs: the call reports it through the library's one status path, as the files of
-    tests/test_status.py do (whose rules about the pointers apply here too)."""
-    from materialrefgs_amd import _lib
-    L = _lib.lib()
-    buf = (ctypes.c_float * 4096)()
-    p = (ctypes.addressof(buf) + 255) & ~255
-    assert L.mrgs_edge_mask(p, 4, 4, 7, 0.0, 80.0, 1, p, None, p, L.mrgs_edges_ws_bytes(4, 4), None) == _lib.MRGS_E_HIP
-    text = L.mrgs_last_hip_error()
-    assert text and b" at mrgs_edges.hip:" in text, text
-
-
 def test_python_wrapper_refuses_what_it_cannot_serve():
     from materialrefgs_amd import edges
     with pytest.raises(RuntimeError, match="device tensor"):

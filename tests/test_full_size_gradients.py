@@ -8,7 +8,7 @@ A. The surfel tracer's backward (csrc/mrgs_surfel_trace.hip: replay of the forwa
    the path the forward took, and the production record path (HardwareRendering.render_gaussians -> mrgs_surfel_trace_prep_raw_*) against
    GaussianModel's activations + eval_sh + the dense statement.  The walk again (MRGS_TRACE_NO_RECORD, read once per process) runs the
    first two in a child process.
-B. The fused shading backward shade_fused_bwd_kernel<false / true> (csrc/mrgs_shade.hip: dense LDS levels, the 4 096-entry hash table, its
+B. The fused shading backward shade_fused_bwd_kernel<false / true> (csrc/mrgs_shade.hip on the fetch of csrc/mrgs_envmap.h: dense LDS levels, the 4 096-entry hash table, its
    mid-loop flush and 8-probe global fallback) at 800^2 and 1600^2 on the 128 -> 16 chain with every level a leaf, against
    oracle/shading_oracle.specular_color_surfel in float64 on the GPU; a host model of the tile schedule proves that the hash paths run.
 """

@@ -142,24 +142,6 @@ def test_smooth_abi_argument_checks_without_gpu():
     assert bwd(its=(Item(p, p, None, 3, 0), Item(p, None, None, 1, 1)), table=none) == 0     # nothing to write: nothing launched
 
 
-@pytest.mark.skipif(torch.cuda.device_count() != 0, reason="host addresses as arguments: only for a machine without a device")
-def test_hip_failure_names_the_file():
-    """Without a device the launches fail and nothing runs: both calls report it through the library's one status path, as the files of
-    tests/test_status.py do (whose rules about the pointers apply here too)."""
-    from materialrefgs_amd import _lib
-    L = _lib.lib()
-    buf = (ctypes.c_float * 4096)()
-    p = (ctypes.addressof(buf) + 255) & ~255
-    cfg = _cfg(4, 4)
-    its = (_lib.MrgsSmoothItem * 1)(_lib.MrgsSmoothItem(p, None, p, 3, 1))
-    table = (ctypes.c_void_p * 1)(p)
-    for rc in (L.mrgs_smooth_terms_forward(ctypes.byref(cfg), p, its, 1, p, L.mrgs_smooth_ws_bytes(4, 4), p, None),
-               L.mrgs_smooth_terms_backward(ctypes.byref(cfg), p, its, 1, table, None)):
-        assert rc == _lib.MRGS_E_HIP
-        text = L.mrgs_last_hip_error()
-        assert text and b" at mrgs_smooth.hip:" in text, text
-
-
 def test_wrappers_raise_without_gpu():
     """A CPU tensor, another dtype, a shape the kernels do not serve or an image that requires grad raises before anything native is
     touched."""

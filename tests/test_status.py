@@ -43,10 +43,42 @@ def _prior_terms(L):
     return L.mrgs_prior_terms_forward(ctypes.byref(cfg), None, None, None, None, None, P, P, None, None, None, P, L.mrgs_prior_ws_bytes(8, 8), P, None)
 
 
+def _mips():
+    """A chain of one 4 x 4 level."""
+    from materialrefgs_amd._lib import MrgsEnvMips
+    m = MrgsEnvMips()
+    m.n_levels, m.res[0], m.tex[0], m.min_roughness, m.max_roughness = 1, 4, P, 0.08, 0.5
+    return m
+
+
+def _bounce(L):
+    from materialrefgs_amd._lib import MrgsBounceConfig
+    cfg = MrgsBounceConfig(0, 4, 10, 12, 4, 8)
+    return L.mrgs_bounce_shade_forward(ctypes.byref(cfg), ctypes.byref(_mips()), P, P, P, P, P, None, P, P, P, P, P, None)
+
+
+def _smooth(L):
+    """Both directions: the forward is checked here, the backward's status is returned; its text names another line of the same file."""
+    from materialrefgs_amd import _lib
+    cfg = _lib.MrgsSmoothConfig(4, 4, 0)
+    its = (_lib.MrgsSmoothItem * 1)(_lib.MrgsSmoothItem(P, None, P, 3, 1))
+    table = (ctypes.c_void_p * 1)(P)
+    assert L.mrgs_smooth_terms_forward(ctypes.byref(cfg), P, its, 1, P, L.mrgs_smooth_ws_bytes(4, 4), P, None) == _lib.MRGS_E_HIP
+    forward = L.mrgs_last_hip_error()
+    assert forward and b" at mrgs_smooth.hip:" in forward, forward
+    rc = L.mrgs_smooth_terms_backward(ctypes.byref(cfg), P, its, 1, table, None)
+    assert L.mrgs_last_hip_error() != forward
+    return rc
+
+
 # one well-formed call per translation unit that has launch entry points: file -> call(L) -> status
 CALLS = {
     "mrgs_api": lambda L: L.mrgs_mark_visible(4, P, P, P, P, None),
-    "mrgs_shade": lambda L: L.mrgs_cubemap_mip_forward(2, P, P, None),
+    "mrgs_shade": lambda L: L.mrgs_envmap_lookup_forward(ctypes.byref(_mips()), 4, P, None, P, None),
+    "mrgs_prefilter": lambda L: L.mrgs_cubemap_mip_forward(2, P, P, None),
+    "mrgs_bounce": _bounce,
+    "mrgs_smooth": _smooth,
+    "mrgs_edges": lambda L: L.mrgs_edge_mask(P, 4, 4, 7, 0.0, 80.0, 1, P, None, P, L.mrgs_edges_ws_bytes(4, 4), None),
     "mrgs_maps": lambda L: L.mrgs_surfel_composite_forward(2, 2, 0, *([P] * 7), None),
     "mrgs_surfel": _surfel_features,
     "mrgs_loss": _loss,

@@ -1,6 +1,7 @@
 // atomic_scope.hip -- rate of scattered fp32 atomic adds on MI355X: device (agent) scope against XCD-private copies updated with
 // workgroup-scope atomics (no sc1: the read-modify-write is done by the issuing XCD's L2, which every CU of that XCD shares), and whether
-// the latter loses updates.  Behind the texel-gradient scatter of csrc/mrgs_shade.hip.
+// the latter loses updates.  Behind the texel-gradient scatter (texel_scatter of csrc/mrgs_envmap.h, the workgroup
+// accumulators of csrc/mrgs_shade.hip).
 //
 //   hipcc --offload-arch=gfx950 -O3 -o atomic_scope atomic_scope.hip && ./atomic_scope
 //
