@@ -74,7 +74,7 @@ KnnWs knn_ws(int64_t P)
 }
 
 // bounds[k] = max ord(x_k), bounds[3 + k] = max ~ord(x_k) over the finite coordinates (a non-finite one is left out: it is clamped into
-// the grid later).  One partial row per block, folded by the last block to finish (grid_max6_last_block_folds, as st_aabb_kernel of mrgs_surfel_trace.hip).
+// the grid later).  One partial row per block, folded by the last block to finish (grid_max6_last_block_folds, as st_aabb_kernel of mrgs_surfel_hier.hip).
 __global__ __launch_bounds__(256) void knn_bounds_kernel(int P, const float* __restrict__ pts, uint32_t* __restrict__ partial,
                                                          uint32_t* __restrict__ ticket, uint32_t* __restrict__ bounds)
 {

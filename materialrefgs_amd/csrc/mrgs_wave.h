@@ -14,6 +14,16 @@
 __device__ __forceinline__ uint32_t ld_agent(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void st_agent(uint32_t* p, uint32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
+// ---- one wave's lanes exchange data through LDS --------------------------------------------------------------------------------------
+// What the lanes of this wave wrote to LDS before the call, every lane of it reads behind it (no s_barrier: the other waves of the
+// workgroup are not waited for).  So far only the surfel tracer calls it; the other files still spell the three lines out.
+__device__ __forceinline__ void wave_lds_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
 // ---- ordered float keys, Morton codes --------------------------------------------------------------------------------------------
 __device__ __forceinline__ uint32_t ord_f(float f)          // order-preserving float -> uint
 {

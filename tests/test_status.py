@@ -17,6 +17,7 @@ pytestmark = pytest.mark.skipif(torch.cuda.device_count() != 0, reason="host add
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 _BUF = (ctypes.c_float * 65536)()
 P = (ctypes.addressof(_BUF) + 63) & ~63        # every pointer argument (the k-NN workspace has to be 16-byte aligned)
+_BG = (ctypes.c_float * 3)(0.0, 0.0, 0.0)       # the tracer's background colour is read on the host
 
 
 def _surfel_features(L):
@@ -84,7 +85,9 @@ CALLS = {
     "mrgs_loss": _loss,
     "mrgs_multiview": _ncc_backward,
     "mrgs_trace_prep": lambda L: L.mrgs_traced_blend_forward(1, 1, P, P, 1, 3, P, 1, P, None),
-    "mrgs_surfel_trace": lambda L: L.mrgs_surfel_bvh_build(P, 4, P, L.mrgs_surfel_bvh_bytes(4), P, L.mrgs_surfel_bvh_ws_bytes(4), None),
+    "mrgs_surfel_hier": lambda L: L.mrgs_surfel_bvh_build(P, 4, P, L.mrgs_surfel_bvh_bytes(4), P, L.mrgs_surfel_bvh_ws_bytes(4), None),
+    # an empty model: the forward clears the maps of its 4 rays, the first HIP call of that file
+    "mrgs_surfel_trace": lambda L: L.mrgs_surfel_trace_forward(None, 0, 4, 0, P, P, None, None, _BG, P, P, P, P, P, P, None, None, 0, None),
     "mrgs_bvh": lambda L: L.mrgs_bvh_trace(P, 4, 4, P, P, P, P, P, P, None),
     "mrgs_knn": lambda L: L.mrgs_knn_mean_dist2(P, 64, P, P, L.mrgs_knn_ws_bytes(64), None),
     "mrgs_densify": lambda L: L.mrgs_densify_stats(4, *([P] * 6), None),
