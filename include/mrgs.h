@@ -1239,6 +1239,58 @@ const char* mrgs_version(void);
 #define MRGS_ABI_VERSION 10
 int32_t mrgs_abi_version(void);
 
+/* GaussianModel's reset family and its normal-propagation step (scene/gaussian_model.py:532-722) in ONE launch: for up to
+ * MRGS_RESET_MAX_ITEMS parameter groups the new raw values and, where the optimizer has stepped, both Adam moments written 0 for EVERY
+ * row (replace_tensor_to_optimizer, :840-854).  All tensors are device fp32, row-major [P,width]; a dst never aliases any src, so the
+ * items of one call all read the values from before the call (a fused step equals the sequence of its single methods as long as no item
+ * writes what another item's rule or keep mask reads -- true of the three steps the training loops run).
+ * Keep mask: `keep` is an OR of MRGS_RESET_KEEP_*; a row for which ANY selected condition holds copies its src bits to dst unchanged.
+ *   EXCLUSIVE    exclusive[row] != 0
+ *   REFL_ABOVE   sigmoid(refl_raw[row]) > refl_thr        REFL_BELOW   sigmoid(refl_raw[row]) < refl_thr
+ *   ROUGH_ABOVE  sigmoid(rough_raw[row]) > rough_thr
+ * The decisions compare the fp32 sigmoid 1 / (1 + expf(-x)) with the fp32 threshold, as the reference does -- not the raw value with
+ * logit(thr).  Rules (v a src element, s = that sigmoid of v, L(x) = log(x / (1 - x)) taken in double on the host from the caller's
+ * double and rounded once to fp32; af, bf = a, b rounded to fp32; every fp32 operation un-fused, in the order written):
+ *   CAP           s > af ? L(a) : v                         reset_opacity0 (a = 0.01)
+ *   FLOOR         s < af ? L(a) : v                         reset_refl, reset_refl_strength2
+ *   LIFT          s > af ? v : L(a)                         reset_opacity1 (a = 0.9)
+ *   CONST         L(a)                                      reset_refl_strength, reset_roughness
+ *   FILL          af                                        reset_features
+ *   JITTER        v + ((u af) 2 - af)                       dist_color, dist_albedo (a = 0.4)
+ *   JITTER_CONST  logf(c / (1 - c)), c = clamp(af + (u - 0.5) bf, 0, 1)      reset_ori_color (0.5, 0.05)
+ *   ENLARGE       log(exp(v) af) taken in double from the fp32 v, rounded once      enlarge_refl_scales(ret_raw=True) / reset_scale
+ * On the unchanged side of CAP / FLOOR / LIFT the row keeps v bit for bit (the reference writes logit(sigmoid(v)) there: v up to a round
+ * trip that loses e^|v| 2^-24 and becomes +-inf from |v| ~ 16.6 on).
+ * u: item.noise[row, column] when given, else Philox4x32-10 with key `seed` and counter (row low word, row high word, column, item
+ * index), u = (x0 >> 8) 2^-24 in [0, 1).
+ * Codes, all before any HIP call: MRGS_E_BAD_ARG for a wrong struct_size, n_items outside 1..MRGS_RESET_MAX_ITEMS, P < 0, width < 1, an
+ * unknown rule or unknown keep bits, one moment pointer without the other, a KEEP_* bit whose source pointer is NULL, a NULL src or dst
+ * with P > 0, a outside (0, 1) where L(a) is taken; MRGS_E_UNSUPPORTED for width > 2^20 or more than 2^31 - 1 blocks of 256 rows.
+ * P == 0 returns MRGS_OK and launches nothing.  One launch, nothing allocated or read back, no synchronisation. */
+#define MRGS_RESET_MAX_ITEMS 8
+enum { MRGS_RESET_CAP = 0, MRGS_RESET_FLOOR = 1, MRGS_RESET_LIFT = 2, MRGS_RESET_CONST = 3, MRGS_RESET_FILL = 4, MRGS_RESET_JITTER = 5,
+       MRGS_RESET_JITTER_CONST = 6, MRGS_RESET_ENLARGE = 7 };
+enum { MRGS_RESET_KEEP_EXCLUSIVE = 1, MRGS_RESET_KEEP_REFL_ABOVE = 2, MRGS_RESET_KEEP_REFL_BELOW = 4, MRGS_RESET_KEEP_ROUGH_ABOVE = 8 };
+typedef struct MrgsResetItem {
+    const float* src;          /* [P,width] raw values, read only */
+    float* dst;                /* [P,width] new raw values (never aliases any src) */
+    float* exp_avg_dst;        /* [P,width] written 0 for EVERY row, or NULL (optimizer has not stepped) */
+    float* exp_avg_sq_dst;     /* both NULL or both set */
+    const float* noise;        /* [P,width] uniforms in [0,1) for the JITTER rules, or NULL: Philox */
+    int32_t width, rule, keep, reserved;
+    double a, b;
+} MrgsResetItem;
+typedef struct MrgsResetConfig {
+    uint32_t struct_size;      /* = sizeof(MrgsResetConfig) */
+    int64_t P;
+    const float* refl_raw;     /* [P] raw _refl_strength, needed by KEEP_REFL_* */
+    const float* rough_raw;    /* [P] raw _roughness,     needed by KEEP_ROUGH_ABOVE */
+    const uint8_t* exclusive;  /* [P] or NULL */
+    float refl_thr, rough_thr;
+    uint64_t seed;
+} MrgsResetConfig;
+int mrgs_model_reset(const MrgsResetConfig* cfg, const MrgsResetItem* items, int32_t n_items, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

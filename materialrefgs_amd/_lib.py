@@ -199,6 +199,22 @@ class MrgsMeshConfig(_Sized):
                 ("radius", c_float)]
 
 
+MRGS_RESET_MAX_ITEMS = 8
+(MRGS_RESET_CAP, MRGS_RESET_FLOOR, MRGS_RESET_LIFT, MRGS_RESET_CONST, MRGS_RESET_FILL, MRGS_RESET_JITTER, MRGS_RESET_JITTER_CONST,
+ MRGS_RESET_ENLARGE) = range(8)
+MRGS_RESET_KEEP_EXCLUSIVE, MRGS_RESET_KEEP_REFL_ABOVE, MRGS_RESET_KEEP_REFL_BELOW, MRGS_RESET_KEEP_ROUGH_ABOVE = 1, 2, 4, 8
+
+
+class MrgsResetItem(ctypes.Structure):
+    _fields_ = [(n, c_void_p) for n in ("src", "dst", "exp_avg_dst", "exp_avg_sq_dst", "noise")] + \
+               [(n, c_int32) for n in ("width", "rule", "keep", "reserved")] + [("a", ctypes.c_double), ("b", ctypes.c_double)]
+
+
+class MrgsResetConfig(_Sized):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("P", c_int64), ("refl_raw", c_void_p), ("rough_raw", c_void_p), ("exclusive", c_void_p),
+                ("refl_thr", c_float), ("rough_thr", c_float), ("seed", ctypes.c_uint64)]
+
+
 class MrgsKernelTimes(ctypes.Structure):
     _fields_ = [(n, c_float) for n in ("preprocess_ms", "sort_ms", "duplicate_ms", "render_fwd_ms", "render_bwd_ms",
                                        "preprocess_bwd_ms")]
@@ -372,6 +388,7 @@ SYMBOLS = {
     "mrgs_last_hip_error": (ctypes.c_char_p, []),
     "mrgs_version": (ctypes.c_char_p, []),
     "mrgs_abi_version": (c_int32, []),
+    "mrgs_model_reset": (ctypes.c_int, [ctypes.POINTER(MrgsResetConfig), ctypes.POINTER(MrgsResetItem), c_int32, c_void_p]),
 }
 MRGS_ABI_VERSION = 10   # the revision of include/mrgs.h these ctypes declarations were written against
 
