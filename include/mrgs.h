@@ -1291,6 +1291,69 @@ typedef struct MrgsResetConfig {
 } MrgsResetConfig;
 int mrgs_model_reset(const MrgsResetConfig* cfg, const MrgsResetItem* items, int32_t n_items, void* stream);
 
+/* ---- LPIPS (VGG16) perceptual distance of one image pair (lpipsPyTorch/modules: networks.py:88-96, lpips.py:30-36, utils.py:6-8) -----
+ * Network: thirteen 3 x 3 convolutions (pad 1, bias, ReLU): 3-64, 64-64 | 64-128, 128-128 | 128-256, 256-256, 256-256 | 256-512,
+ * 512-512, 512-512 | 512-512, 512-512, 512-512, a 2 x 2 / stride 2 maximum (floor) at every `|`; stage s works on (H >> s) x (W >> s).
+ * Taps: the ReLU outputs of convolutions 2, 4, 7, 10 and 13.  Input: a = in_scale x + in_offset, then (a - shift_c) / scale_c with shift
+ * (-.030, -.088, -.188), scale (.458, .448, .450); the padding ring of the first convolution is 0 in that space.  Head: per level and
+ * pixel u = f / (sqrt(sum_c f_c^2) + 1e-10) for both images, term_l = mean over the level's pixels of sum_c w_c (u_c - v_c)^2; the
+ * result is the sum of the five.  DIFFERENCE to torch: a pixel whose feature vector is all zero in either image contributes 0 and gets
+ * gradient 0 (torch's sqrt backward yields NaN there, and its forward counts the other image's vector alone).
+ * fp32 throughout: a product sum is an fmaf chain over each chunk of 16 input channels (144 products, on the f32-input matrix
+ * instructions), the chunk sums added in order; one plain fmaf chain in the two 3-channel layers.  No
+ * float atomics: every sum has a fixed order, the same call twice gives the same bits.  No host read or synchronisation in any call.
+ * Images x, y: [3,H,W] fp32 planes.  Activations inside the workspace are channel-last [H_s][W_s][C].
+ *
+ * Weights: mrgs_lpips_pack_weights reads torch-layout device tensors (conv_w[i] [Cout,Cin,3,3], conv_b[i] [Cout], lin_w[l] [C_l]) and
+ * writes ONE blob of mrgs_lpips_weights_bytes() (117.7 MB; 256-byte aligned): per convolution the forward matrix [9][Cin][Cout], the bias,
+ * and the matrix of the backward-to-data pass [9][Cout][Cin] with the taps flipped; then the five lin vectors.
+ * Workspace: mrgs_lpips_ws_bytes(H, W, with_grad), 0 for sizes the calls refuse; 256-byte aligned.  With H W = n pixels, in floats:
+ *   with_grad = 1: the 13 ReLU outputs of x (270 n) + the 5 taps of y (122 n) + two ping-pong buffers of 64 n for y (they carry the
+ *     gradient in backward) + the pooled x (16 n) + the head's gradient of one level (64 n) = 600 n floats: 1.54 GB at 800 x 800.
+ *   with_grad = 0: two ping-pong buffers per image, 256 n floats: 0.66 GB at 800 x 800; the head runs level by level.
+ *   Both: 5 x 1024 partial rows of 16 bytes.  The workspace of a with_grad forward must reach the backward unchanged.
+ * mrgs_lpips_forward: terms[6] (device) = the five level terms and their sum.  mrgs_lpips_backward: g_total = device scalar, the upstream
+ * gradient of terms[5]; g_x [3,H,W] is written in full (d terms[5] / d x times g_total); y gets none.  May be called again on the same
+ * workspace: it changes only the gradient buffers.
+ * mrgs_lpips_ws_offsets: byte offsets inside a with_grad workspace of the 13 stored ReLU outputs of x, then of the 5 taps of y (tests).
+ * MRGS_E_BAD_ARG before any launch: wrong struct_size, H or W < 16 (the last stage would be empty) or H W > 2^24, with_grad other than
+ * 0 / 1 (backward: other than 1), a NULL pointer, a blob or workspace not 256-byte aligned, ws_bytes too small. */
+typedef struct MrgsLpipsConfig {
+    uint32_t struct_size;           /* = sizeof(MrgsLpipsConfig) */
+    int32_t H, W;
+    float in_scale, in_offset;
+    int32_t with_grad;
+} MrgsLpipsConfig;
+size_t mrgs_lpips_weights_bytes(void);
+int mrgs_lpips_pack_weights(const float* const* conv_w /*[13]*/, const float* const* conv_b /*[13]*/, const float* const* lin_w /*[5]*/,
+                            void* blob, void* stream);
+size_t mrgs_lpips_ws_bytes(int32_t H, int32_t W, int32_t with_grad);
+int mrgs_lpips_ws_offsets(int32_t H, int32_t W, size_t* offsets /*[18]*/);
+int mrgs_lpips_forward(const MrgsLpipsConfig* cfg, const void* blob, const float* x, const float* y, void* ws, size_t ws_bytes,
+                       float* terms /*[6]*/, void* stream);
+int mrgs_lpips_backward(const MrgsLpipsConfig* cfg, const void* blob, void* ws, const float* g_total, float* g_x, void* stream);
+/* One convolution launch of the network on caller tensors (tests).  (Cin, Cout) is one of the eight pairs above and names the weights
+ * w [Cout,Cin,3,3] (torch layout; packed into ws first, ws_bytes >= 36 Cin Cout).  backward = 0: in [n][H][W][Cin] -> out [n][H][W][Cout]
+ * = conv + bias (bias nullable).  backward = 1: the data gradient, in [n][H][W][Cout] -> out [n][H][W][Cin], no bias.  Then, in this
+ * order: + add (nullable, shaped as out), ReLU when relu = 1, 0 where gate <= 0 (nullable, shaped as out).  The 3-channel side is planes
+ * [n][3][H][W] instead: the input of the forward 3-64 (mapped as the network's input when zscore = 1, as it stands when 0) and the output
+ * of the backward 64-3 (times in_scale / scale_c when zscore = 1); these two launches take no add and no gate.  n_images 1 or 2; any H, W
+ * >= 1.  MRGS_E_BAD_ARG: wrong struct_size, an unserved pair, NULL in / w / out / ws, pointers not 16-byte aligned, a short ws. */
+typedef struct MrgsLpipsConvConfig {
+    uint32_t struct_size;           /* = sizeof(MrgsLpipsConvConfig) */
+    int32_t H, W, Cin, Cout, n_images, backward, relu, zscore;
+    float in_scale, in_offset;
+} MrgsLpipsConvConfig;
+int mrgs_lpips_debug_conv(const MrgsLpipsConvConfig* cfg, const float* in, const float* w, const float* bias, const float* add,
+                          const float* gate, float* out, void* ws, size_t ws_bytes, void* stream);
+/* The 2 x 2 maximum on a [H][W][C] (C a multiple of 4, H, W >= 1).  g_pooled NULL: out [H/2][W/2][C] = the maxima.  Otherwise out
+ * [H][W][C] = g_pooled's entry at the window's FIRST maximum in row-major order (as torch), 0 elsewhere and in a last odd row or column. */
+int mrgs_lpips_debug_pool(int32_t H, int32_t W, int32_t C, const float* a, const float* g_pooled, float* out, void* stream);
+/* The head of one level alone: fx, fy [P][C] (C in {64, 128, 256, 512}), w [C]; ws = 1024 rows of 16 bytes.  term (device scalar) = the
+ * level term; with g (device scalar) and g_fx [P][C] also its gradient with respect to fx times g. */
+int mrgs_lpips_debug_head(int64_t P, int32_t C, const float* fx, const float* fy, const float* w, void* ws, size_t ws_bytes, float* term,
+                          const float* g, float* g_fx, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -215,6 +215,16 @@ class MrgsResetConfig(_Sized):
                 ("refl_thr", c_float), ("rough_thr", c_float), ("seed", ctypes.c_uint64)]
 
 
+class MrgsLpipsConfig(_Sized):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("H", c_int32), ("W", c_int32), ("in_scale", c_float), ("in_offset", c_float),
+                ("with_grad", c_int32)]
+
+
+class MrgsLpipsConvConfig(_Sized):
+    _fields_ = [("struct_size", ctypes.c_uint32)] + [(n, c_int32) for n in ("H", "W", "Cin", "Cout", "n_images", "backward", "relu", "zscore")] + \
+               [("in_scale", c_float), ("in_offset", c_float)]
+
+
 class MrgsKernelTimes(ctypes.Structure):
     _fields_ = [(n, c_float) for n in ("preprocess_ms", "sort_ms", "duplicate_ms", "render_fwd_ms", "render_bwd_ms",
                                        "preprocess_bwd_ms")]
@@ -389,6 +399,16 @@ SYMBOLS = {
     "mrgs_version": (ctypes.c_char_p, []),
     "mrgs_abi_version": (c_int32, []),
     "mrgs_model_reset": (ctypes.c_int, [ctypes.POINTER(MrgsResetConfig), ctypes.POINTER(MrgsResetItem), c_int32, c_void_p]),
+    "mrgs_lpips_weights_bytes": (c_size_t, []),
+    "mrgs_lpips_pack_weights": (ctypes.c_int, [ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p), c_void_p, c_void_p]),
+    "mrgs_lpips_ws_bytes": (c_size_t, [c_int32, c_int32, c_int32]),
+    "mrgs_lpips_ws_offsets": (ctypes.c_int, [c_int32, c_int32, ctypes.POINTER(c_size_t)]),
+    "mrgs_lpips_forward": (ctypes.c_int, [ctypes.POINTER(MrgsLpipsConfig), c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "mrgs_lpips_backward": (ctypes.c_int, [ctypes.POINTER(MrgsLpipsConfig), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mrgs_lpips_debug_conv": (ctypes.c_int, [ctypes.POINTER(MrgsLpipsConvConfig)] + [c_void_p] * 7 + [c_size_t, c_void_p]),
+    "mrgs_lpips_debug_pool": (ctypes.c_int, [c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mrgs_lpips_debug_head": (ctypes.c_int, [c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p,
+                                             c_void_p]),
 }
 MRGS_ABI_VERSION = 10   # the revision of include/mrgs.h these ctypes declarations were written against
 

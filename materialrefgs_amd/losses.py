@@ -6,11 +6,13 @@ elementwise kernels and their autograd mirror); there is no torch fallback -- CP
 Differences a caller sees: the entries of `tb_dict` are 0-d device tensors instead of python floats (the reference calls
 `.item()` five times per iteration, each a host sync; `float(x)` still works), only the first image is differentiated (a second
 image that requires grad raises ValueError while grad mode is on), `lpips_loss` needs network weights that are not part of this build
-(it raises NotImplementedError when enabled and no network is registered), and the two Sobel smoothness terms
+(the native network of materialrefgs_amd.lpips from the files MRGS_LPIPS_WEIGHTS names, a network registered with `set_lpips_fn`, or the
+`lpips` package; it raises NotImplementedError when enabled and none of them is there), and the two Sobel smoothness terms
 (`first_order_edge_aware_loss`, `smooth_loss`; kornia is not needed) run in libmrgs.so too for fp32 device tensors
 (materialrefgs_amd.smoothness, csrc/mrgs_smooth.hip) and as kornia's Sobel restated in torch for every other input.
 """
 import ctypes
+import os
 
 import torch
 
@@ -174,6 +176,10 @@ def set_lpips_fn(fn):
 def lpips_loss(x, y, net="vgg"):
     """utils/loss_utils.py:35-43: the registered network on the images mapped from [0, 1] to [-1, 1], mean over the batch."""
     global _LPIPS_FN
+    if _LPIPS_FN is None and os.environ.get("MRGS_LPIPS_WEIGHTS"):
+        # the native network (materialrefgs_amd.lpips) from the user's weight files; not registered, so unsetting the variable undoes it
+        from . import lpips as native_lpips
+        return native_lpips.from_env(os.environ["MRGS_LPIPS_WEIGHTS"])(x * 2.0 - 1.0, y * 2.0 - 1.0).mean()
     if _LPIPS_FN is None:
         try:
             import lpips as lpips_module           # the reference's own lazy construction (:38-41), where the package exists
@@ -190,6 +196,10 @@ def check_loss_config(opt):
     """Optional set-up check (a training script may call it before iteration 1): the reference enables the LPIPS term by default
     (arguments/__init__.py:223-225: use_perceptual_loss = True, active after perceptual_loss_start_iter = 18 000); raise now rather
     than 18 000 iterations into a run when no network is registered and the `lpips` package is absent."""
+    if getattr(opt, "use_perceptual_loss", False) and _LPIPS_FN is None and os.environ.get("MRGS_LPIPS_WEIGHTS"):
+        from . import lpips as native_lpips
+        native_lpips.from_env(os.environ["MRGS_LPIPS_WEIGHTS"])        # a missing or unusable file raises here, naming the variable
+        return
     if getattr(opt, "use_perceptual_loss", False) and _LPIPS_FN is None:
         try:
             import lpips  # noqa: F401
@@ -202,7 +212,7 @@ def calculate_loss(viewpoint_camera, pc, render_pkg, opt, iteration, image_weigh
     """utils/loss_utils.py:142-228: same arguments, same keys in tb_dict (values are 0-d tensors, see module docstring)."""
     use_perc = bool(getattr(opt, "use_perceptual_loss", False))
     global _LPIPS_WARNED
-    if use_perc and _LPIPS_FN is None and not _LPIPS_WARNED:
+    if use_perc and _LPIPS_FN is None and not _LPIPS_WARNED and not os.environ.get("MRGS_LPIPS_WEIGHTS"):
         # the reference's defaults reach this state (the term is on by default and becomes active at iteration 18 000): training runs
         # as the reference does until then; say once what will happen at that iteration instead of failing at iteration 1
         _LPIPS_WARNED = True
