@@ -466,6 +466,47 @@ int mrgs_surfel_features_forward(const MrgsSurfelParams* p, float* opacity, floa
 int mrgs_surfel_features_backward(const MrgsSurfelParams* p, const float* g_opacity, const float* g_scales, const float* g_rotations,
                                   const float* g_features, const MrgsSurfelGrads* grads, const float* g_xyz_upstream, void* stream);
 
+/* ---- per-gaussian shading of the volume renderer (fused glue) ---------------------------------------------------
+ * One kernel instead of the chain of torch ops render_volume runs per view before the rasterizer call (gaussian_renderer/__init__.py:
+ * 559-661 with opt.indirect false, utils/refl_utils.py:426-445, scene/light.py:99-129): the GaussianModel getters, get_normal, and
+ * get_full_color_volume --
+ *   n = facing unit third column of R(q) (facing `campos`), w_o = safe_normalize(rays_o - xyz), NdotV = w_o . n,
+ *   rays_refl = safe_normalize(2 n NdotV - w_o),
+ *   diffuse  = sigmoid(fetch(diffuse level 0, n)) (1 - refl) ori_color,
+ *   specular = sigmoid(trilinear fetch(specular chain, rays_refl, get_mip(roughness))) ((0.04 (1 - refl) + ori_color refl) fg0.x + fg0.y)
+ * where fg0 = the FG LUT at (NdotV, roughness).clamp(0, 1) OF GAUSSIAN 0 for every gaussian, as the reference indexes it
+ * (refl_utils.py:443).  `campos` (camera_center) and `rays_o` (the origin of sample_camera_rays) are the reference's two differently
+ * rounded camera positions; a caller with one passes it twice.  Pointers are device pointers to contiguous fp32 tensors in the
+ * GaussianModel layout (MrgsSurfelParams); lut [lut_res,lut_res,2].  viewmatrix (16 floats, world_view_transform as stored; "pgsr") or NULL. */
+typedef struct MrgsVolumeParams {
+    uint32_t struct_size;    /* = sizeof(MrgsVolumeParams); checked like MrgsRasterConfig::struct_size */
+    int32_t P;
+    const float *xyz, *scaling_raw, *rotation_raw, *opacity_raw, *refl_raw, *rough_raw, *ori_color_raw, *campos, *rays_o, *lut, *viewmatrix;
+    int32_t lut_res;
+    int32_t reserved;        /* 0 */
+} MrgsVolumeParams;
+typedef struct MrgsVolumeGrads {   /* gradients w.r.t. the raw parameters, same shapes, fully written */
+    uint64_t struct_size;    /* = sizeof(MrgsVolumeGrads) */
+    float *d_xyz, *d_scaling, *d_rotation, *d_opacity, *d_refl, *d_rough, *d_ori_color;
+} MrgsVolumeGrads;
+/* bytes of the backward's scratch `ws` (8-byte aligned; the backward clears it itself).  The library allocates nothing. */
+size_t mrgs_volume_features_ws_bytes(void);
+/* outputs: opacity[P,1], scales[P,2], rotations[P,4] (unit), colors_precomp[P,3] = specular + diffuse, features[P,11] = (roughness, refl,
+ * diffuse[3], specular[3], ori_color[3]); with viewmatrix features[P,12], channel 11 = get_distance (|facing normal . centre| in the
+ * camera frame) -- exactly what render_volume feeds GaussianRasterizer.  `diffuse` is a chain of which level 0 is fetched (no roughness).
+ * `features` 16-byte aligned.  MRGS_E_BAD_ARG before any launch: a wrong struct_size, P < 0, lut_res < 1, a malformed chain, with P > 0
+ * a NULL input or output.  P == 0: MRGS_OK, nothing launched. */
+int mrgs_volume_features_forward(const MrgsVolumeParams* p, const MrgsEnvMips* specular, const MrgsEnvMips* diffuse, float* opacity,
+                                 float* scales, float* rotations, float* colors_precomp, float* features, void* stream);
+/* The exact derivative (flip sign constant; clamp(0,1) and safe_normalize's clamp_min(1e-20) as torch's): upstream gradients of the five
+ * outputs (any may be NULL = zero; g_features 16-byte aligned), g_xyz_upstream [P,3] (NULL = zero) added into d_xyz as in
+ * mrgs_surfel_features_backward.  Texel gradients are accumulated into grad / grad_copies of BOTH chains (the caller zero-fills and sums
+ * them, as for mrgs_envmap_lookup_backward).  The sum over all rows of dL/dfg0 goes through `ws`; a one-thread launch behind the
+ * kernel on the same stream adds its share to row 0's d_xyz, d_rotation and d_rough.  Two launches and a 64-byte clear. */
+int mrgs_volume_features_backward(const MrgsVolumeParams* p, const MrgsEnvMips* specular, const MrgsEnvMips* diffuse, const float* g_opacity,
+                                  const float* g_scales, const float* g_rotations, const float* g_colors_precomp, const float* g_features,
+                                  const MrgsVolumeGrads* grads, const float* g_xyz_upstream, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- per-pixel maps of the surfel renderer (fused glue) ------------------------------------------------------------
  * compute_2dgs_normal_and_regularizations (gaussian_renderer/__init__.py:42-90) + depths_to_points / depth_to_normal
  * (utils/point_utils.py:9-37) + the normal_map of render_surfel (:419-421) in one kernel each way.

@@ -90,6 +90,17 @@ class MrgsSurfelGrads(ctypes.Structure):
                                         "d_indirect_dc", "d_indirect_rest")]
 
 
+class MrgsVolumeParams(_Sized):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("P", c_int32)] + \
+               [(n, c_void_p) for n in ("xyz", "scaling_raw", "rotation_raw", "opacity_raw", "refl_raw", "rough_raw", "ori_color_raw", "campos",
+                                        "rays_o", "lut", "viewmatrix")] + [("lut_res", c_int32), ("reserved", c_int32)]
+
+
+class MrgsVolumeGrads(_Sized):
+    _fields_ = [("struct_size", ctypes.c_uint64)] + [(n, c_void_p) for n in ("d_xyz", "d_scaling", "d_rotation", "d_opacity", "d_refl", "d_rough",
+                                                                             "d_ori_color")]
+
+
 class MrgsMapsFrame(ctypes.Structure):
     _fields_ = [("H", c_int32), ("W", c_int32), ("view_rot", c_float * 9), ("ray_matrix", c_float * 9), ("ray_origin", c_float * 3),
                 ("depth_ratio", c_float), ("pgsr_fx", c_float), ("pgsr_fy", c_float), ("rend_distance", c_void_p), ("g_rend_distance", c_void_p)]
@@ -409,6 +420,11 @@ SYMBOLS = {
     "mrgs_lpips_debug_pool": (ctypes.c_int, [c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "mrgs_lpips_debug_head": (ctypes.c_int, [c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p,
                                              c_void_p]),
+    "mrgs_volume_features_ws_bytes": (c_size_t, []),
+    "mrgs_volume_features_forward": (ctypes.c_int, [ctypes.POINTER(MrgsVolumeParams), ctypes.POINTER(MrgsEnvMips), ctypes.POINTER(MrgsEnvMips)] +
+                                     [c_void_p] * 6),
+    "mrgs_volume_features_backward": (ctypes.c_int, [ctypes.POINTER(MrgsVolumeParams), ctypes.POINTER(MrgsEnvMips), ctypes.POINTER(MrgsEnvMips)] +
+                                      [c_void_p] * 5 + [ctypes.POINTER(MrgsVolumeGrads), c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 MRGS_ABI_VERSION = 10   # the revision of include/mrgs.h these ctypes declarations were written against
 

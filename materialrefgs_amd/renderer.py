@@ -27,7 +27,7 @@ from ._lib import MrgsMapsFrame, MrgsSurfelGrads, MrgsSurfelParams
 from .gs_utils import build_scaling_rotation, eval_sh, flip_align_view, linear_to_srgb, safe_normalize
 from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer, deferred_raster_count
 from .shading import (EnvLight, GradStackHandoff, _kinv_tuple, get_full_color_volume, get_full_color_volume_indirect,
-                      get_specular_color_surfel, shade_and_composite_surfel)
+                      get_specular_color_surfel, shade_and_composite_surfel, volume_features, volume_raw_model)
 
 
 class SurfelModel:
@@ -123,6 +123,7 @@ class _GlueLink:
 
 
 _FUSE_GLUE = os.environ.get("MRGS_NO_GLUE_EPILOGUE", "0") != "1"
+_NATIVE_VOLUME = os.environ.get("MRGS_NO_VOLUME_KERNEL", "0") != "1"      # render_volume's per-gaussian stage in HIP (shading.volume_features)
 
 
 class _SurfelFeatures(torch.autograd.Function):
@@ -579,41 +580,51 @@ def render_volume(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, ov
     weight, environment lookups: utils/refl_utils.py:426-484) and the rasterizer blends the shaded colour (`colors_precomp =
     specular + diffuse`) plus S = 11 material channels (roughness, refl, diffuse 3, specular 3, ori_color 3; 18 with opt.indirect:
     + visibility, indirect 3, direct_light 3).  SH-indirect branch (`pipe.use_asg` False) by default.  Environment lookups and the rasterizer run in
-    libmrgs.so; the per-gaussian elementwise glue is torch, as in the reference.  `pipe.compute_cov3D_python`: cov3D_precomp_of."""
+    libmrgs.so, and so does the whole per-gaussian stage without `opt.indirect` (shading.volume_features: one kernel each way); with
+    `opt.indirect` or `pipe.compute_cov3D_python` (cov3D_precomp_of) the per-gaussian elementwise glue is torch, as in the reference."""
     if opt is None:
         opt = SimpleNamespace(indirect=False)
     means2D = zero_leaf(pc.get_xyz)       # screenspace_points (gaussian_renderer/__init__.py:229-233): its .grad receives the 2D-mean gradients
     rasterizer = GaussianRasterizer(raster_settings=_raster_settings(viewpoint_camera, pc, pipe, bg_color, scaling_modifier))
-    means3D, opacity = pc.get_xyz, pc.get_opacity
-    refl, ori_color, roughness = pc.get_refl, pc.get_ori_color, pc.get_rough
-    if getattr(pipe, "compute_cov3D_python", False):       # :572-586
-        scales, rotations, cov3D_precomp = None, None, cov3D_precomp_of(pc, viewpoint_camera, scaling_modifier)
-    else:
-        scales, rotations, cov3D_precomp = pc.get_scaling, pc.get_rotation, None
-    dir_pp = means3D - viewpoint_camera.camera_center
-    dir_pp_normalized = dir_pp / dir_pp.norm(dim=1, keepdim=True)
-    normals = pc.get_normal(scaling_modifier, dir_pp_normalized)
-    w_o = -dir_pp_normalized
-    reflection = 2 * torch.sum(normals * w_o, dim=1, keepdim=True) * normals - w_o
-    if getattr(pipe, "use_asg", False):                                      # :604-627
-        from .gs_utils import asg_indirect
-        indirect = asg_indirect(pc.get_asg, pc.asg_param, normals, reflection)
-    else:
-        shs_indirect = pc.get_indirect.transpose(1, 2).reshape(-1, 3, (pc.max_sh_degree + 1) ** 2)
-        indirect = torch.clamp_min(eval_sh(3, shs_indirect, reflection), 0.0)
     indirect_on = bool(getattr(opt, "indirect", False))
-    if indirect_on:
-        diffuse, specular, extra = get_full_color_volume_indirect(pc.get_envmap_2, means3D, ori_color, viewpoint_camera.HWK, viewpoint_camera.R,
-                                                                  viewpoint_camera.T, normals.contiguous(), opacity, refl_strength=refl,
-                                                                  roughness=roughness, pc=pc, indirect_light=indirect)
-        features = torch.cat((roughness, refl, diffuse, specular, ori_color, extra["visibility"], indirect, extra["direct_light"]), dim=-1)
+    # activations, facing normal, view and mirror directions, the two environment lookups, the split-sum weight and the feature concat
+    # (__init__.py:559-661 without opt.indirect): one HIP kernel each way (shading.volume_features; the centres come back as an output of
+    # the same node, as in render_surfel).  opt.indirect, compute_cov3D_python and models that are not the raw GaussianModel tensors take
+    # the chain of torch ops below, as does everything with MRGS_NO_VOLUME_KERNEL=1.
+    if _NATIVE_VOLUME and not indirect_on and not getattr(pipe, "compute_cov3D_python", False) and volume_raw_model(pc) is not None:
+        opacity, scales, rotations, colors_precomp, features, means3D = volume_features(pc, viewpoint_camera, pc.get_envmap_2, flag=flag,
+                                                                                        pass_xyz=True)
+        cov3D_precomp = None
     else:
-        diffuse, specular = get_full_color_volume(pc.get_envmap_2, means3D, ori_color, viewpoint_camera.HWK, viewpoint_camera.R,
-                                                  viewpoint_camera.T, normals.contiguous(), opacity, refl_strength=refl, roughness=roughness)
-        features = torch.cat((roughness, refl, diffuse, specular, ori_color), dim=-1)
-    colors_precomp = specular + diffuse
-    if flag != "2dgs":          # "pgsr": + the plane distance as the last channel, back as "rend_distance" (:657-661, 744-746)
-        features = torch.cat((features, get_distance(scaling_modifier, means3D, viewpoint_camera, pc)), dim=-1)
+        means3D, opacity = pc.get_xyz, pc.get_opacity
+        refl, ori_color, roughness = pc.get_refl, pc.get_ori_color, pc.get_rough
+        if getattr(pipe, "compute_cov3D_python", False):       # :572-586
+            scales, rotations, cov3D_precomp = None, None, cov3D_precomp_of(pc, viewpoint_camera, scaling_modifier)
+        else:
+            scales, rotations, cov3D_precomp = pc.get_scaling, pc.get_rotation, None
+        dir_pp = means3D - viewpoint_camera.camera_center
+        dir_pp_normalized = dir_pp / dir_pp.norm(dim=1, keepdim=True)
+        normals = pc.get_normal(scaling_modifier, dir_pp_normalized)
+        w_o = -dir_pp_normalized
+        reflection = 2 * torch.sum(normals * w_o, dim=1, keepdim=True) * normals - w_o
+        if getattr(pipe, "use_asg", False):                                      # :604-627
+            from .gs_utils import asg_indirect
+            indirect = asg_indirect(pc.get_asg, pc.asg_param, normals, reflection)
+        else:
+            shs_indirect = pc.get_indirect.transpose(1, 2).reshape(-1, 3, (pc.max_sh_degree + 1) ** 2)
+            indirect = torch.clamp_min(eval_sh(3, shs_indirect, reflection), 0.0)
+        if indirect_on:
+            diffuse, specular, extra = get_full_color_volume_indirect(pc.get_envmap_2, means3D, ori_color, viewpoint_camera.HWK, viewpoint_camera.R,
+                                                                      viewpoint_camera.T, normals.contiguous(), opacity, refl_strength=refl,
+                                                                      roughness=roughness, pc=pc, indirect_light=indirect)
+            features = torch.cat((roughness, refl, diffuse, specular, ori_color, extra["visibility"], indirect, extra["direct_light"]), dim=-1)
+        else:
+            diffuse, specular = get_full_color_volume(pc.get_envmap_2, means3D, ori_color, viewpoint_camera.HWK, viewpoint_camera.R,
+                                                      viewpoint_camera.T, normals.contiguous(), opacity, refl_strength=refl, roughness=roughness)
+            features = torch.cat((roughness, refl, diffuse, specular, ori_color), dim=-1)
+        colors_precomp = specular + diffuse
+        if flag != "2dgs":          # "pgsr": + the plane distance as the last channel, back as "rend_distance" (:657-661, 744-746)
+            features = torch.cat((features, get_distance(scaling_modifier, means3D, viewpoint_camera, pc)), dim=-1)
     contrib, rendered_image, rendered_features, radii, allmap = rasterizer(
         means3D=means3D, means2D=means2D, shs=None, colors_precomp=colors_precomp, features=features, opacities=opacity, scales=scales,
         rotations=rotations, cov3D_precomp=cov3D_precomp)
