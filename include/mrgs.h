@@ -1395,6 +1395,58 @@ int mrgs_lpips_debug_pool(int32_t H, int32_t W, int32_t C, const float* a, const
 int mrgs_lpips_debug_head(int64_t P, int32_t C, const float* fx, const float* fy, const float* w, void* ws, size_t ws_bytes, float* term,
                           const float* g, float* g_fx, void* stream);
 
+/* ---- evaluation of one rendered view (eval.py:23-102; evaluate_psnr / training_report, train_refreal.py:1656-1735) --------------------
+ * mrgs_eval_metrics: image, gt [3,H,W] fp32 planes (a [4,H,W] ground truth passes its first three), both clamped to [0, 1] AS THEY ARE
+ * READ (eval.py:44-46; no clamped copy is written).  Forward only, two launches, no host read.  out (device, 8 floats at any 4-byte aligned
+ * address, e.g. row idx of an [n_views,8] table):
+ *   [0] psnr_image    20 log10(1 / sqrt(mse over all 3 H W values))      utils/image_utils.py:20-23 on the [1,3,H,W] tensors of eval.py:51
+ *   [1] ssim          utils/loss_utils.py:83-119: 11x11 window, sigma 1.5, zero padding, C1 = 0.01^2, C2 = 0.03^2, mean over everything
+ *   [2] l1            mean |image - gt|
+ *   [3] psnr_channels mean over the channels of the per-channel psnr: psnr(image, gt).mean() on [3,H,W] tensors (train_refreal.py:1704,
+ *                     :1730), the convention of out_terms[6] of mrgs_loss_forward
+ *   [4..6] mse per channel    [7] 0
+ * A zero mse gives +inf as the reference does.  Sums have a fixed order: two calls give the same bits.  ws: mrgs_eval_metrics_ws_bytes
+ * (the per-workgroup partials, 48 bytes per 32x32 tile; 16-byte aligned).
+ * MRGS_E_BAD_ARG before any HIP call: wrong struct_size, H or W <= 0, flags != 0, a NULL or misaligned pointer; MRGS_E_WORKSPACE for a
+ * short ws; MRGS_E_UNSUPPORTED for H > 65535 * 32. */
+typedef struct MrgsEvalConfig {
+    uint32_t struct_size;           /* = sizeof(MrgsEvalConfig) */
+    int32_t H, W;
+    uint32_t flags;                 /* 0 */
+} MrgsEvalConfig;
+size_t mrgs_eval_metrics_ws_bytes(int32_t H, int32_t W);
+int mrgs_eval_metrics(const MrgsEvalConfig* cfg, const float* image, const float* gt, void* ws, size_t ws_bytes, float* out /*[8]*/,
+                      void* stream);
+/* mrgs_export_rgb8: 1..MRGS_EXPORT_MAX_MAPS maps of one view, each [1,H,W] or [3,H,W] fp32 planes, to out uint8 [n_maps,H,W,3]
+ * (pixel-interleaved, what a PNG row is; 4-byte aligned); a one-channel map is replicated to three bytes (eval.py:63-64).  Modes:
+ *   UNIT    byte = trunc(clamp(x * 255 + 0.5, 0, 255)), the product and the sum rounded separately: torchvision.utils.save_image's
+ *           mul(255).add_(0.5).clamp_(0, 255).to(uint8)
+ *   NORMAL  the same after x * 0.5 + 0.5 (two roundings again; eval.py:56)
+ *   DEPTH   visualize_depth (utils/image_utils.py:73-80) in fp32 and in its order: level = trunc(clip(((d - min) / (1e-20f + max - min))
+ *           * 255, 0, 255)) with min / max over the map (reduced on the device, NaN skipped), the division correctly rounded; the three
+ *           bytes are row `level` of the table mrgs_eval_jet_table returns (256 x 3, RGB).  One channel only.
+ * The table is THIS LIBRARY'S OWN jet -- at v = level / 255 in double r = clamp(1.5 - |4 v - 3|, 0, 1), g = clamp(1.5 - |4 v - 2|, 0, 1),
+ * b = clamp(1.5 - |4 v - 1|, 0, 1), byte = floor(255 c + 0.5) -- parity with cv2's COLORMAP_JET table unpinned; the level is what follows the
+ * reference's statement.
+ * NaN gives byte 0 in UNIT / NORMAL and level 0 in DEPTH (the reference's cast is undefined there).
+ * At most two launches (one when no map is DEPTH), no host read.  ws: mrgs_export_ws_bytes(), needed (8-byte aligned) only with a DEPTH map.
+ * MRGS_E_BAD_ARG before any HIP call: wrong struct_size, H or W <= 0, flags != 0, n_maps outside 1..MRGS_EXPORT_MAX_MAPS, a NULL or
+ * misaligned pointer, channels other than 1 / 3, an unknown mode, DEPTH with three channels; MRGS_E_WORKSPACE for a short ws. */
+#define MRGS_EXPORT_MAX_MAPS 16
+enum { MRGS_EXPORT_UNIT = 0, MRGS_EXPORT_NORMAL = 1, MRGS_EXPORT_DEPTH = 2 };
+typedef struct MrgsExportMap {
+    const float* data;              /* [channels,H,W] */
+    int32_t channels, mode;
+} MrgsExportMap;
+typedef struct MrgsExportConfig {
+    uint32_t struct_size;           /* = sizeof(MrgsExportConfig) */
+    int32_t H, W, n_maps;
+    uint32_t flags;                 /* 0 */
+} MrgsExportConfig;
+size_t mrgs_export_ws_bytes(void);
+int mrgs_export_rgb8(const MrgsExportConfig* cfg, const MrgsExportMap* maps, void* ws, size_t ws_bytes, uint8_t* out, void* stream);
+int mrgs_eval_jet_table(uint8_t* table768 /*host, [256][3]*/);
+
 #ifdef __cplusplus
 }
 #endif

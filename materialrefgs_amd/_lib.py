@@ -236,6 +236,22 @@ class MrgsLpipsConvConfig(_Sized):
                [("in_scale", c_float), ("in_offset", c_float)]
 
 
+class MrgsEvalConfig(_Sized):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("H", c_int32), ("W", c_int32), ("flags", ctypes.c_uint32)]
+
+
+MRGS_EXPORT_MAX_MAPS = 16
+MRGS_EXPORT_UNIT, MRGS_EXPORT_NORMAL, MRGS_EXPORT_DEPTH = 0, 1, 2
+
+
+class MrgsExportMap(ctypes.Structure):
+    _fields_ = [("data", c_void_p), ("channels", c_int32), ("mode", c_int32)]
+
+
+class MrgsExportConfig(_Sized):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("H", c_int32), ("W", c_int32), ("n_maps", c_int32), ("flags", ctypes.c_uint32)]
+
+
 class MrgsKernelTimes(ctypes.Structure):
     _fields_ = [(n, c_float) for n in ("preprocess_ms", "sort_ms", "duplicate_ms", "render_fwd_ms", "render_bwd_ms",
                                        "preprocess_bwd_ms")]
@@ -425,6 +441,11 @@ SYMBOLS = {
                                      [c_void_p] * 6),
     "mrgs_volume_features_backward": (ctypes.c_int, [ctypes.POINTER(MrgsVolumeParams), ctypes.POINTER(MrgsEnvMips), ctypes.POINTER(MrgsEnvMips)] +
                                       [c_void_p] * 5 + [ctypes.POINTER(MrgsVolumeGrads), c_void_p, c_void_p, c_size_t, c_void_p]),
+    "mrgs_eval_metrics_ws_bytes": (c_size_t, [c_int32, c_int32]),
+    "mrgs_eval_metrics": (ctypes.c_int, [ctypes.POINTER(MrgsEvalConfig), c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "mrgs_export_ws_bytes": (c_size_t, []),
+    "mrgs_export_rgb8": (ctypes.c_int, [ctypes.POINTER(MrgsExportConfig), ctypes.POINTER(MrgsExportMap), c_void_p, c_size_t, c_void_p, c_void_p]),
+    "mrgs_eval_jet_table": (ctypes.c_int, [c_void_p]),
 }
 MRGS_ABI_VERSION = 10   # the revision of include/mrgs.h these ctypes declarations were written against
 

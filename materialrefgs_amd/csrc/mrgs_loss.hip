@@ -10,15 +10,14 @@
 //   loss_bwd_kernel   same tiling: the three derivative maps are convolved with the (symmetric) window and combined with the
 //                     pixel values into dL/dimage; L1 sign term, normal and distortion gradients are added in the same pass.
 // Zero padding as F.conv2d(padding=5): pixels outside the image count as 0 in the moments and carry no derivative.
+// The forward's staging, window pass and SSIM point formula are the functions of mrgs_ssim_tile.h, which the evaluation metrics (mrgs_eval.hip) call too.
 #include "mrgs_internal.h"
 #include "mrgs_wave.h"
+#include "mrgs_ssim_tile.h"
 
 namespace {
 
-constexpr int LT = 32;            // tile edge
-constexpr int LP = 4;             // outputs per thread and pass (256 threads x 4 = 32 x 32)
-constexpr int LR = 5;             // window radius (window_size 11, loss_utils.py:91)
-constexpr int LH = LT + 2 * LR;   // tile + halo
+// LT, LP, LR, LH and the tile passes: mrgs_ssim_tile.h (shared with the evaluation metrics)
 constexpr int NPART = 8;          // floats per workgroup partial: ssim, l1, sq, normal, dist
 
 struct LossArgs {
@@ -41,58 +40,13 @@ __global__ __launch_bounds__(256) void loss_fwd_kernel(LossArgs a, const float* 
     const size_t HW = (size_t)H * W;
     const float* I1 = img + c * HW;
     const float* I2 = gt + c * HW;
-    {   // all loads of the tile in flight before the first LDS store (a rolled loop waits for every round trip in turn)
-        constexpr int NL = (LH * LH + 255) / 256;
-        float v1[NL], v2[NL];
-#pragma unroll
-        for (int n = 0; n < NL; ++n) {
-            const int i = tid + n * 256, r = i / LH, cc = i - r * LH, y = by + r - LR, x = bx + cc - LR;
-            const bool in = (i < LH * LH) & (x >= 0) & (x < W) & (y >= 0) & (y < H);
-            v1[n] = in ? I1[(size_t)y * W + x] : 0.f;
-            v2[n] = in ? I2[(size_t)y * W + x] : 0.f;
-        }
-#pragma unroll
-        for (int n = 0; n < NL; ++n) {
-            const int i = tid + n * 256, r = i / LH, cc = i - r * LH;
-            if (i < LH * LH) { s1[r][cc] = v1[n]; s2[r][cc] = v2[n]; }
-        }
-    }
+    ssim_tile_stage<false>(I1, I2, H, W, bx, by, tid, s1, s2);
     __syncthreads();
-    // rows: a thread produces LP consecutive outputs of one row from LP + 10 inputs (sliding window: 3.1 LDS reads per output
-    // and quantity instead of 11)
-    for (int it = tid; it < LH * (LT / LP); it += 256) {
-        const int r = it / (LT / LP), c0 = (it - r * (LT / LP)) * LP;
-        float p[LP + 2 * LR], q[LP + 2 * LR];
-#pragma unroll
-        for (int j = 0; j < LP + 2 * LR; ++j) { p[j] = s1[r][c0 + j]; q[j] = s2[r][c0 + j]; }
-#pragma unroll
-        for (int o = 0; o < LP; ++o) {
-            float m1 = 0.f, m2 = 0.f, e11 = 0.f, e22 = 0.f, e12 = 0.f;
-#pragma unroll
-            for (int k = 0; k <= 2 * LR; ++k) {
-                const float w = a.w[k], wp = w * p[o + k], wq = w * q[o + k];
-                m1 += wp; m2 += wq; e11 = fmaf(wp, p[o + k], e11); e22 = fmaf(wq, q[o + k], e22); e12 = fmaf(wp, q[o + k], e12);
-            }
-            hz[0][r][c0 + o] = m1; hz[1][r][c0 + o] = m2; hz[2][r][c0 + o] = e11; hz[3][r][c0 + o] = e22; hz[4][r][c0 + o] = e12;
-        }
-    }
+    ssim_tile_rows(a.w, tid, s1, s2, hz);
     __syncthreads();
-    // columns: thread (tx, tg) produces the LP outputs (tx, LP tg .. LP tg + LP - 1)
     const int tx = tid & (LT - 1), y0 = (tid / LT) * LP;
     float mom[5][LP];
-#pragma unroll
-    for (int qn = 0; qn < 5; ++qn) {
-        float v[LP + 2 * LR];
-#pragma unroll
-        for (int j = 0; j < LP + 2 * LR; ++j) v[j] = hz[qn][y0 + j][tx];
-#pragma unroll
-        for (int o = 0; o < LP; ++o) {
-            float acc = 0.f;
-#pragma unroll
-            for (int k = 0; k <= 2 * LR; ++k) acc = fmaf(a.w[k], v[o + k], acc);
-            mom[qn][o] = acc;
-        }
-    }
+    ssim_tile_cols(a.w, tx, y0, hz, mom);
     float part[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
     const int x = bx + tx;
 #pragma unroll
@@ -100,13 +54,9 @@ __global__ __launch_bounds__(256) void loss_fwd_kernel(LossArgs a, const float* 
         const int y = by + y0 + o;
         if ((x >= W) | (y >= H)) continue;
         const size_t pix = (size_t)y * W + x;
-        const float mu1 = mom[0][o], mu2 = mom[1][o], e11 = mom[2][o], e22 = mom[3][o], e12 = mom[4][o];
-        const float C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f;            // loss_utils.py:107-108
-        const float mu1_sq = mu1 * mu1, mu2_sq = mu2 * mu2, mu12 = mu1 * mu2;
-        const float sg1 = e11 - mu1_sq, sg2 = e22 - mu2_sq, sg12 = e12 - mu12;
-        const float A1 = 2.f * mu12 + C1, A2 = 2.f * sg12 + C2, B1 = mu1_sq + mu2_sq + C1, B2 = sg1 + sg2 + C2;
-        const float inv = 1.f / (B1 * B2);
-        const float S = A1 * A2 * inv;                                  // :110
+        const float mu1 = mom[0][o], mu2 = mom[1][o];
+        const SsimPoint sp = ssim_point(mu1, mu2, mom[2][o], mom[3][o], mom[4][o]);
+        const float S = sp.S, A1 = sp.A1, A2 = sp.A2, B1 = sp.B1, B2 = sp.B2, inv = sp.inv;
         const size_t CHW = HW * a.C;
         // total derivative with respect to mu1 (sigma1_sq = e11 - mu1^2, sigma12 = e12 - mu1 mu2), to e11 and to e12
         dmaps[c * HW + pix] = 2.f * mu2 * (A2 - A1) * inv + 2.f * mu1 * S * (1.f / B2 - 1.f / B1);
@@ -320,16 +270,7 @@ int make_args(const MrgsLossConfig* cfg, bool has_weight, LossArgs& a)
     a.H = cfg->H; a.W = cfg->W; a.C = cfg->C;
     a.lambda_dssim = cfg->lambda_dssim; a.lambda_normal = cfg->lambda_normal; a.lambda_dist = cfg->lambda_dist;
     a.normal_mode = cfg->lambda_normal > 0.f ? (has_weight ? 1 : 2) : 0;
-    // gaussian(11, 1.5) (loss_utils.py:28-30): exp in double, stored as fp32, divided by their fp32 sum (torch's sum of these 11
-    // values equals the correctly rounded one; tests/golden/reference_loss.npz holds the resulting window)
-    float g[2 * LR + 1];
-    double sum = 0.0;
-    for (int i = 0; i <= 2 * LR; ++i) {
-        const double d = (double)(i - LR);
-        g[i] = (float)exp(-(d * d) / (2.0 * 1.5 * 1.5));
-        sum += (double)g[i];
-    }
-    for (int i = 0; i <= 2 * LR; ++i) a.w[i] = g[i] / (float)sum;
+    ssim_window(a.w);
     return MRGS_OK;
 }
 

@@ -3,7 +3,8 @@ scene/env_gaussian_model.py), with its per-gaussian policy on csrc/mrgs_env_dens
 without a host read, `densify_and_prune` -- clone, split in 2, opacity prune, quantile-of-weights prune with split in 5, top-k visibility
 cap, reset -- classify passes over per-row numbers and ONE emit pass with ONE host read.  Attribute names and activations are the
 reference's, so surfel_tracing._raw_model takes its fast path.  No CPU path and no torch fallback: the tensors must live on the GPU.
-Left out: save_ply / load_ply of the environment set (nothing in the training loop calls them) and env_gaussian_model3.py.
+env_point_cloud.ply is written and read by the module functions `save_ply(model, path)` / `load_ply(model, path)` below (on
+materialrefgs_amd.io); the class itself still has no methods of those names.  Left out: env_gaussian_model3.py.
 Differences from the reference are listed in INTEGRATION.md section 4e."""
 import ctypes
 import math
@@ -82,6 +83,25 @@ def _counts(raw):
     return SimpleNamespace(rows=raw[24], segments=tuple(seg), kept=dict(zip(_SLOTS, seg[:4])), children5=sum(seg[4:]), n_clone=raw[25],
                            n_split=raw[26], n_stage3=raw[27], n_pruned4=raw[28], n_split4=raw[29], n_pruned5=raw[30], q=f32(raw[31]),
                            W0=f32(raw[32]), W1=f32(raw[33]), W4=f32(raw[34]), cut=f32(raw[35]), rows_before_cap=raw[36], capped=bool(raw[37]))
+
+
+def save_ply(model, path):
+    """EnvGaussianModel.save_ply (scene/env_gaussian_model.py:212-229; Scene.save writes env_point_cloud.ply with it) as a function of the
+    model: the class has no method of this name (tests/test_env_model.py holds it to that)."""
+    from . import io
+    io.save_env_ply(path, {"xyz": model._xyz, "features_dc": model._features_dc, "features_rest": model._features_rest, "opacity": model._opacity,
+                           "scaling": model._scaling, "rotation": model._rotation})
+
+
+def load_ply(model, path, device="cuda"):
+    """EnvGaussianModel.load_ply (:236-277) as a function of the model: the parameters on `device` with requires_grad, active_sh_degree =
+    max_sh_degree."""
+    from . import io
+    t = io.load_env_ply(path, model.max_sh_degree, device)
+    for key, attr in (("xyz", "_xyz"), ("features_dc", "_features_dc"), ("features_rest", "_features_rest"), ("opacity", "_opacity"),
+                      ("scaling", "_scaling"), ("rotation", "_rotation")):
+        setattr(model, attr, nn.Parameter(t[key].requires_grad_(True)))
+    model.active_sh_degree = model.max_sh_degree
 
 
 class EnvGaussianModel:

@@ -37,19 +37,24 @@ def _flat(key, t):
     return a.reshape(a.shape[0], -1).contiguous().numpy()
 
 
-def save_ply(path: str, tensors: Dict[str, torch.Tensor], env_map=None, env_map_2=None):
-    """tensors: GaussianModel layout -- xyz [P,3], normal1/2 [P,3], features_dc [P,1,3], features_rest [P,15,3], indirect_dc [P,1,3],
-    indirect_rest [P,15,3], indirect_asg [P,32,5], opacity/refl_strength/metalness/roughness [P,1], ori_color/diffuse_color [P,3],
-    scaling [P,2], rotation [P,4] (raw, pre-activation values as the reference stores them)."""
+def _write_vertex_ply(path: str, names, data):
+    """One `vertex` element of float properties `names`, rows `data` [P, len(names)], binary little-endian: what plyfile writes."""
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-    cols = [_flat(k, tensors[k]) for k, _ in _FIELDS]
-    names = attribute_names({k: tuple(tensors[k].shape) for k, _ in _FIELDS})
-    data = np.ascontiguousarray(np.concatenate(cols, axis=1), dtype="<f4")
-    assert data.shape[1] == len(names)
+    data = np.ascontiguousarray(data, dtype="<f4")
+    assert data.ndim == 2 and data.shape[1] == len(names)
     header = ["ply", "format binary_little_endian 1.0", f"element vertex {data.shape[0]}"] + [f"property float {n}" for n in names] + ["end_header"]
     with open(path, "wb") as f:
         f.write(("\n".join(header) + "\n").encode("ascii"))
         f.write(data.tobytes())
+
+
+def save_ply(path: str, tensors: Dict[str, torch.Tensor], env_map=None, env_map_2=None):
+    """tensors: GaussianModel layout -- xyz [P,3], normal1/2 [P,3], features_dc [P,1,3], features_rest [P,15,3], indirect_dc [P,1,3],
+    indirect_rest [P,15,3], indirect_asg [P,32,5], opacity/refl_strength/metalness/roughness [P,1], ori_color/diffuse_color [P,3],
+    scaling [P,2], rotation [P,4] (raw, pre-activation values as the reference stores them)."""
+    cols = [_flat(k, tensors[k]) for k, _ in _FIELDS]
+    names = attribute_names({k: tuple(tensors[k].shape) for k, _ in _FIELDS})
+    _write_vertex_ply(path, names, np.concatenate(cols, axis=1))
     if env_map is not None:
         torch.save(env_map.state_dict(), path.replace(".ply", "1.map"))
     if env_map_2 is not None:
@@ -253,6 +258,48 @@ def load_ply(path: str, max_sh_degree: int = 3, device="cpu") -> Dict[str, torch
         "indirect_asg": group("ind_asg").reshape(P, 5, -1).transpose(0, 2, 1),          # :788
         "opacity": cols("opacity"), "refl_strength": cols("refl_strength"), "metalness": cols("metalness"), "roughness": cols("roughness"),
         "ori_color": group("ori_color"), "diffuse_color": group("diffuse_color"), "scaling": group("scale"), "rotation": group("rot"),
+    }
+    return {k: torch.tensor(np.ascontiguousarray(v), dtype=torch.float32, device=device) for k, v in out.items()}
+
+
+# ---- the environment set (scene/env_gaussian_model.py:198-277) ------------------------------------------------------------------------
+_ENV_FIELDS = [("features_dc", "f_dc"), ("features_rest", "f_rest"), ("opacity", "opacity"), ("scaling", "scale"), ("rotation", "rot")]
+
+
+def env_attribute_names(shapes: Dict[str, tuple]):
+    """construct_list_of_attributes of EnvGaussianModel (:198-210): x y z nx ny nz f_dc_* f_rest_* opacity scale_* rot_*."""
+    names = ["x", "y", "z", "nx", "ny", "nz"]
+    for key, prefix in _ENV_FIELDS:
+        names += [prefix] if key in _SCALAR else [f"{prefix}_{i}" for i in range(int(np.prod(shapes[key][1:])))]
+    return names
+
+
+def save_env_ply(path: str, tensors: Dict[str, torch.Tensor]):
+    """EnvGaussianModel.save_ply (:212-229).  tensors: xyz [P,3], features_dc [P,1,3], features_rest [P,K,3] (both stored transposed),
+    opacity [P,1], scaling [P,2], rotation [P,4], raw values; the normals are zeros."""
+    xyz = _flat("xyz", tensors["xyz"])
+    cols = [xyz, np.zeros_like(xyz)] + [_flat(k, tensors[k]) for k, _ in _ENV_FIELDS]
+    _write_vertex_ply(path, env_attribute_names({k: tuple(tensors[k].shape) for k, _ in _ENV_FIELDS}), np.concatenate(cols, axis=1))
+
+
+def load_env_ply(path: str, max_sh_degree: int = 3, device="cpu") -> Dict[str, torch.Tensor]:
+    """EnvGaussianModel.load_ply (:236-275): the tensors of save_env_ply; the f_rest count is checked as the reference asserts it (:251)."""
+    names, data = read_ply_vertices(path)
+    col = {n: i for i, n in enumerate(names)}
+
+    def group(prefix):
+        ks = sorted([n for n in names if n.startswith(prefix)], key=lambda x: int(x.split("_")[-1]))
+        return data[:, [col[k] for k in ks]]
+
+    P = data.shape[0]
+    f_rest = group("f_rest_")
+    if f_rest.shape[1] != 3 * (max_sh_degree + 1) ** 2 - 3:
+        raise ValueError(f"{path}: {f_rest.shape[1]} f_rest properties, sh degree {max_sh_degree} needs {3 * (max_sh_degree + 1) ** 2 - 3}")
+    out = {
+        "xyz": data[:, [col["x"], col["y"], col["z"]]],
+        "features_dc": data[:, [col["f_dc_0"], col["f_dc_1"], col["f_dc_2"]]].reshape(P, 3, 1).transpose(0, 2, 1),
+        "features_rest": f_rest.reshape(P, 3, (max_sh_degree + 1) ** 2 - 1).transpose(0, 2, 1),
+        "opacity": data[:, [col["opacity"]]], "scaling": group("scale_"), "rotation": group("rot"),
     }
     return {k: torch.tensor(np.ascontiguousarray(v), dtype=torch.float32, device=device) for k, v in out.items()}
 
