@@ -1088,6 +1088,58 @@ int mrgs_sh_grad_expand_surfel_rows(int32_t P, int32_t D, int32_t V, const float
 size_t mrgs_knn_ws_bytes(int64_t P);
 int mrgs_knn_mean_dist2(const float* points, int64_t P, float* out, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- ball query, furthest point sampling and the 3D max-pooling of the reflection score -------------------------------------------
+ * Replaces pointnet2_ops' ball_query and furthest_point_sample (a CUDA-only extension the reference imports at
+ * utils/ref_score_utils.py:1 and does not carry) and the pooling of ref_scores_max_pooling / ref_scores_max_pooling_wiht_mask
+ * (utils/ref_score_utils.py:21-121).  The definitions restate pointnet2_ops' published kernels and are what is pinned
+ * (tests/pool_statement.py); parity with the CUDA binary is unpinned, its contracted distances may differ in the last bit.
+ *   d(q, k) = (dx dx + dy dy) + dz dz in fp32, un-fused, dx = fl(q.x - p_k.x), ...; r = radius, r2 = fl(r r); k HITS q iff d(q, k) < r2
+ *   (strictly; a comparison with a NaN is false, so a row with a non-finite coordinate never hits and is never hit).
+ *
+ * mrgs_ball_query: idx [B,M,nsample] int32; with h_0 < h_1 < ... the hits of query j of new_xyz [B,M,3] among xyz [B,N,3] in ascending
+ * index order and c = min(#hits, nsample), row j is h_0 .. h_{c-1} followed by h_0 repeated, all zeros without a hit (and with N = 0):
+ * a pure function of the inputs, bit-equal to the fp32 brute force over k = 0 .. N-1.
+ *
+ * mrgs_ball_max_pool: pooled [B,N]; pooled[j] = the maximum of score[k] (the first hit's score, then fmaxf with each further one) over
+ * the row mrgs_ball_query(r, nsample, points, points) would hold for j -- the first nsample hits, not all -- without that row ever
+ * existing.  r = radius, or fl(*radius_dev * radius) when radius_dev (one device float, read by the kernel: no host read) is given.
+ * valid NULL: a row without a hit takes score[0] of its batch, as the zero row does.  valid [B,N] bytes: rows whose byte is 0 are neither
+ * candidates nor queries and keep their own score; the order among the others is their order in the full cloud; a valid row without
+ * a hit keeps its own score.
+ *
+ * mrgs_furthest_point_sample: idx [B,npoint] int32; idx[0] = 0, temp[k] = 1e10; for each further pick every k whose magnitude
+ * (x x + y y) + z z (fp32) is > 1e-3 (compared in double: the published kernel's test, kept) is eligible and takes
+ * temp[k] = fminf(temp[k], d(p_old, p_k)) with p_old the pick before; the pick is the eligible k of largest temp[k], ties to the lowest
+ * index (this library's rule; the CUDA kernel's tie depends on its block size), 0 without an eligible point.  One launch per pick,
+ * each reading the pick before from device memory.  span_out (optional, [B] device floats): |p[idx[0]] - p[idx[1]]|, the square root
+ * of d correctly rounded; 0 when npoint < 2.
+ *
+ * mrgs_depth_points: points [n_views H W, 3]; point v H W + y W + x is ((x - cx) / fx z, (y - cy) / fy z, z) with z = depth[y W + x] of
+ * view v, then (p - T) @ R^T (R row-major): utils/ref_score_utils.py:8-19 with scale = 1 over scene/cameras.py:96-104.  One launch for
+ * all views; `views` is a device array.
+ *
+ * All pointers are device pointers.  ws (mrgs_ball_query_ws_bytes(B, N) bytes -- one size serves the three calls that take it: 16 B N
+ * plus 33 bytes per 64 points -- 16-byte aligned, contents arbitrary) is scratch that may be reused once the call's kernels have run.
+ * Everything is queued on `stream`; nothing is read back to the host and nothing is allocated.  Before any HIP call: MRGS_E_BAD_ARG for
+ * B < 0, B > 65535 (batches are grid.y), N or M outside [0, 2^31), nsample < 1, npoint < 0, n_views outside [0, 65535], H or W < 0,
+ * n_views H W >= 2^31, a null pointer that would be used, a misaligned ws, or N = 0 with a pick to make; MRGS_E_WORKSPACE for ws_bytes
+ * too small.  An empty input (B = 0, M = 0, N = 0 for the pooling, npoint = 0, n_views H W = 0) returns MRGS_OK and launches nothing.
+ * mrgs_ball_query_ws_bytes is 0 outside those ranges. */
+typedef struct MrgsDepthView {
+    const float* depth;      /* device fp32 [H, W] */
+    float R[9];              /* the camera's R (scene/cameras.py:85), row-major */
+    float T[3];
+    float fx, fy, cx, cy;
+} MrgsDepthView;
+size_t mrgs_ball_query_ws_bytes(int64_t B, int64_t N);
+int mrgs_ball_query(float radius, int32_t nsample, const float* xyz, const float* new_xyz, int64_t B, int64_t N, int64_t M, int32_t* idx, void* ws,
+                    size_t ws_bytes, void* stream);
+int mrgs_furthest_point_sample(const float* xyz, int64_t B, int64_t N, int32_t npoint, int32_t* idx, float* span_out, void* ws, size_t ws_bytes,
+                               void* stream);
+int mrgs_depth_points(const MrgsDepthView* views, int32_t n_views, int32_t H, int32_t W, float* points, void* stream);
+int mrgs_ball_max_pool(float radius, const float* radius_dev, int32_t nsample, const float* points, const float* score, const uint8_t* valid, int64_t B,
+                       int64_t N, float* pooled, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- mesh extraction: TSDF fusion, marching tetrahedra, floater removal -----------------------------------------------------
  * Replaces the in-loop mesh step of the training scripts (utils/mesh_utils.py: extract_mesh_bounded :212-253, extract_mesh_unbounded
  * :309-404, post_process_mesh :30-51; utils/mcube_utils.py).  Everything is queued on `stream`; nothing is allocated by the library.

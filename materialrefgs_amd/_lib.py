@@ -252,6 +252,10 @@ class MrgsExportConfig(_Sized):
     _fields_ = [("struct_size", ctypes.c_uint32), ("H", c_int32), ("W", c_int32), ("n_maps", c_int32), ("flags", ctypes.c_uint32)]
 
 
+class MrgsDepthView(ctypes.Structure):
+    _fields_ = [("depth", c_void_p), ("R", c_float * 9), ("T", c_float * 3), ("fx", c_float), ("fy", c_float), ("cx", c_float), ("cy", c_float)]
+
+
 class MrgsKernelTimes(ctypes.Structure):
     _fields_ = [(n, c_float) for n in ("preprocess_ms", "sort_ms", "duplicate_ms", "render_fwd_ms", "render_bwd_ms",
                                        "preprocess_bwd_ms")]
@@ -446,6 +450,12 @@ SYMBOLS = {
     "mrgs_export_ws_bytes": (c_size_t, []),
     "mrgs_export_rgb8": (ctypes.c_int, [ctypes.POINTER(MrgsExportConfig), ctypes.POINTER(MrgsExportMap), c_void_p, c_size_t, c_void_p, c_void_p]),
     "mrgs_eval_jet_table": (ctypes.c_int, [c_void_p]),
+    "mrgs_ball_query_ws_bytes": (c_size_t, [c_int64, c_int64]),
+    "mrgs_ball_query": (ctypes.c_int, [c_float, c_int32, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "mrgs_furthest_point_sample": (ctypes.c_int, [c_void_p, c_int64, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "mrgs_depth_points": (ctypes.c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    "mrgs_ball_max_pool": (ctypes.c_int, [c_float, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_size_t,
+                                          c_void_p]),
 }
 MRGS_ABI_VERSION = 10   # the revision of include/mrgs.h these ctypes declarations were written against
 

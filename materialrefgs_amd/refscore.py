@@ -11,15 +11,30 @@ Differences a caller sees: the rendered maps stay on the device between the rend
 on the host), nothing is written to disk (the reference dumps debug PNGs), and the function's std / coefficient-of-variation / edge
 experiments, none of which reaches its return value, are not built.
 
+`ref_scores_max_pooling` and `ref_scores_max_pooling_wiht_mask` (utils/ref_score_utils.py:21-121) are the reference's step between that
+score and the masks: every pixel of every view is lifted to 3D by its depth, and its score becomes the maximum over the first
+n_samples = 49 points of the whole cloud, in cloud order, inside a ball around it -- pointnet2_ops' ball_query over the cloud against
+itself, then a gather and a max.  Here it is two calls of libmrgs.so (csrc/mrgs_ballquery.hip; contracts at mrgs_depth_points and
+mrgs_ball_max_pool in include/mrgs.h): one launch lifts all views, one fused walk keeps a running maximum per pixel, and the
+[points, 49] index tensor (12.5 GB at 100 views of 800 x 800) never exists.  The values are bit-equal to the float32 brute force of
+that definition on the same points (tests/pool_statement.py); parity with pointnet2_ops' CUDA binary is unpinned.
+The reference's text cannot run as written, which is why `depth_images` is a required keyword here:
+  * it calls the three-argument get_points_from_depth(self, fov_camera, depth) with two arguments (:41, :91);
+  * it passes the score image where the depth belongs (same lines), so no depth source is named at all;
+  * it indexes the (1, N) tensors total_points and ref_score with flat indices (:51, :59, :102, :110);
+  * the masked variant calls `.resshape(-1)` (:90) and indexes `mask_images[mask]` with the mask itself (:92).
+What is built is what those lines evidently mean: depth from the caller, points and scores as flat [N] rows.
+
 `ref_score_mask` -- score > threshold -- is this project's own definition of the boolean map the loss takes: the reference contains no
-code that turns the score into the PNG masks its training script loads.  Parity unpinned.
+code that thresholds the (pooled) score into the PNG masks its training script loads.  Parity unpinned.
 """
 import ctypes
+from collections.abc import Mapping
 
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, ballquery
 from ._cache import Bounded, derived
 from .multiview import _focal
 
@@ -182,10 +197,101 @@ def calc_ref_score(scene, opt, gaussians, dataset, pipe, albeldo_images, mtl_ima
     return out
 
 
+def _per_view(maps, cams, what, fn):
+    """The maps in camera order: by position, as the reference indexes them, or by image_name when a mapping is given."""
+    if isinstance(maps, Mapping):
+        missing = [c.image_name for c in cams if c.image_name not in maps]
+        if missing:
+            raise ValueError(f"{fn}: {what} has no entry for {missing[:3]}")
+        return [maps[c.image_name] for c in cams]
+    maps = list(maps)
+    if len(maps) != len(cams):
+        raise ValueError(f"{fn}: {len(maps)} {what} for {len(cams)} cameras")
+    return maps
+
+
+def _max_pool(fn, ref_score_images, mask_images, viewpoint_cam_lst, scene_extend, radius_ratio, n_samples, backend, calc_depth_points_radius,
+              depth_images):
+    if backend != 'ball query':
+        raise NotImplementedError("Only ball query is supported")
+    if depth_images is None:
+        raise TypeError(f"{fn}() needs the keyword depth_images (one depth map per camera, e.g. the render's surf_depth): the reference "
+                        "lifts the SCORE image where the depth belongs and calls its three-argument get_points_from_depth with two, so "
+                        "it never ran and names no depth source")
+    cams = list(viewpoint_cam_lst)
+    if not cams:
+        return {}
+    n_samples = int(n_samples)
+    if n_samples < 1:
+        raise ValueError(f"{fn}: n_samples must be at least 1, got {n_samples}")
+    H, W = ballquery.image_size(cams)
+    # sizes first, devices second: a wrong shape is reported as such wherever the tensors live
+    named = [(what, ballquery.check_maps(_per_view(maps, cams, what, fn), what, H, W, len(cams), fn))
+             for what, maps in (("ref_score_images", ref_score_images), ("depth_images", depth_images), ("mask_images", mask_images))
+             if maps is not None]
+    scores = ballquery.device_maps(named[0][1], named[0][0], fn)
+    dev = scores[0].device
+    depths = ballquery.device_maps(named[1][1], named[1][0], fn, dev)
+    valid = None
+    if mask_images is not None:
+        for i, m in enumerate(named[2][1]):
+            if not m.is_cuda or m.device != dev:
+                raise RuntimeError(f"{fn}: mask_images[{i}] must be a device tensor on {dev} (libmrgs.so has no CPU path)")
+        valid = torch.cat([(m.reshape(-1) != 0) for m in named[2][1]]).to(torch.uint8)
+    points = ballquery.points_from_depth(cams, depths)
+    score = torch.cat([s.reshape(-1) for s in scores])
+    N = score.numel()
+    radius_dev = None
+    if calc_depth_points_radius:
+        # |p[f0] - p[f1]| stays on the device; the kernel multiplies it by the ratio
+        _idx, radius_dev = ballquery.furthest_point_sample(points.unsqueeze(0), 2, return_span=True)
+        radius = float(radius_ratio)
+    elif torch.is_tensor(scene_extend) and scene_extend.is_cuda:
+        radius_dev, radius = _lib.f32c(scene_extend).reshape(-1)[:1].to(dev), float(radius_ratio)
+    else:
+        radius = float(scene_extend) * float(radius_ratio)
+    L = _lib.lib()
+    pooled = torch.empty(N, dtype=torch.float32, device=dev)
+    ws = torch.empty(int(L.mrgs_ball_query_ws_bytes(1, N)), dtype=torch.uint8, device=dev)
+    with _lib.guard(dev):
+        _lib.check(L.mrgs_ball_max_pool(radius, _p(radius_dev), n_samples, _p(points), _p(score), _p(valid), 1, N, _p(pooled), _p(ws), ws.numel(),
+                                        _lib.stream_ptr(dev)))
+    pooled = pooled.reshape(len(cams), H, W)
+    return {cam.image_name: pooled[i] for i, cam in enumerate(cams)}
+
+
+@torch.no_grad()
+def ref_scores_max_pooling(ref_score_images, viewpoint_cam_lst, scene_extend, radius_ratio=0.1, n_samples=7 * 7, backend='ball query',
+                           calc_depth_points_radius=False, *, depth_images=None):
+    """utils/ref_score_utils.py:21-67: {image_name: [H,W] float32 on the device}, every pixel's score replaced by the maximum over the
+    first `n_samples` points (in cloud order: view by view, row by row) of all views' depth points within the radius of its own.
+    ref_score_images and depth_images: one map per camera ([H*W], [H,W] or [1,H,W]), by position in viewpoint_cam_lst or as a mapping
+    by image_name (what calc_ref_score returns).  The radius is scene_extend * radius_ratio, or with calc_depth_points_radius the
+    distance between the two points furthest_point_sample(points, 2) picks times radius_ratio, which never leaves the device.  A pixel
+    whose ball is empty (radius 0, a non-finite depth) takes the score of point 0, as ball_query's zero row makes the reference do.
+    One fused call: no [points, n_samples] index tensor exists.  No host read when the cameras' R and T are host tensors."""
+    return _max_pool("ref_scores_max_pooling", ref_score_images, None, viewpoint_cam_lst, scene_extend, radius_ratio, n_samples, backend,
+                     calc_depth_points_radius, depth_images)
+
+
+@torch.no_grad()
+def ref_scores_max_pooling_wiht_mask(ref_score_images, mask_images, viewpoint_cam_lst, scene_extend, radius_ratio=0.1, n_samples=7 * 7,
+                                     backend='ball query', calc_depth_points_radius=False, *, depth_images=None):
+    """utils/ref_score_utils.py:69-121 (the reference's spelling): as ref_scores_max_pooling over the pixels whose mask is nonzero only.
+    Masked-out pixels are neither candidates nor queries and keep their own score; the others keep their order in the full cloud, so
+    nothing is compacted; a masked-in pixel with an empty ball keeps its own score.  mask_images: by position or by image_name, as the
+    other maps.  With calc_depth_points_radius the two points are sampled from the full cloud."""
+    if mask_images is None:
+        raise TypeError("ref_scores_max_pooling_wiht_mask: mask_images is None (use ref_scores_max_pooling)")
+    return _max_pool("ref_scores_max_pooling_wiht_mask", ref_score_images, mask_images, viewpoint_cam_lst, scene_extend, radius_ratio, n_samples,
+                     backend, calc_depth_points_radius, depth_images)
+
+
 def ref_score_mask(score, threshold, fg_mask=None, *, shape=None):
     """[1,H,W] bool for `priors.ref_score_loss`: score > threshold, and inside `fg_mask` (H*W elements, nonzero = foreground) where one
     is given.  `score` is [H,W] or [1,H,W]; a flat [H*W] score (what calc_ref_score returns) needs shape=(H, W).  This compare is the
-    project's own definition -- the reference has no code that produces its masks from the score: parity unpinned."""
+    project's own definition -- the reference has no code that produces its masks from the score: parity unpinned.  The reference's step
+    between the score and such a compare, the 3D max-pooling across views, is ref_scores_max_pooling above."""
     if shape is None:
         if score.dim() < 2:
             raise ValueError("ref_score_mask: a flat score needs shape=(H, W)")
