@@ -1499,6 +1499,66 @@ size_t mrgs_export_ws_bytes(void);
 int mrgs_export_rgb8(const MrgsExportConfig* cfg, const MrgsExportMap* maps, void* ws, size_t ws_bytes, uint8_t* out, void* stream);
 int mrgs_eval_jet_table(uint8_t* table768 /*host, [256][3]*/);
 
+/* ---- the dataset side of a view: 8-bit planes on the device (scene/dataset_readers.py, utils/camera_utils.py, utils/general_utils.py) ----
+ * mrgs_image_resize_u8: `pil_image.resize((out_w, out_h))` of PILtoTorch (general_utils.py:21-27), i.e. Pillow's BICUBIC on 8-bit
+ * channels, bit for bit.  src: `channels` (1..4) byte channels of an in_h x in_w image, element (c, y, x) at byte c stride_c + y stride_y +
+ * x stride_x (a pixel-interleaved [H,W,C] image is stride (1, W C, C), planes are (H W, W, 1)); dst: planes [channels][out_h][out_w].
+ * Channels are independent (RGBA is four L images, no premultiplication).  Per resized axis the caller passes the coefficient table Pillow
+ * computes, as DEVICE arrays: bounds [out][2] int32 = (first source index, tap count n), kk [out][ksize] int32 = the normalised Keys
+ * (a = -0.5) weights times 2^22, rounded half away from zero.  A pass writes clip8((2^21 + sum_{t<n} kk[t] * pixel[first + t]) >> 22),
+ * arithmetic shift; the horizontal pass runs first over every source row into an 8-bit intermediate, then the vertical pass.  An axis whose
+ * size does not change has no pass and needs no table (NULL); equal sizes are a copy into planes.  The tables are READ AS GIVEN: first >= 0
+ * and first + n <= the source extent are the caller's contract (materialrefgs_amd/viewstore.py: resize_table builds them).
+ * ws: mrgs_image_resize_ws_bytes bytes (channels in_h out_w when both axes change, else 0).  At most two launches, no host read.
+ * MRGS_E_BAD_ARG before any HIP call: wrong struct_size, flags != 0, channels outside 1..4, a size outside 1..2^24, a stride_y / stride_x
+ * <= 0 or stride_c < 0, NULL src / dst, a missing table or ksize < 1 for an axis that changes, NULL ws when one is needed;
+ * MRGS_E_WORKSPACE for a short ws. */
+typedef struct MrgsResizeConfig {
+    uint32_t struct_size;           /* = sizeof(MrgsResizeConfig) */
+    int32_t channels, in_h, in_w, out_h, out_w;
+    int32_t ksize_x, ksize_y;       /* row length of kk_x / kk_y */
+    uint32_t flags;                 /* 0 */
+    int64_t stride_c, stride_y, stride_x;
+} MrgsResizeConfig;
+size_t mrgs_image_resize_ws_bytes(int32_t channels, int32_t in_h, int32_t in_w, int32_t out_h, int32_t out_w);
+int mrgs_image_resize_u8(const MrgsResizeConfig* cfg, const uint8_t* src, const int32_t* bounds_x, const int32_t* kk_x,
+                         const int32_t* bounds_y, const int32_t* kk_y, void* ws, size_t ws_bytes, uint8_t* dst, void* stream);
+/* mrgs_image_composite_u8: readCamerasFromTransforms' compositing onto a constant background (dataset_readers.py:276-282).  rgba
+ * [n_pixels][4] bytes (4-byte aligned), table [256][256] device bytes indexed [colour][alpha] -- the host evaluates the reference's float64
+ * expression and its wrapping cast once per (colour, alpha) pair and background -- dst planes [3][n_pixels].  One launch.
+ * MRGS_E_BAD_ARG: n_pixels < 0 or >= 2^36, a NULL pointer or a misaligned rgba with n_pixels > 0; n_pixels = 0 returns MRGS_OK. */
+int mrgs_image_composite_u8(int64_t n_pixels, const uint8_t* rgba, const uint8_t* table, uint8_t* dst, void* stream);
+/* mrgs_view_decode: one launch turns the byte planes of a view into the fp32 tensors the losses read.  Every output may be NULL; an
+ * output that is not NULL needs its input.
+ *   gt [3,H,W]         = rgb [3,H,W] / 255.0f, IEEE division: torch's `uint8_tensor / 255.0`
+ *   alpha_out [1,H,W]  = alpha [H,W] / 255.0f
+ *   grey [1,Hg,Wg]     = (0.299f r + 0.587f g) + 0.114f b on r, g, b = grey_rgb [3,Hg,Wg] / 255.0f, every product and sum rounded on its
+ *                        own (utils/camera_utils.py:37); grey_rgb is rgb itself when the grey image has the image's size
+ *   normal_out [H W,3] = normal_table[normal [H,W,3]]; the table (256 device floats) is float32((n / 255.) * 2. - 1) from float64
+ *   mask_out [H W,1]   = mask [H,W] > 128 ? 1 : 0        (train_refnerf.py:124)
+ *   score_out [1,H,W]  = score [H,W] > 128 as bool bytes (train_refnerf.py:193)
+ * MRGS_E_BAD_ARG before any HIP call: wrong struct_size, flags != 0, H or W outside 1..2^24 (Hg, Wg with grey), no output at all, an output
+ * without its input, a float pointer that is not 4-byte aligned. */
+typedef struct MrgsViewDecode {
+    uint64_t struct_size;           /* = sizeof(MrgsViewDecode) */
+    int32_t H, W, Hg, Wg;
+    const uint8_t* rgb;
+    const uint8_t* alpha;
+    const uint8_t* grey_rgb;
+    const uint8_t* normal;
+    const uint8_t* mask;
+    const uint8_t* score;
+    const float* normal_table;
+    float* gt;
+    float* alpha_out;
+    float* grey;
+    float* normal_out;
+    float* mask_out;
+    uint8_t* score_out;
+    uint64_t flags;                 /* 0 */
+} MrgsViewDecode;
+int mrgs_view_decode(const MrgsViewDecode* view, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

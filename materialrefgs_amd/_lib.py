@@ -252,6 +252,17 @@ class MrgsExportConfig(_Sized):
     _fields_ = [("struct_size", ctypes.c_uint32), ("H", c_int32), ("W", c_int32), ("n_maps", c_int32), ("flags", ctypes.c_uint32)]
 
 
+class MrgsResizeConfig(_Sized):
+    _fields_ = [("struct_size", ctypes.c_uint32)] + [(n, c_int32) for n in ("channels", "in_h", "in_w", "out_h", "out_w", "ksize_x", "ksize_y")] + \
+               [("flags", ctypes.c_uint32), ("stride_c", c_int64), ("stride_y", c_int64), ("stride_x", c_int64)]
+
+
+class MrgsViewDecode(_Sized):
+    _fields_ = [("struct_size", ctypes.c_uint64)] + [(n, c_int32) for n in ("H", "W", "Hg", "Wg")] + \
+               [(n, c_void_p) for n in ("rgb", "alpha", "grey_rgb", "normal", "mask", "score", "normal_table", "gt", "alpha_out", "grey",
+                                        "normal_out", "mask_out", "score_out")] + [("flags", ctypes.c_uint64)]
+
+
 class MrgsDepthView(ctypes.Structure):
     _fields_ = [("depth", c_void_p), ("R", c_float * 9), ("T", c_float * 3), ("fx", c_float), ("fy", c_float), ("cx", c_float), ("cy", c_float)]
 
@@ -456,6 +467,10 @@ SYMBOLS = {
     "mrgs_depth_points": (ctypes.c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
     "mrgs_ball_max_pool": (ctypes.c_int, [c_float, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_size_t,
                                           c_void_p]),
+    "mrgs_image_resize_ws_bytes": (c_size_t, [c_int32] * 5),
+    "mrgs_image_resize_u8": (ctypes.c_int, [ctypes.POINTER(MrgsResizeConfig)] + [c_void_p] * 6 + [c_size_t, c_void_p, c_void_p]),
+    "mrgs_image_composite_u8": (ctypes.c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mrgs_view_decode": (ctypes.c_int, [ctypes.POINTER(MrgsViewDecode), c_void_p]),
 }
 MRGS_ABI_VERSION = 10   # the revision of include/mrgs.h these ctypes declarations were written against
 

@@ -36,6 +36,30 @@ def get_projection_matrix(znear, zfar, fovX, fovY):
     return torch.tensor(rows, dtype=torch.float32)
 
 
+def get_projection_matrix_correct(znear, zfar, H, W, K):
+    """The perspective matrix of a pinhole with intrinsics K [3,3] whose principal point need not be the image centre
+    (graphics_utils.py:74-92).  The frustum extents are host arithmetic in K's precision; each entry is cast once on assignment."""
+    top = (K[1, 2]) / K[1, 1] * znear
+    bottom = -(H - K[1, 2]) / K[1, 1] * znear
+    right = (K[0, 2]) / K[0, 0] * znear
+    left = -(W - K[0, 2]) / K[0, 0] * znear
+    P = torch.zeros(4, 4)
+    z_sign = 1.0
+    P[0, 0] = 2.0 * znear / (right - left)
+    P[1, 1] = 2.0 * znear / (top - bottom)
+    P[0, 2] = (right + left) / (right - left)
+    P[1, 2] = (top + bottom) / (top - bottom)
+    P[3, 2] = z_sign
+    P[2, 2] = z_sign * zfar / (zfar - znear)
+    P[2, 3] = -(zfar * znear) / (zfar - znear)
+    return P
+
+
+def focal2fov(focal, pixels):
+    """graphics_utils.py:98-99"""
+    return 2 * math.atan(pixels / (2 * focal))
+
+
 def fov2focal(fov, pixels):
     """Focal length in pixels of a pinhole with field of view `fov` across `pixels` (graphics_utils.py:73-74)."""
     return 0.5 * pixels / math.tan(0.5 * fov)

@@ -4,7 +4,7 @@ torch.save, :520-527).  Plain host I/O in numpy -- the reference goes through th
 layout: ASCII header, one `vertex` element, every property `float` (f4), little-endian rows in the attribute order of
 `construct_list_of_attributes` (:462-487)."""
 import os
-from typing import Dict
+from typing import Dict, NamedTuple
 
 import numpy as np
 import torch
@@ -310,3 +310,187 @@ def load_env_maps(path: str, env_map=None, env_map_2=None):
         p = path.replace(".ply", suffix)
         if env is not None and os.path.exists(p):
             env.load_state_dict(torch.load(p, map_location="cpu"))
+
+
+# ---- the input point cloud (scene/dataset_readers.py:168-197) ------------------------------------------------------------------------------
+class BasicPointCloud(NamedTuple):
+    """utils/graphics_utils.py:17-20"""
+    points: np.ndarray
+    colors: np.ndarray
+    normals: np.ndarray
+
+
+_PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "<i2", "int16": "<i2", "ushort": "<u2", "uint16": "<u2",
+              "int": "<i4", "int32": "<i4", "uint": "<u4", "uint32": "<u4", "float": "<f4", "float32": "<f4", "double": "<f8", "float64": "<f8"}
+_POINT_DTYPE = [("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1")]
+_POINT_PLY_NAMES = {"<f4": "float", "u1": "uchar"}
+
+
+def storePly(path, xyz, rgb):
+    """storePly (:182-197): x y z nx ny nz as float, red green blue as uchar, the normals zero, binary little endian -- the header and the
+    rows `plyfile` writes for that structured array.  Values are cast as its element assignment casts them (colours truncate)."""
+    xyz, rgb = np.asarray(xyz), np.asarray(rgb)
+    if xyz.ndim != 2 or xyz.shape[1] != 3 or rgb.shape != xyz.shape:
+        raise ValueError(f"materialrefgs_amd.io: storePly takes xyz and rgb of shape [N,3], got {xyz.shape} and {rgb.shape}")
+    elements = np.zeros(xyz.shape[0], dtype=_POINT_DTYPE)
+    for k, n in enumerate("xyz"):
+        elements[n] = xyz[:, k]
+    for k, n in enumerate(("red", "green", "blue")):
+        elements[n] = np.asarray(rgb[:, k], dtype=np.float64).astype(np.int64).astype(np.uint8) if rgb.dtype.kind == "f" else rgb[:, k]
+    header = ["ply", "format binary_little_endian 1.0", f"element vertex {xyz.shape[0]}"] + \
+             [f"property {_POINT_PLY_NAMES[t]} {n}" for n, t in _POINT_DTYPE] + ["end_header"]
+    with open(path, "wb") as f:
+        f.write(("\n".join(header) + "\n").encode("ascii"))
+        f.write(elements.tobytes())
+
+
+def read_ply_points(path):
+    """The vertex element of a binary little-endian PLY as a structured array, whatever scalar types its properties have."""
+    with open(path, "rb") as f:
+        if f.readline().strip() != b"ply":
+            raise ValueError("not a PLY file")
+        fmt, count, fields, element = None, None, [], None
+        while True:
+            line = f.readline()
+            if not line:
+                raise ValueError("PLY header not terminated")
+            tok = line.decode("ascii").split()
+            if not tok or tok[0] == "comment":
+                continue
+            if tok[0] == "format":
+                fmt = tok[1]
+            elif tok[0] == "element":
+                element = tok[1]
+                if element == "vertex":
+                    count = int(tok[2])
+                elif count is None:
+                    raise ValueError("the vertex element must come first")
+            elif tok[0] == "property" and element == "vertex":
+                if tok[1] not in _PLY_TYPES:
+                    raise ValueError(f"unsupported vertex property type {tok[1]}")
+                fields.append((tok[2], _PLY_TYPES[tok[1]]))
+            elif tok[0] == "end_header":
+                break
+        if fmt != "binary_little_endian":
+            raise ValueError(f"unsupported PLY format {fmt}")
+        dtype = np.dtype(fields)
+        data = np.frombuffer(f.read(count * dtype.itemsize), dtype=dtype)
+        if len(data) != count:
+            raise ValueError("PLY file is shorter than its header says")
+    return data
+
+
+def fetchPly(path):
+    """fetchPly (:168-180): positions as stored, colours / 255.0, normals; a file without colours or normals gets the reference's random
+    ones (numpy's global generator, colours first)."""
+    vertices = read_ply_points(path)
+    positions = np.vstack([vertices['x'], vertices['y'], vertices['z']]).T
+    try:
+        colors = np.vstack([vertices['red'], vertices['green'], vertices['blue']]).T / 255.0
+        normals = np.vstack([vertices['nx'], vertices['ny'], vertices['nz']]).T
+    except ValueError:                                   # "no field of name ..."
+        print('Load Ply color and normals failed, random init')
+        colors = np.random.rand(*positions.shape) / 255.0
+        normals = np.random.rand(*positions.shape)
+        normals = normals / np.linalg.norm(normals, axis=-1, keepdims=True)
+    return BasicPointCloud(points=positions, colors=colors, normals=normals)
+
+
+# ---- PNG decoding: the counterpart of evaluate.write_png ------------------------------------------------------------------------------------
+_PNG_CHANNELS = {0: 1, 2: 3, 4: 2, 6: 4}
+
+
+def _paeth_row(cur, prev, bpp):
+    out = bytearray(cur)
+    for i in range(len(out)):
+        a = out[i - bpp] if i >= bpp else 0
+        b = prev[i]
+        c = prev[i - bpp] if i >= bpp else 0
+        p = a + b - c
+        pa, pb, pc = abs(p - a), abs(p - b), abs(p - c)
+        out[i] = (out[i] + (a if pa <= pb and pa <= pc else (b if pb <= pc else c))) & 255
+    return out
+
+
+def _average_row(cur, prev, bpp):
+    out = bytearray(cur)
+    for i in range(len(out)):
+        out[i] = (out[i] + (((out[i - bpp] if i >= bpp else 0) + prev[i]) >> 1)) & 255
+    return out
+
+
+def read_png(path):
+    """uint8 [H,W] (grey) or [H,W,2|3|4] (grey+alpha, RGB, RGBA) of an 8-bit non-interlaced PNG, all five filter types, on the standard
+    library's zlib.  Palette, 16-bit and interlaced files raise ValueError.  Checksums are verified."""
+    import struct
+    import zlib
+    raw = open(path, "rb").read()
+    if raw[:8] != b"\x89PNG\r\n\x1a\n":
+        raise ValueError(f"{path}: not a PNG file")
+    at, head, idat = 8, None, []
+    while at + 12 <= len(raw):
+        n, tag = struct.unpack(">I4s", raw[at:at + 8])
+        data = raw[at + 8:at + 8 + n]
+        if len(data) != n or struct.unpack(">I", raw[at + 8 + n:at + 12 + n])[0] != zlib.crc32(tag + data) & 0xFFFFFFFF:
+            raise ValueError(f"{path}: damaged {tag!r} chunk")
+        if tag == b"IHDR":
+            head = struct.unpack(">IIBBBBB", data)
+        elif tag == b"IDAT":
+            idat.append(data)
+        elif tag == b"IEND":
+            break
+        at += 12 + n
+    if head is None:
+        raise ValueError(f"{path}: no IHDR chunk")
+    W, H, depth, colour, comp, filt, interlace = head
+    if colour == 3:
+        raise ValueError(f"{path}: palette PNG files are not read (convert to RGB)")
+    if depth != 8 or colour not in _PNG_CHANNELS:
+        raise ValueError(f"{path}: only 8-bit grey / grey+alpha / RGB / RGBA PNG files are read, got bit depth {depth}, colour type {colour}")
+    if interlace != 0:
+        raise ValueError(f"{path}: interlaced PNG files are not read")
+    if comp != 0 or filt != 0 or W < 1 or H < 1:
+        raise ValueError(f"{path}: malformed IHDR")
+    bpp = _PNG_CHANNELS[colour]
+    stride = W * bpp
+    data = zlib.decompress(b"".join(idat))
+    if len(data) != H * (1 + stride):
+        raise ValueError(f"{path}: {len(data)} bytes of image data, expected {H * (1 + stride)}")
+    rows = np.frombuffer(data, dtype=np.uint8).reshape(H, 1 + stride)
+    out = np.empty((H, stride), dtype=np.uint8)
+    prev = np.zeros(stride, dtype=np.uint8)
+    for y in range(H):
+        kind, cur = int(rows[y, 0]), rows[y, 1:]
+        if kind == 0:
+            out[y] = cur
+        elif kind == 1:                                   # Sub: a running sum per channel, modulo 256
+            out[y] = np.cumsum(cur.reshape(W, bpp), axis=0, dtype=np.uint8).reshape(stride)
+        elif kind == 2:                                   # Up
+            out[y] = cur + prev
+        elif kind == 3:
+            out[y] = np.frombuffer(bytes(_average_row(cur.tobytes(), prev.tobytes(), bpp)), dtype=np.uint8)
+        elif kind == 4:
+            out[y] = np.frombuffer(bytes(_paeth_row(cur.tobytes(), prev.tobytes(), bpp)), dtype=np.uint8)
+        else:
+            raise ValueError(f"{path}: unknown filter type {kind} in row {y}")
+        prev = out[y]
+    return out.reshape(H, W) if bpp == 1 else out.reshape(H, W, bpp)
+
+
+def read_image(path):
+    """(uint8 array [H,W] or [H,W,C], mode "L" / "LA" / "RGB" / "RGBA") of an image file: Pillow's decode when Pillow imports (palette and
+    other modes converted as `Image.convert` does: P with transparency and anything with alpha to RGBA, the rest to RGB), otherwise
+    read_png for PNG files.  Other formats without Pillow raise."""
+    try:
+        from PIL import Image
+    except ImportError:
+        Image = None
+    if Image is not None:
+        with Image.open(path) as im:
+            if im.mode not in ("L", "LA", "RGB", "RGBA"):
+                im = im.convert("RGBA" if (im.mode in ("PA", "RGBa", "La") or "transparency" in im.info) else "RGB")
+            return np.array(im), im.mode
+    if not str(path).lower().endswith(".png"):
+        raise RuntimeError(f"{path}: only PNG files can be decoded without Pillow (JPEG and other formats need `pip install pillow`)")
+    a = read_png(path)
+    return a, {1: "L", 2: "LA", 3: "RGB", 4: "RGBA"}[1 if a.ndim == 2 else a.shape[2]]
