@@ -1,7 +1,24 @@
-"""Mesh ray queries: host-built hierarchy (CPU checks) and GPU traversal vs the brute-force oracle."""
+"""Mesh ray queries: host-built hierarchy (CPU checks) and GPU traversal vs the brute-force oracle.
+
+The bar is EXACT, for the closest-hit query (depth and position bit for bit) and for the fused visibility (every pixel, none left
+out), for three reasons:
+  * csrc/mrgs_bvh.hip is compiled with -ffp-contract=off: no multiply-add is fused, every float32 operation is the one written;
+  * its sqrtf and / are the correctly rounded ones, so numpy float32 reproduces each intermediate (oracle/trace_oracle.py for the
+    triangle test, tests/visibility_statement.py for the mirror-ray set-up);
+  * the hierarchy only prunes, and conservatively (padded boxes, widened slab test): the answer is the brute-force minimum over all
+    triangles, whatever the tree looks like.
+An allowance of "a few silhouette pixels" belongs only where the other side builds its rays with different arithmetic (the torch
+sequence kept in test_fused_visibility_matches_traced_mirror_rays, the float64 checkers of tests/test_render_e2e.py).
+
+The deepest supported walk (test_trace_deepest_supported_walk: 4**10 + 1 triangles, every box entered by each of 64 rays) was measured
+on an MI355X on 2026-10-21: 0.50 s for the first launch, 0.43 s for the second.
+"""
 import ctypes
+import functools
 import os
+import re
 import sys
+import time
 
 import numpy as np
 import pytest
@@ -10,9 +27,20 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from oracle import trace_oracle  # noqa: E402
+import visibility_statement as vs  # noqa: E402
 
 
 from materialrefgs_amd.synthetic import sphere_mesh  # noqa: E402
+
+
+def _constant(name):
+    with open(os.path.join(ROOT, "materialrefgs_amd", "csrc", "mrgs_bvh.hip")) as f:
+        return int(re.search(rf"constexpr int {name} = (\d+);", f.read()).group(1))
+
+
+BVH_LEAF, BVH_STACK = _constant("BVH_LEAF"), _constant("BVH_STACK")
+BVH_EMPTY = 0x7FFFFFFF
+BVH_LEVELS = (BVH_STACK - 1) // 3                  # inner levels the LDS stack has room for: three pushes per level
 
 
 def scene(seed=0, n_lat=16, n_lon=24):
@@ -144,13 +172,168 @@ def test_trace_oracle_known_answers():
     np.testing.assert_array_equal(pos[1], [0.25, 0.25, 8])               # a miss still advances by MAX_DIST (bvh.cu:706-708)
 
 
+def _inner_levels(codes):
+    """Number of inner levels of a built hierarchy (the root is level 1), walked level by level from the child codes."""
+    frontier, levels = np.zeros(1, dtype=np.int64), 0
+    while frontier.size:
+        levels += 1
+        ch = codes[frontier].reshape(-1)
+        frontier = ch[(ch >= 0) & (ch != BVH_EMPTY)].astype(np.int64)
+    return levels
+
+
+def test_bvh_build_stack_bound_both_sides():
+    """The LDS traversal stack holds BVH_STACK entries and a walk pushes up to three per inner level, so the build accepts
+    3 * levels + 1 <= BVH_STACK.  With BVH_LEAF triangles per leaf and four children per node the largest accepted mesh has
+    BVH_LEAF ** (BVH_LEVELS + 1) triangles (4 194 304 with the shipped constants, measured), one more is MRGS_E_UNSUPPORTED.
+    The triangles are index triples into six vertices: all that counts here is their number."""
+    assert BVH_LEAF == 4                                                 # the boundary below is that of a 4-ary tree with 4-triangle leaves
+    L = _lib()
+    lib = L.lib()
+    n_max = BVH_LEAF ** (BVH_LEVELS + 1)
+    v = np.array([[0, 0, 0], [1, 0, 0], [0, 1, 0], [1, 1, 0.5], [0.5, 0.2, 1], [0.1, 0.9, 0.3]], dtype=np.float32)
+    rng = np.random.default_rng(0)
+    t = np.ascontiguousarray(np.argsort(rng.random((n_max + 1, 6)), axis=1)[:, :3].astype(np.int32))   # three distinct vertices each
+    nbytes = lib.mrgs_bvh_bytes(n_max + 1)
+    blob = np.zeros(nbytes, dtype=np.uint8)
+
+    def build(n):
+        return lib.mrgs_bvh_build(ctypes.c_void_p(v.ctypes.data), len(v), ctypes.c_void_p(t.ctypes.data), n,
+                                  ctypes.c_void_p(blob.ctypes.data), nbytes)
+    assert build(n_max + 1) == L.MRGS_E_UNSUPPORTED
+    assert build(n_max) == L.MRGS_OK
+    _, codes, _, perm = _views(blob, n_max)
+    assert _inner_levels(codes) == BVH_LEVELS                            # the deepest inner node sits exactly at the bound
+    assert np.array_equal(np.sort(perm), np.arange(n_max, dtype=np.int32))
+
+
+# ---------------------------------------------------------------- CPU: the visibility statement and the inputs of the GPU cases
+VIS_SIZES = ((120, 160), (7, 31), (9, 33), (41, 67))                    # full tiles; a partial tile; one pixel past a tile each way; ragged
+
+
+@functools.lru_cache(maxsize=None)
+def _vis_mesh():
+    return scene(3, 24, 36)
+
+
+def _vis_camera(H, W):
+    from materialrefgs_amd.synthetic import orbit_camera
+    cam = orbit_camera(2, H, W)
+    K = np.asarray(cam.HWK[2], dtype=np.float32)
+    return cam, K, cam.R.float().numpy(), cam.T.float().numpy()
+
+
+@functools.lru_cache(maxsize=None)
+def _vis_case(H, W):
+    """Inputs of one visibility case, numpy float32 on the CPU, and the statement's answer for them: (normal [H,W,3], alpha [H,W],
+    surf_depth [H,W], statement [H,W], blocked share of the traced pixels).  The surface is the first hit of the pixel rays against the
+    mesh itself (brute force), the depth just in front of it, the normal the face normal plus noise, alpha 0 on a fifth.  On top of
+    that five groups of pixels, spread over the image by a multiplicative hash of the pixel index: negative alpha; a zero normal (the
+    mirror direction degenerates to the view ray); surf_depth 0 (origin at the camera); a grazing normal, n . w = 1e-4; a surface point
+    behind the camera-facing mesh (depth x 1.05)."""
+    v, t = _vis_mesh()
+    _, K, R, T = _vis_camera(H, W)
+    Kinv = vs.kinv_f32(K)
+    ro, c = vs.camera_rays(H, W, Kinv, R, T)
+    _, nrm, t_hit, _ = trace_oracle.trace(v, t, np.broadcast_to(ro, (H * W, 3)), c.reshape(-1, 3))      # t runs along the un-normalised ray
+    rng = np.random.default_rng(11 + H * W)
+    hit = t_hit < 10
+    sd = (np.where(hit, t_hit, np.float32(3.0)) * np.float32(0.999)).astype(np.float32)
+    rnd = rng.standard_normal((H * W, 3)).astype(np.float32)
+    n = np.where(hit[:, None], nrm, rnd / np.linalg.norm(rnd, axis=1, keepdims=True))
+    n = n + np.float32(0.2) * rng.standard_normal((H * W, 3)).astype(np.float32)
+    n = (n / np.linalg.norm(n, axis=1, keepdims=True)).astype(np.float32)
+    alpha = ((rng.random(H * W) > 0.2) * rng.random(H * W)).astype(np.float32)
+    group = (np.arange(H * W) * 7919) % 13
+    alpha[group == 0] = -0.5
+    alpha[(group >= 1) & (group <= 4) & (alpha <= 0)] = 0.5             # the groups below are traced
+    n[group == 1] = 0.0
+    sd[group == 2] = 0.0
+    w = -c.reshape(-1, 3) / np.linalg.norm(c.reshape(-1, 3), axis=1, keepdims=True)
+    side = np.cross(w, np.array([0.3, -0.5, 0.8], dtype=np.float32))
+    graze = side / np.linalg.norm(side, axis=1, keepdims=True) + np.float32(1e-4) * w
+    n[group == 3] = graze[group == 3].astype(np.float32)
+    sd[group == 4] = (sd[group == 4] * np.float32(1.05)).astype(np.float32)
+    normal, alpha, sd = n.reshape(H, W, 3).astype(np.float32), alpha.reshape(H, W), sd.reshape(H, W)
+    stmt = vs.visibility(v, t, H, W, Kinv, R, T, normal, alpha, sd)
+    traced = alpha > 0
+    assert (alpha == 0).any() and (alpha < 0).any() and bool((stmt[~traced] == 1).all())
+    blocked = float((stmt[traced] == 0).mean())
+    for a in (normal, alpha, sd, stmt):
+        a.setflags(write=False)
+    return normal, alpha, sd, stmt, blocked
+
+
+@functools.lru_cache(maxsize=None)
+def _vis_case_one_pixel(want_blocked):
+    """The 1 x 1 image: its single mirror ray starts 3 units along the pixel ray; the normal is the first of a fixed random sequence
+    for which the statement reports the wanted outcome."""
+    v, t = _vis_mesh()
+    _, K, R, T = _vis_camera(1, 1)
+    rng = np.random.default_rng(5)
+    for _ in range(64):
+        n = rng.standard_normal(3).astype(np.float32)
+        normal = (n / np.linalg.norm(n)).astype(np.float32).reshape(1, 1, 3)
+        alpha, sd = np.full((1, 1), 0.7, dtype=np.float32), np.full((1, 1), 3.0, dtype=np.float32)
+        stmt = vs.visibility(v, t, 1, 1, vs.kinv_f32(K), R, T, normal, alpha, sd)
+        if bool(stmt[0, 0] == 0) == want_blocked:
+            return normal, alpha, sd, stmt, float(stmt[0, 0] == 0)
+    raise AssertionError("no normal with the wanted outcome")
+
+
+def test_visibility_cases_exercise_both_outcomes():
+    """What the GPU cases assume of their inputs, checked without a GPU: both outcomes at every size, and the special groups present."""
+    for H, W in VIS_SIZES[1:]:
+        normal, alpha, sd, stmt, blocked = _vis_case(H, W)
+        assert 0.02 < blocked < 0.98, (H, W, blocked)
+        assert (sd == 0).any() and (np.abs(normal).sum(-1) == 0).any()
+    assert _vis_case_one_pixel(True)[3][0, 0] == 0 and _vis_case_one_pixel(False)[3][0, 0] == 1
+
+
+def test_visibility_statement_is_the_reference_sequence_up_to_rounding():
+    """tests/visibility_statement.py (the kernel's float32 operations) against the reference's sequence (utils/refl_utils.py:379-391)
+    in float64 on the 120 x 160 case: directions within 1e-6, origins within 1e-6 of the largest coordinate, and every pixel whose
+    visibility differs is a near-tie in float64 -- for each triangle that one side accepts and the other does not, one of the
+    quantities the triangle test compares with a threshold (u, v, 1 - u - v, dn, t - 10) lies within 1e-4 of it."""
+    H, W = VIS_SIZES[0]
+    v, t = _vis_mesh()
+    _, K, R, T = _vis_camera(H, W)
+    normal, alpha, sd, stmt, blocked = _vis_case(H, W)
+    assert 0.02 < blocked < 0.98, blocked
+    o32, d32, traced = vs.mirror_rays(H, W, vs.kinv_f32(K), R, T, normal, alpha, sd)
+    o64, d64 = vs.reference_rays_f64(H, W, K, R, T, normal, sd)
+    d_err = float(np.abs(d32[traced] - d64[traced]).max())
+    o_err = float(np.abs(o32[traced] - o64[traced]).max())
+    o_scale = float(np.abs(o64[traced]).max())
+    print(f"directions differ by {d_err:.3e}, origins by {o_err:.3e} at a largest coordinate of {o_scale:.3f}")
+    assert d_err <= 1e-6, d_err
+    assert o_err <= 1e-6 * o_scale, (o_err, o_scale)
+    # the float64 triangle test on the float64 rays, brute force; the float32 side is the statement
+    pix = np.argwhere(traced)
+    O, D, o32t, d32t = o64[traced], d64[traced], o32[traced], d32[traced]
+    free32 = stmt[traced] == 1
+    n_diff = 0
+    for s in range(0, len(O), 512):
+        slack, tt = vs.triangle_slack_f64(v, t, O[s:s + 512], D[s:s + 512])
+        acc = (slack[..., :3] >= 0).all(-1) & (slack[..., 0] <= 1) & (slack[..., 3] > 0) & (slack[..., 4] > 0) & (tt >= 0)
+        free64 = ~acc.any(1)
+        for k in np.nonzero(free64 != free32[s:s + 512])[0]:
+            n_diff += 1
+            where = tuple(pix[s + k])
+            if free64[k]:                   # float32 blocked: the triangle it reports is rejected in float64, but by a hair only
+                _, _, _, j = trace_oracle.trace(v, t, o32t[s + k:s + k + 1], d32t[s + k:s + k + 1])
+                assert j[0] >= 0
+                worst = min(float(slack[k, j[0]].min()), float(tt[k, j[0]]))
+                assert -1e-4 <= worst < 0, (where, int(j[0]), slack[k, j[0]].tolist(), float(tt[k, j[0]]))
+            else:                           # float64 blocked: every triangle it accepts sits within 1e-4 of one of its thresholds
+                for j in np.nonzero(acc[k])[0]:
+                    assert float(slack[k, j].min()) <= 1e-4, (where, int(j), slack[k, j].tolist())
+    print(f"float32 and float64 visibility differ at {n_diff} of {len(O)} traced pixels, every one a near-tie")
+
+
 # ---------------------------------------------------------------- GPU: traversal vs brute force
-def _check_against_oracle(v, t, o, d, inplace=False):
-    from materialrefgs_amd.raytracing import RayTracer
-    rt = RayTracer(v, t)
-    to, td = torch.from_numpy(o).cuda(), torch.from_numpy(d).cuda()
-    pos, nrm, depth, ids = rt.trace(to.clone(), td.clone(), inplace=inplace, return_faceids=True)
-    pos, nrm, depth, ids = pos.cpu().numpy(), nrm.cpu().numpy(), depth.cpu().numpy(), ids.cpu().numpy()
+def _compare_with_oracle(v, t, o, d, pos, nrm, depth, ids):
+    """Depth and position bit-equal; ids equal or an exact tie proven by hit_time; normals equal where the ids agree."""
     rpos, rnrm, rdepth, rids = trace_oracle.trace(v, t, o, d)
     np.testing.assert_array_equal(depth, rdepth)                         # bit-exact closest distance
     np.testing.assert_array_equal(pos, rpos)
@@ -161,6 +344,15 @@ def _check_against_oracle(v, t, o, d, inplace=False):
         np.testing.assert_array_equal(tt, rdepth[idx])
     np.testing.assert_array_equal(nrm[same], rnrm[same])
     return depth, ids
+
+
+def _check_against_oracle(v, t, o, d, inplace=False):
+    from materialrefgs_amd.raytracing import RayTracer
+    rt = RayTracer(v, t)
+    to, td = torch.from_numpy(o).cuda(), torch.from_numpy(d).cuda()
+    pos, nrm, depth, ids = rt.trace(to.clone(), td.clone(), inplace=inplace, return_faceids=True)
+    pos, nrm, depth, ids = pos.cpu().numpy(), nrm.cpu().numpy(), depth.cpu().numpy(), ids.cpu().numpy()
+    return _compare_with_oracle(v, t, o, d, pos, nrm, depth, ids)
 
 
 @pytest.mark.gpu
@@ -234,7 +426,8 @@ def _camera_rays_unnormalized(H, W, K, R, T):
 
 @pytest.mark.gpu
 def test_fused_visibility_matches_traced_mirror_rays():
-    """mrgs_bvh_visibility against the reference's sequence (utils/refl_utils.py:379-391) executed with torch ops + RayTracer.trace."""
+    """mrgs_bvh_visibility on maps made on the device: exactly the statement (tests/visibility_statement.py) at every pixel, and beside it
+    the reference's sequence (utils/refl_utils.py:379-391) executed with torch ops + RayTracer.trace, whose rays round differently."""
     from materialrefgs_amd.raytracing import RayTracer
     from materialrefgs_amd.synthetic import orbit_camera
     H, W = 120, 160
@@ -262,8 +455,12 @@ def test_fused_visibility_matches_traced_mirror_rays():
     ref[mask] = (depth >= 10).float().unsqueeze(-1)
     assert vis.shape == (H, W, 1)
     assert bool((vis[~mask] == 1).all())
+    # the kernel's own operations restated in numpy float32 on exactly these maps: every pixel, no allowance
+    stmt = vs.visibility(v, t, H, W, vs.kinv_f32(np.asarray(cam.HWK[2])), cam.R.float().cpu().numpy(), cam.T.float().cpu().numpy(),
+                         normal.cpu().numpy(), alpha.cpu().numpy(), surf_depth.cpu().numpy())
+    assert torch.equal(vis.cpu()[..., 0], torch.from_numpy(stmt))
     mism = float((vis != ref).float().mean())
-    assert mism < 2e-3, mism                                            # rounding of the ray set-up at silhouettes only
+    assert mism < 2e-3, mism                                            # torch builds these rays with other roundings: silhouettes only
     blocked = float((ref[mask] == 0).float().mean())
     assert 0.02 < blocked < 0.98, blocked                               # the case exercises both outcomes
 
@@ -355,3 +552,289 @@ def test_trace_tiny_and_degenerate_meshes():
     assert pos.shape == (0, 3) and depth.shape == (0,)
     with pytest.raises(AssertionError):
         RayTracer(v, t[:8])
+
+
+# ---------------------------------------------------------------- GPU: the fused visibility, exact, every pixel
+def _normal_layouts(n):
+    """normal [H,W,3] on the device, three ways: contiguous; the permuted view of a [3,H,W] tensor (stride_c = H W); channels 1..3 of
+    an [H,W,5] tensor whose other channels hold values a wrong stride would pick up."""
+    H, W, _ = n.shape
+    wide = torch.full((H, W, 5), 7.0, device=n.device)
+    wide[..., 1:4] = n
+    return {"hwc": n.contiguous(), "chw": n.permute(2, 0, 1).contiguous().permute(1, 2, 0), "slice": wide[..., 1:4]}
+
+
+def _alpha_layouts(a):
+    """alpha [H,W] on the device as [H,W,1] contiguous, as the permuted view of [1,H,W] (what render_surfel passes), 2-D, and as
+    channel 1 of an [H,W,2] tensor: the only one of the four whose stride_w is not 1."""
+    wide = torch.full((a.shape[0], a.shape[1], 2), -3.0, device=a.device)
+    wide[..., 1] = a
+    return {"hw1": a.unsqueeze(-1).contiguous(), "1hw": a.unsqueeze(0).contiguous().permute(1, 2, 0), "hw": a.contiguous(),
+            "slice": wide[..., 1:2]}
+
+
+@functools.lru_cache(maxsize=None)
+def _vis_tracer():
+    from materialrefgs_amd.raytracing import RayTracer
+    return RayTracer(*_vis_mesh())
+
+
+def _assert_visibility_is_the_statement(H, W, case):
+    from materialrefgs_amd.synthetic import orbit_camera
+    normal, alpha, sd, stmt, _ = case
+    rt = _vis_tracer()
+    cam = orbit_camera(2, H, W).to("cuda")
+    want = torch.tensor(stmt)                                             # (copies: the cached case is read-only)
+    n_dev, a_dev = torch.tensor(normal).cuda(), torch.tensor(alpha).cuda()
+    sd_dev = torch.tensor(sd).cuda().view(1, H, W)
+    for kn, n_ in _normal_layouts(n_dev).items():
+        for ka, a_ in _alpha_layouts(a_dev).items():
+            vis = rt.visibility(cam.HWK, cam.R, cam.T, n_, a_, sd_dev)
+            assert vis.shape == (H, W, 1)
+            got = vis.cpu()[..., 0]
+            assert torch.equal(got, want), (kn, ka, torch.nonzero(got != want)[:8].tolist())
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("H,W", VIS_SIZES)
+def test_fused_visibility_is_exact_at_every_pixel(H, W):
+    """mrgs_bvh_visibility against tests/visibility_statement.py: equal at every pixel, for every layout of the normal and alpha maps,
+    at sizes with full, partial and ragged 8 x 32 tiles, on inputs that hold alpha <= 0, zero and grazing normals, a zero depth and
+    surface points behind the mesh (_vis_case)."""
+    case = _vis_case(H, W)
+    assert 0.02 < case[4] < 0.98, case[4]                                # the case exercises both outcomes
+    _assert_visibility_is_the_statement(H, W, case)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("want_blocked", [True, False])
+def test_fused_visibility_of_a_single_pixel(want_blocked):
+    """A 1 x 1 image: one lane of one workgroup, once blocked and once free."""
+    case = _vis_case_one_pixel(want_blocked)
+    assert bool(case[3][0, 0] == 0) == want_blocked
+    _assert_visibility_is_the_statement(1, 1, case)
+
+
+# ---------------------------------------------------------------- GPU: small and awkward trees through the C ABI
+def _trace_abi(v, t, o, d, inplace=False):
+    """mrgs_bvh_build + mrgs_bvh_trace by ctypes (RayTracer refuses <= 8 triangles; the library does not): numpy results."""
+    L = _lib()
+    rc, blob = _build(v, t)
+    assert rc == L.MRGS_OK, rc
+    dev = torch.device("cuda")
+    blob_dev = torch.from_numpy(blob).to(dev)
+    to, td = torch.from_numpy(np.ascontiguousarray(o)).to(dev), torch.from_numpy(np.ascontiguousarray(d)).to(dev)
+    n = to.shape[0]
+    pos, nrm = (to, td) if inplace else (torch.empty_like(to), torch.empty_like(td))
+    depth = torch.empty(n, dtype=torch.float32, device=dev)
+    ids = torch.empty(n, dtype=torch.int32, device=dev)
+    p = lambda x: ctypes.c_void_p(x.data_ptr())   # noqa: E731
+    with L.guard(dev):
+        L.check(L.lib().mrgs_bvh_trace(p(blob_dev), len(t), n, p(to), p(td), p(pos), p(nrm), p(depth), p(ids), L.stream_ptr(dev)))
+    return pos.cpu().numpy(), nrm.cpu().numpy(), depth.cpu().numpy(), ids.cpu().numpy()
+
+
+def _check_abi_against_oracle(v, t, o, d, inplace=False):
+    pos, nrm, depth, ids = _trace_abi(v, t, o, d, inplace)
+    return _compare_with_oracle(v, t, o, d, pos, nrm, depth, ids)
+
+
+CUBE_V = np.array([[0, 0, 0], [1, 0, 0], [0, 1, 0], [1, 1, 0], [0, 0, 1], [1, 0, 1], [0, 1, 1], [1, 1, 1], [0.5, 0.5, 0.5], [2, 2, 2]], dtype=np.float32)
+CUBE_T = np.array([[0, 2, 1], [1, 2, 3], [4, 5, 6], [5, 7, 6], [0, 1, 4], [1, 5, 4], [8, 8, 8], [9, 9, 1], [0, 2, 1]], dtype=np.int32)
+
+
+def _small_mesh(n):
+    """The first n of 65 triangles: the nine of the tiny cube case (with its zero-area and duplicated ones), then random ones."""
+    rng = np.random.default_rng(21)
+    extra = rng.uniform(-0.5, 1.5, size=(65 - len(CUBE_T), 3, 3)).astype(np.float32)
+    v = np.concatenate([CUBE_V, extra.reshape(-1, 3)])
+    t = np.concatenate([CUBE_T, len(CUBE_V) + np.arange(3 * len(extra), dtype=np.int32).reshape(-1, 3)])
+    return v, np.ascontiguousarray(t[:n])
+
+
+def _awkward_rays(n=257):
+    """n rays at the unit cube; the first 24 are special: signed zeros in the direction, directions of length 0.25 and 3, origins on
+    a triangle's plane and on a vertex, zero directions (indices 20..23)."""
+    o, d = rays(n, 3)
+    o = (o * np.float32(0.7)).astype(np.float32)
+    nz = np.float32(-0.0)
+    so = np.array([[0.25, 0.25, 3], [0.25, 0.25, 3], [0.25, 0.25, -3], [0.25, 0.25, -3], [3, 0.3, 0.4], [-3, 0.3, 0.4],      # signed zeros
+                   [0.25, 0.25, 3], [0.25, 0.25, -3], [0.3, -2, 0.5], [0.3, -2, 0.5],                                     # lengths 0.25 and 3
+                   [0.25, 0.25, 0], [0.25, 0.25, 0], [0.25, 0.25, 0], [0.6, 0, 0.3],                                      # on a plane
+                   [1, 0, 0], [1, 0, 0], [1, 0, 0], [0, 0, 0], [0, 0, 0], [1, 1, 1],                                      # on a vertex
+                   [0.5, 0.5, 0.5], [0.25, 0.25, 0], [1, 0, 0], [5, 5, 5]], dtype=np.float32)                             # zero direction
+    sd = np.array([[0, nz, -1], [nz, 0, -1], [nz, nz, 1], [0, 0, 1], [-1, nz, 0], [1, nz, nz],
+                   [0, 0, -0.25], [0, 0, 3], [0, 0.25, 0], [0, 3, 0],
+                   [0, 0, 1], [0, 0, -1], [0.6, 0.8, 0], [0, 1, 0],
+                   [0, 0, 1], [-0.6, 0.48, 0.64], [0, 1, 0], [0, 0, 1], [0.577, 0.577, 0.577], [-0.577, -0.577, -0.577],
+                   [0, 0, 0], [0, nz, 0], [nz, nz, nz], [0, 0, 0]], dtype=np.float32)
+    k = min(n, len(so))
+    o[:k], d[:k] = so[:k], sd[:k]
+    if n > 40:
+        d[24:32] = (d[24:32] * np.float32(0.25)).astype(np.float32)
+        d[32:40] = (d[32:40] * np.float32(3.0)).astype(np.float32)
+    return o, d
+
+
+ZERO_RAYS = slice(20, 24)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("shift", [0.0, 1.0], ids=["origin", "far"])
+@pytest.mark.parametrize("n", [1, 2, 4, 5, 8, 9, 16, 17, 64, 65])
+def test_trace_small_trees_through_the_c_abi(n, shift):
+    """1..8 triangles (a forced inner root with empty slots) and the leaf / inner boundaries around 16 and 64, with 1, 255, 256 and
+    257 rays that include signed zeros, non-unit and zero directions and origins on planes and vertices; `far` translates mesh and
+    rays to coordinates of order 1e3."""
+    v, t = _small_mesh(n)
+    o, d = _awkward_rays(257)
+    off = (np.float32(shift) * np.array([1000, -2000, 1500], dtype=np.float32)).astype(np.float32)
+    v, o = (v + off).astype(np.float32), (o + off).astype(np.float32)
+    for count in (257, 256, 255, 1):
+        _check_abi_against_oracle(v, t, o[:count], d[:count], inplace=count == 255)
+    pos, nrm, depth, ids = _trace_abi(v, t, o, d)
+    assert bool((depth[ZERO_RAYS] == 10).all()) and bool((ids[ZERO_RAYS] == -1).all())          # a zero direction misses ...
+    want = (o[ZERO_RAYS] + np.float32(10) * d[ZERO_RAYS]).astype(np.float32)
+    assert pos[ZERO_RAYS].tobytes() == want.tobytes()                                            # ... and stays where it is, bit for bit
+    assert not np.any(nrm[ZERO_RAYS])
+    if n >= 9 and shift == 0:
+        assert (depth < 10).any() and (depth >= 10).any()
+
+
+@pytest.mark.gpu
+def test_trace_mesh_of_repeated_triangles():
+    """1 000 copies of three distinct triangles: every centroid ties with 999 others, so the median split falls back on the index
+    order; every hit is an exact tie between copies, which the id check accepts only with proof."""
+    v = CUBE_V
+    t = np.ascontiguousarray(np.tile(CUBE_T[[0, 2, 4]], (1000, 1)))
+    o, d = _awkward_rays(257)
+    depth, ids = _check_abi_against_oracle(v, t, o, d)
+    assert (depth < 10).any() and (depth >= 10).any()
+
+
+# ---------------------------------------------------------------- GPU: the deepest supported walk
+def _slab_hit(lo, hi, o, d, mint=np.float32(10.0)):
+    """bvh_traverse's box test for rays o, d [N,3] against one box, float32 as written there."""
+    with np.errstate(all="ignore"):
+        iv = np.float32(1.0) / d
+        a, b = (lo[None] - o) * iv, (hi[None] - o) * iv
+        t_in = np.fmax(np.fmax(np.fmin(a[:, 0], b[:, 0]), np.fmin(a[:, 1], b[:, 1])), np.fmax(np.fmin(a[:, 2], b[:, 2]), np.float32(0)))
+        t_out = np.fmin(np.fmin(np.fmax(a[:, 0], b[:, 0]), np.fmax(a[:, 1], b[:, 1])), np.fmax(a[:, 2], b[:, 2]))
+        return (t_in <= t_out * np.float32(1.00001) + np.float32(1e-30)) & (t_in * np.float32(0.99999) < mint), t_in
+
+
+def _first_descent_fill(nodes, codes, o, d):
+    """Stack entries of ray (o, d) when its walk reaches its first leaf: bvh_traverse's child order (the sorting network on t_in,
+    ties keep the slot order) followed from the root."""
+    cur, fill = 0, 0
+    while cur >= 0:
+        dist, code = [], [int(c) for c in codes[cur]]
+        for c in range(4):
+            h, t_in = _slab_hit(nodes[cur, [0 + c, 4 + c, 8 + c]], nodes[cur, [12 + c, 16 + c, 20 + c]], o[None], d[None])
+            dist.append(float(t_in[0]) if (h[0] and code[c] != BVH_EMPTY) else np.inf)
+        for i, j in ((0, 1), (2, 3), (0, 2), (1, 3), (1, 2)):
+            if dist[j] < dist[i]:
+                dist[i], dist[j], code[i], code[j] = dist[j], dist[i], code[j], code[i]
+        assert dist[0] < np.inf
+        fill += sum(1 for c in (1, 2, 3) if dist[c] < np.inf)
+        cur = code[0]
+    return fill
+
+
+def _deep_mesh(staggered):
+    """BVH_LEAF ** BVH_LEVELS + 1 triangles (one root-to-leaf path has BVH_LEVELS inner levels, as in the largest mesh the build
+    accepts): copies of eight large tilted triangles that face away from rays travelling in -z, plus one that faces them, farther
+    along the rays than all the others, stored in the middle of the index range.  `staggered`: copies of the first of them alone,
+    copy i lifted by i * 2**-20 in z, so that every split is along z in index order, the larger (deeper) last quarter of every node
+    is the one the rays enter first, and the walk descends the deepest path first with three siblings pushed at every level."""
+    n = BVH_LEAF ** BVH_LEVELS + 1
+    rng = np.random.default_rng(3)
+    base = np.zeros((9, 3, 3), dtype=np.float32)
+    for k in range(8):                                                    # (A, B, C): n_z = -64, away from the rays
+        j = rng.uniform(-0.3, 0.3, size=(3, 2))
+        base[k] = [[-4 + j[0, 0], -4 + j[0, 1], rng.uniform(0.0, 0.1)], [0 + j[1, 0], 4 + j[1, 1], rng.uniform(2.9, 3.0)],
+                   [4 + j[2, 0], -4 + j[2, 1], rng.uniform(0.4, 0.6)]]
+    base[8] = [[-4, -4, -1.5], [4, -4, -1.5], [0, 4, 2.0]]               # (A, C, B): faces +z, below the others over the ray patch
+    if not staggered:
+        kind = (np.arange(n) % 8).astype(np.int64)
+        kind[n // 2] = 8
+        v = base.reshape(-1, 3)
+        t = (3 * kind[:, None] + np.arange(3)[None]).astype(np.int32)
+    else:
+        lift = np.arange(n, dtype=np.float32) * np.float32(2.0 ** -20)
+        lift[n - 2:] = 1.5                                                # two copies on top of everything ...
+        v = np.broadcast_to(base[0], (n, 3, 3)).copy()
+        v[..., 2] += lift[:, None]
+        base[8] = [[-4, -4, 3.9], [4, -4, 3.9], [0, 4, -0.3]]            # ... and the facing triangle's centroid right below theirs:
+        v[n // 2] = base[8]                                               # it is one of the three leaves pushed at the deepest node
+        v = v.reshape(-1, 3)
+        t = np.arange(3 * n, dtype=np.int32).reshape(-1, 3)
+    gx, gy = np.meshgrid(np.linspace(-0.5, 0.5, 8), np.linspace(-0.5, 0.5, 8), indexing="ij")
+    o = np.stack([gx.ravel(), gy.ravel(), np.full(64, 5.0)], -1).astype(np.float32)
+    d = np.stack([0.02 * gy.ravel() + 0.003, -0.02 * gx.ravel() + 0.001, np.full(64, -1.0)], -1)
+    d = (d / np.linalg.norm(d, axis=1, keepdims=True)).astype(np.float32)
+    return np.ascontiguousarray(v, dtype=np.float32), np.ascontiguousarray(t), base, o, d
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("staggered", [False, True], ids=["copies", "staggered"])
+def test_trace_deepest_supported_walk(staggered):
+    """One wave of 64 rays through a mesh of 4**10 + 1 triangles in which every ray enters every box: the walk with the longest stack
+    the build lets through.  All triangles but one face away from the rays, so nothing is accepted before the one facing triangle is
+    met and no box is pruned after it (it lies below every box's top): about 350 000 node visits and a million triangle tests per
+    lane.  The host confirms that every ray passes through the intersection of all boxes, and the stack fill of the first descent.
+
+    `copies` is the mesh of exact copies of eight triangles: boxes of equal children tie, ties keep the slot order, and the deeper
+    last child is visited last, so the stack reaches 3 * 9 = 27 entries.  `staggered` lifts copy i of one triangle by i * 2**-20:
+    the deepest path is walked first and the stack holds 3 * 10 = 30 entries, the most the build accepts; the facing triangle sits in
+    one of the three leaves pushed last, so a walk that loses or overwrites an entry above 27 loses the hit.  A second launch writes
+    positions and normals over the rays and must give the same bits.
+
+    Measured on an MI355X, 2026-10-21: 0.50 s for the first launch and 0.43 s for the second, the same for both meshes; the whole
+    test takes 1.1 s."""
+    L = _lib()
+    v, t, base, o, d = _deep_mesh(staggered)
+    n = len(t)
+    assert n == BVH_LEAF ** BVH_LEVELS + 1
+    rc, blob = _build(v, t)
+    assert rc == L.MRGS_OK, rc
+    nodes, codes, _, perm = _views(blob, n)
+    assert _inner_levels(codes) == BVH_LEVELS
+    if staggered:                                                          # the facing triangle is one of the three leaves pushed on top of
+        assert n - int(np.nonzero(perm == n // 2)[0][0]) in (3, 4, 5)      # the full stack: the deepest node holds the last five, 1 + 1 + 1 + 2
+    used = np.zeros(len(codes), dtype=bool)
+    used[0] = True
+    used[codes[(codes >= 0) & (codes != BVH_EMPTY)]] = True
+    real = (codes != BVH_EMPTY) & used[:, None]                            # child slots of the nodes the build wrote
+    lo = np.stack([nodes[:, 0:4][real].max(), nodes[:, 4:8][real].max(), nodes[:, 8:12][real].max()]).astype(np.float32)
+    hi = np.stack([nodes[:, 12:16][real].min(), nodes[:, 16:20][real].min(), nodes[:, 20:24][real].min()]).astype(np.float32)
+    assert bool((lo < hi).all()), (lo, hi)                                 # all boxes share a volume ...
+    inside, _ = _slab_hit(lo, hi, o, d)
+    assert bool(inside.all())                                              # ... every ray passes through, so it enters every box (the slab test is monotone)
+    fills = {_first_descent_fill(nodes, codes, o[r], d[r]) for r in (0, 21, 63)}
+    assert fills == {3 * BVH_LEVELS if staggered else 3 * (BVH_LEVELS - 1)}, fills
+    # expected: the facing triangle, at the distance the brute force finds among the nine distinct triangles
+    _, _, rdepth, rids = trace_oracle.trace(base.reshape(-1, 3), np.arange(27).reshape(9, 3), o, d)
+    assert bool((rids == 8).all()) and bool((rdepth < 10).all())
+    dev = torch.device("cuda")
+    blob_dev = torch.from_numpy(blob).to(dev)
+    p = lambda x: ctypes.c_void_p(x.data_ptr())   # noqa: E731
+    results = []
+    for inplace in (False, True):
+        to, td = torch.from_numpy(o).to(dev), torch.from_numpy(d).to(dev)
+        pos, nrm = (to, td) if inplace else (torch.empty_like(to), torch.empty_like(td))
+        depth = torch.empty(64, dtype=torch.float32, device=dev)
+        ids = torch.empty(64, dtype=torch.int32, device=dev)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        with L.guard(dev):
+            L.check(L.lib().mrgs_bvh_trace(p(blob_dev), n, 64, p(to), p(td), p(pos), p(nrm), p(depth), p(ids), L.stream_ptr(dev)))
+        torch.cuda.synchronize()
+        print(f"deepest walk ({'staggered' if staggered else 'copies'}, inplace={inplace}): {time.perf_counter() - t0:.3f} s")
+        results.append((pos.cpu().numpy(), nrm.cpu().numpy(), depth.cpu().numpy(), ids.cpu().numpy()))
+    pos, nrm, depth, ids = results[0]
+    assert bool((ids == n // 2).all()), ids
+    np.testing.assert_array_equal(depth, rdepth)
+    np.testing.assert_array_equal(pos, (o + rdepth[:, None] * d).astype(np.float32))
+    for a, b in zip(results[0], results[1]):
+        assert a.tobytes() == b.tobytes()

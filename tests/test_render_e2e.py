@@ -119,6 +119,22 @@ def test_leaf_gradient_helper_equals_the_plain_end_to_end_checker_on_cpu():
     assert not render_oracle.leaf_gradient_report(hip, grads, render_oracle.LEAF_NAMES)[1]
 
 
+def _capturing_visibility(stash, real):
+    """RayTracer.visibility, with the arguments of its last call kept as numpy arrays in stash["visibility_args"]."""
+    def visibility(self, HWK, R, T, normal_map, render_alpha, surf_depth):
+        stash["visibility_args"] = (HWK, *(a.detach().float().cpu().numpy().copy() for a in (R, T, normal_map, render_alpha, surf_depth)))
+        return real(self, HWK, R, T, normal_map, render_alpha, surf_depth)
+    return visibility
+
+
+def _visibility_statement(mesh, args):
+    """tests/visibility_statement.py on the maps a render handed to RayTracer.visibility: [H,W] float32 tensor."""
+    import visibility_statement as vs
+    (H, W, K), R, T, normal, alpha, surf_depth = args
+    assert normal.shape == (H, W, 3) and alpha.shape[:2] == (H, W) and surf_depth.shape[-2:] == (H, W)
+    return torch.from_numpy(vs.visibility(mesh[0], mesh[1], H, W, vs.kinv_f32(K), R, T, normal, alpha, surf_depth))
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("indirect,srgb", [(False, False), (False, True), (True, False)])
 def test_render_surfel_matches_the_composed_oracle(gpu_device, indirect, srgb):
@@ -153,10 +169,13 @@ def test_render_surfel_matches_the_composed_oracle(gpu_device, indirect, srgb):
         stash["o"] = [t_.detach().cpu().double().requires_grad_(True) for t_ in o[:4]]
         return o
     renderer_mod.surfel_features = capturing
+    real_visibility = RayTracer.visibility
+    RayTracer.visibility = _capturing_visibility(stash, real_visibility)
     try:
         out_h = render_surfel(cam.to(gpu_device), pc_h, pipe, bg.to(gpu_device), srgb=srgb, opt=SimpleNamespace(indirect=indirect))
     finally:
         renderer_mod.surfel_features = glue
+        RayTracer.visibility = real_visibility
     vis_bits = out_h["visibility"].detach().cpu()[0] if indirect else None     # compared with the oracle's own trace below
     inter_o = stash["o"]
     glue_f64 = glue_oracle.surfel_features_reference(pc_o, cam.camera_center.double())
@@ -171,7 +190,8 @@ def test_render_surfel_matches_the_composed_oracle(gpu_device, indirect, srgb):
     if indirect:
         vh, vo = out_h["visibility"].cpu()[0], out_o["visibility_traced"][0].float()
         ok = vh == vo
-        assert float((~ok).float().mean()) < 2e-3           # ray set-up rounding at silhouettes only
+        assert float((~ok).float().mean()) < 2e-3           # ray set-up rounding at silhouettes only (the checker composes its rays in float64)
+        assert torch.equal(vh, _visibility_statement(mesh, stash["visibility_args"]))      # the kernel's own operations on its own inputs: exact
         assert 0.02 < float((vo == 0).float().mean()) < 0.98
     keys = MAP_KEYS + (("indirect_color", "direct_light", "indirect_light") if indirect else ())
     for k in keys:
@@ -288,6 +308,7 @@ def test_render_surfel_pgsr_matches_the_composed_oracle(gpu_device, case, fused,
         stash["o"] = [t_.detach().cpu().double() for t_ in o[:4]]
         return o
     renderer_mod.surfel_features = capturing
+    monkeypatch.setattr(RayTracer, "visibility", _capturing_visibility(stash, RayTracer.visibility))
     try:
         out_h = render_surfel(cam.to(gpu_device), pc_h, pipe, bg.to(gpu_device), srgb=False, opt=SimpleNamespace(indirect=indirect), flag="pgsr")
     finally:
@@ -310,7 +331,8 @@ def test_render_surfel_pgsr_matches_the_composed_oracle(gpu_device, case, fused,
     assert torch.equal(out_h["radii"].cpu(), out_o["radii"]) and torch.equal(out_h["visibility_filter"].cpu(), out_o["visibility_filter"])
     if indirect:
         vh, vo = out_h["visibility"].cpu()[0], out_o["visibility_traced"][0].float()
-        assert float((vh != vo).float().mean()) < 2e-3           # ray set-up rounding at silhouettes only
+        assert float((vh != vo).float().mean()) < 2e-3           # ray set-up rounding at silhouettes only (float64-composed rays)
+        assert torch.equal(vh, _visibility_statement(mesh, stash["visibility_args"]))      # the kernel's own operations on its own inputs: exact
         print(f"case {case}: occluded share {float((vo == 0).float().mean()):.4f}")
         assert 0.02 < float((vo == 0).float().mean()) < 0.98
     keys = MAP_KEYS + ("rend_distance",) + (("indirect_color", "direct_light", "indirect_light") if indirect else ())
