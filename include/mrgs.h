@@ -1499,6 +1499,57 @@ size_t mrgs_export_ws_bytes(void);
 int mrgs_export_rgb8(const MrgsExportConfig* cfg, const MrgsExportMap* maps, void* ws, size_t ws_bytes, uint8_t* out, void* stream);
 int mrgs_eval_jet_table(uint8_t* table768 /*host, [256][3]*/);
 
+/* ---- the training contact sheet (save_training_vis, train_refreal.py:1513-1620; the same in train_refnerf.py and train_glossy.py) ------
+ * mrgs_sheet_rgb8: 1..MRGS_SHEET_MAX_CELLS cells of one H x W, laid out as torchvision.utils.make_grid(nrow, padding, pad_value 0) lays
+ * them out, resampled as F.interpolate's default (legacy) nearest does, to out uint8 [Ho,Wo,3] (pixel-interleaved, 4-byte aligned) -- every
+ * byte computed from the cells' own planes: no stack, no grid and no resampled tensor exist.
+ *   grid      xmaps = min(nrow, n_cells), ymaps = ceil(n_cells / xmaps), Hg = (H + padding) ymaps + padding, Wg = (W + padding) xmaps +
+ *             padding; cell k has its corner at ((k / xmaps) (H + padding) + padding, (k % xmaps) (W + padding) + padding); the borders and
+ *             the unused places of the last row are 0.  n_cells = 1: the image itself, Hg = H, Wg = W (make_grid's early return).
+ *   resample  source index = min((int)floorf(dst * scale), in - 1) per axis, one fp32 multiply; scale_y = (float)Hg / (float)Ho and
+ *             scale_x = (float)Wg / (float)Wo are computed by the caller in fp32 (what F.interpolate computes).  Ho = Hg, Wo = Wg with
+ *             scales 1 is the identity.
+ * Cell modes (fp32, every product and sum rounded on its own; `UNIT rule` and the jet table are mrgs_export_rgb8's):
+ *   UNIT         [1|3,H,W]: the UNIT rule; one channel is replicated
+ *   ABSDIFF      data, data2 [3,H,W]: |data - data2|, then the UNIT rule                                  (error_map, :1518)
+ *   NORMAL_VIEW  [3,H,W]: y = rot x per pixel, y_i = (rot[3i] x_0 + rot[3i+1] x_1) + rot[3i+2] x_2, channels permuted to [2,1,0],
+ *                0.5 y + 0.5, then the UNIT rule                                                          (a(x), :1521-1524)
+ *   DEPTH        [1,H,W]: mrgs_export_rgb8's DEPTH                                                        (visualize_depth)
+ *   LEVEL        [1,H,W]: level = trunc(clip(x * 255, 0, 255)), then jet                                  (visualize_depth(norm=False))
+ *   DEPTH2       [1,H,W]: std = the population standard deviation of the map, accumulated in double on the device from the fp32 values and
+ *                rounded once to fp32; x clipped to [0, 6.f * std]; then DEPTH on the clipped map        (visualize_depth2,
+ *                utils/image_utils.py:83-93).  A map with an infinite value has no std: level 0 throughout.
+ *   MASK         [H W] fp32 (elem F32) or bytes (elem U8: uint8 / bool): level = trunc(clip(float(m) * 255, 0, 255)), then jet
+ *                (visualize_d_mask; the reference's cast of a value outside [0, 255] is undefined, here it clamps)
+ * NaN gives byte 0 / level 0 and is skipped by the statistics (minimum, maximum, std).
+ * At most two launches (one when no cell is DEPTH / DEPTH2), no host read, no allocation.  ws: mrgs_sheet_ws_bytes(), needed (16-byte
+ * aligned) only with a DEPTH / DEPTH2 cell.
+ * MRGS_E_BAD_ARG before any HIP call: wrong struct_size, H, W, Ho or Wo <= 0, n_cells outside 1..MRGS_SHEET_MAX_CELLS, nrow < 1,
+ * padding < 0, flags != 0, a scale that is not positive and finite, a NULL or misaligned pointer, an unknown mode or element type (U8 with
+ * MASK only), channels that do not fit the mode (UNIT 1 or 3; ABSDIFF, NORMAL_VIEW 3; the others 1), ABSDIFF without data2, Ho Wo 3 or a
+ * grid dimension beyond int32; MRGS_E_WORKSPACE for a short ws. */
+#define MRGS_SHEET_MAX_CELLS 32
+enum { MRGS_SHEET_UNIT = 0, MRGS_SHEET_ABSDIFF = 1, MRGS_SHEET_NORMAL_VIEW = 2, MRGS_SHEET_DEPTH = 3, MRGS_SHEET_LEVEL = 4,
+       MRGS_SHEET_DEPTH2 = 5, MRGS_SHEET_MASK = 6 };
+enum { MRGS_SHEET_ELEM_F32 = 0, MRGS_SHEET_ELEM_U8 = 1 };
+typedef struct MrgsSheetCell {
+    const void* data;               /* [channels,H,W] fp32; MASK: [H W] fp32 or bytes */
+    const void* data2;              /* ABSDIFF: the second image; otherwise not read */
+    int32_t channels, mode;
+    int32_t elem;                   /* MRGS_SHEET_ELEM_*: the element type of a MASK cell; F32 for every other mode */
+    int32_t reserved;               /* 0 */
+} MrgsSheetCell;
+typedef struct MrgsSheetConfig {
+    uint32_t struct_size;           /* = sizeof(MrgsSheetConfig) */
+    int32_t H, W, n_cells, nrow, padding, Ho, Wo;
+    float scale_y, scale_x;         /* (float)Hg / (float)Ho, (float)Wg / (float)Wo */
+    float rot[9];                   /* row-major 3x3 of NORMAL_VIEW (viewpoint_cam.R.T); not read without such a cell */
+    uint32_t flags;                 /* 0 */
+} MrgsSheetConfig;
+size_t mrgs_sheet_ws_bytes(void);
+int mrgs_sheet_rgb8(const MrgsSheetConfig* cfg, const MrgsSheetCell* cells, void* ws, size_t ws_bytes, uint8_t* out /*[Ho,Wo,3]*/,
+                    void* stream);
+
 /* ---- the dataset side of a view: 8-bit planes on the device (scene/dataset_readers.py, utils/camera_utils.py, utils/general_utils.py) ----
  * mrgs_image_resize_u8: `pil_image.resize((out_w, out_h))` of PILtoTorch (general_utils.py:21-27), i.e. Pillow's BICUBIC on 8-bit
  * channels, bit for bit.  src: `channels` (1..4) byte channels of an in_h x in_w image, element (c, y, x) at byte c stride_c + y stride_y +

@@ -252,6 +252,21 @@ class MrgsExportConfig(_Sized):
     _fields_ = [("struct_size", ctypes.c_uint32), ("H", c_int32), ("W", c_int32), ("n_maps", c_int32), ("flags", ctypes.c_uint32)]
 
 
+MRGS_SHEET_MAX_CELLS = 32
+(MRGS_SHEET_UNIT, MRGS_SHEET_ABSDIFF, MRGS_SHEET_NORMAL_VIEW, MRGS_SHEET_DEPTH, MRGS_SHEET_LEVEL, MRGS_SHEET_DEPTH2,
+ MRGS_SHEET_MASK) = range(7)
+MRGS_SHEET_ELEM_F32, MRGS_SHEET_ELEM_U8 = 0, 1
+
+
+class MrgsSheetCell(ctypes.Structure):
+    _fields_ = [("data", c_void_p), ("data2", c_void_p), ("channels", c_int32), ("mode", c_int32), ("elem", c_int32), ("reserved", c_int32)]
+
+
+class MrgsSheetConfig(_Sized):
+    _fields_ = [("struct_size", ctypes.c_uint32)] + [(n, c_int32) for n in ("H", "W", "n_cells", "nrow", "padding", "Ho", "Wo")] + \
+               [("scale_y", c_float), ("scale_x", c_float), ("rot", c_float * 9), ("flags", ctypes.c_uint32)]
+
+
 class MrgsResizeConfig(_Sized):
     _fields_ = [("struct_size", ctypes.c_uint32)] + [(n, c_int32) for n in ("channels", "in_h", "in_w", "out_h", "out_w", "ksize_x", "ksize_y")] + \
                [("flags", ctypes.c_uint32), ("stride_c", c_int64), ("stride_y", c_int64), ("stride_x", c_int64)]
@@ -461,6 +476,8 @@ SYMBOLS = {
     "mrgs_export_ws_bytes": (c_size_t, []),
     "mrgs_export_rgb8": (ctypes.c_int, [ctypes.POINTER(MrgsExportConfig), ctypes.POINTER(MrgsExportMap), c_void_p, c_size_t, c_void_p, c_void_p]),
     "mrgs_eval_jet_table": (ctypes.c_int, [c_void_p]),
+    "mrgs_sheet_ws_bytes": (c_size_t, []),
+    "mrgs_sheet_rgb8": (ctypes.c_int, [ctypes.POINTER(MrgsSheetConfig), ctypes.POINTER(MrgsSheetCell), c_void_p, c_size_t, c_void_p, c_void_p]),
     "mrgs_ball_query_ws_bytes": (c_size_t, [c_int64, c_int64]),
     "mrgs_ball_query": (ctypes.c_int, [c_float, c_int32, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
     "mrgs_furthest_point_sample": (ctypes.c_int, [c_void_p, c_int64, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),

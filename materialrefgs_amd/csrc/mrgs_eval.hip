@@ -19,35 +19,9 @@
 #include "mrgs_internal.h"
 #include "mrgs_wave.h"
 #include "mrgs_ssim_tile.h"
+#include "mrgs_rgb8.h"      // the jet table, to_byte, block_minmax, store_lds_bytes: shared with mrgs_sheet.hip
 
 namespace {
-
-// ---- the colour table of DEPTH maps -----------------------------------------------------------------------------------------------
-// THIS LIBRARY'S OWN jet, parity with cv2's COLORMAP_JET table unpinned (cv2 is not installed where this is built, so its array can be
-// neither read nor pinned).  For level L, v = L / 255 in double:
-//   r = clamp(1.5 - |4 v - 3|, 0, 1), g = clamp(1.5 - |4 v - 2|, 0, 1), b = clamp(1.5 - |4 v - 1|, 0, 1), byte = floor(255 c + 0.5)
-// evaluated by the compiler (IEEE double, nothing fused), the same 768 bytes for the device and for mrgs_eval_jet_table.  Which pixel gets
-// which row -- the level -- is what is pinned to the reference's statement.
-struct JetTable { uint8_t rgb[256][3]; };
-constexpr uint8_t jet_byte(double v, double k)
-{
-    double d = 4.0 * v - k;
-    if (d < 0.0) d = -d;
-    double c = 1.5 - d;
-    c = c < 0.0 ? 0.0 : (c > 1.0 ? 1.0 : c);
-    return (uint8_t)(int)(255.0 * c + 0.5);                          // floor of a value >= 0
-}
-constexpr JetTable make_jet()
-{
-    JetTable t{};
-    for (int L = 0; L < 256; ++L) {
-        const double v = (double)L / 255.0;
-        t.rgb[L][0] = jet_byte(v, 3.0); t.rgb[L][1] = jet_byte(v, 2.0); t.rgb[L][2] = jet_byte(v, 1.0);
-    }
-    return t;
-}
-constexpr JetTable JET = make_jet();
-__constant__ JetTable d_jet = make_jet();
 
 // ---- metrics ------------------------------------------------------------------------------------------------------------------------
 constexpr int EPART = 4;          // floats per workgroup partial: ssim, l1, sq, 0 (one 16-byte row)
@@ -134,7 +108,6 @@ __global__ __launch_bounds__(256) void eval_finalize_kernel(EvalArgs a, const fl
 }
 
 // ---- 8-bit export ---------------------------------------------------------------------------------------------------------------------
-constexpr int XCHUNK = 1024;      // pixels per workgroup: 256 threads x 4
 constexpr int XMM = 256;          // workgroups (= partial rows) per DEPTH map of the min/max launch, at most
 
 struct ExportArgs {
@@ -156,16 +129,9 @@ __global__ __launch_bounds__(256) void export_minmax_kernel(ExportArgs a, float2
         const float v = d[i];
         mn = fminf(mn, v); mx = fmaxf(mx, v);
     }
-    mn = wave_shfl_min(mn); mx = wave_shfl_max(mx);
-    if ((tid & 63) == 0) { red[tid >> 6][0] = mn; red[tid >> 6][1] = mx; }
-    __syncthreads();
-    if (tid == 0)
-        partials[(size_t)slot * XMM + blockIdx.x] = make_float2(fminf(fminf(red[0][0], red[1][0]), fminf(red[2][0], red[3][0])),
-                                                                fmaxf(fmaxf(red[0][1], red[1][1]), fmaxf(red[2][1], red[3][1])));
+    const float2 r = block_minmax(mn, mx, tid, red);
+    if (tid == 0) partials[(size_t)slot * XMM + blockIdx.x] = r;
 }
-
-// trunc(clamp(v, 0, 255)) as a byte; NaN -> 0
-__device__ __forceinline__ uint32_t to_byte(float v) { return v >= 0.f ? (uint32_t)(int)fminf(v, 255.f) : 0u; }
 
 // grid (ceil(HW / XCHUNK), n_maps).  The chunk's 3 n bytes start at global byte `obase` of `out`; LDS holds them shifted by obase & 3, so
 // that a 4-byte aligned global address is a 4-byte aligned LDS offset and the body goes out as whole dwords.
@@ -183,11 +149,9 @@ __global__ __launch_bounds__(256) void export_rgb8_kernel(ExportArgs a, const fl
     if (mode == MRGS_EXPORT_DEPTH) {            // wave-uniform: the map's minimum and maximum from the first launch's partial rows
         float lo = INFINITY, hi = -INFINITY;
         if (tid < a.mm_blocks) { const float2 p = partials[(size_t)a.depth_slot[k] * XMM + tid]; lo = p.x; hi = p.y; }
-        lo = wave_shfl_min(lo); hi = wave_shfl_max(hi);
-        if ((tid & 63) == 0) { red[tid >> 6][0] = lo; red[tid >> 6][1] = hi; }
-        __syncthreads();
-        mn = fminf(fminf(red[0][0], red[1][0]), fminf(red[2][0], red[3][0]));
-        const float mx = fmaxf(fmaxf(red[0][1], red[1][1]), fmaxf(red[2][1], red[3][1]));
+        const float2 r = block_minmax(lo, hi, tid, red);
+        mn = r.x;
+        const float mx = r.y;
         den = __fsub_rn(__fadd_rn(1e-20f, mx), mn);                                // 1e-20 + depth.max() - depth.min()
     }
     for (int c = 0; c < C; ++c) {
@@ -219,18 +183,7 @@ __global__ __launch_bounds__(256) void export_rgb8_kernel(ExportArgs a, const fl
         }
     }
     __syncthreads();
-    // global bytes [obase, obase + 3 n) = LDS bytes [shift, shift + 3 n): bytes up to the first aligned dword, whole dwords, bytes behind
-    const int nbytes = 3 * n, end = shift + nbytes;
-    const int body0 = shift ? 4 : 0, body1 = end & ~3;                              // LDS offsets of the dword body [body0, body1)
-    uint8_t* __restrict__ o = out + (obase - shift);                                // 4-byte aligned (out is)
-    if (body1 > body0) {
-        for (int w = body0 / 4 + tid; w < body1 / 4; w += 256)
-            reinterpret_cast<uint32_t*>(o)[w] = reinterpret_cast<const uint32_t*>(sb)[w];
-        if (tid < body0 - shift && shift) o[shift + tid] = sb[shift + tid];
-        if (tid < end - body1) o[body1 + tid] = sb[body1 + tid];
-    } else {                                                                        // fewer bytes than reach an aligned dword
-        for (int i = shift + tid; i < end; i += 256) o[i] = sb[i];
-    }
+    store_lds_bytes(sb, shift, 3 * n, out, obase, tid);
 }
 
 }   // namespace

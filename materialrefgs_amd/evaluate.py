@@ -105,8 +105,12 @@ def jet_table():
     return np.frombuffer(buf, dtype=np.uint8).reshape(256, 3).copy()
 
 
-def visualize_depth(depth):
-    """utils/image_utils.py:73-80 without the numpy / cv2 round trip: [3,H,W] float on the depth's device, the table bytes / 255."""
+def visualize_depth(depth, norm=True):
+    """utils/image_utils.py:73-80 without the numpy / cv2 round trip: [3,H,W] float on the depth's device, the table bytes / 255.
+    norm=False (the level is x * 255 as it is) is materialrefgs_amd.visualize's."""
+    if not norm:
+        from . import visualize
+        return visualize.visualize_depth(depth, norm=False)
     d = depth.reshape((1,) + tuple(depth.shape[-2:])) if depth.dim() >= 2 else depth
     return to_rgb8([(d, DEPTH)])[0].permute(2, 0, 1).float() / 255.0
 
@@ -142,6 +146,7 @@ class _PngWriter:
     def __init__(self, workers=4, level=1):
         self.pool = ThreadPoolExecutor(max_workers=max(1, int(workers)))
         self.level = level
+        self.write = write_png                                         # (path, bytes [H,W,3], level); visualize.TrainingVisualizer writes then renames
         self.ring, self.pending, self.turn = [None, None], [[], []], 0
 
     def submit(self, dev_u8, paths):
@@ -159,7 +164,7 @@ class _PngWriter:
 
         def job(k, path):
             done.synchronize()
-            write_png(path, arr[k], self.level)
+            self.write(path, arr[k], self.level)
         self.pending[slot] = [self.pool.submit(job, k, p) for k, p in enumerate(paths)]
 
     def close(self):
