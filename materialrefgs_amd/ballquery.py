@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .multiview import _focal
+from ._camconst import consts, focal
 
 _p = _lib.ptr
 
@@ -80,16 +80,15 @@ def furthest_point_sample(xyz, npoint, *, return_span=False):
 
 def _view_table(cams, depths, H, W, dev):
     """The MrgsDepthView array of include/mrgs.h on the device, through pinned memory (torch's host allocator keeps the block until the
-    asynchronous copy has run).  Camera poses held on the device cost one host read each."""
+    asynchronous copy has run).  A camera pose held on the device costs one host read the first time."""
     table = (_lib.MrgsDepthView * len(cams))()
     for rec, cam, depth in zip(table, cams, depths):
-        R = torch.as_tensor(cam.R).detach().to("cpu", torch.float32).reshape(-1)
-        T = torch.as_tensor(cam.T).detach().to("cpu", torch.float32).reshape(-1)
-        if R.numel() != 9 or T.numel() != 3:
+        c = consts(cam, dev)
+        if len(c.r_host) != 9 or len(c.t_host) != 3:
             raise ValueError("points_from_depth: a camera needs R [3,3] and T [3]")
         rec.depth = depth.data_ptr()
-        rec.R[:], rec.T[:] = R.tolist(), T.tolist()
-        rec.fx, rec.fy, rec.cx, rec.cy = _focal(cam)
+        rec.R[:], rec.T[:] = c.r_host, c.t_host
+        rec.fx, rec.fy, rec.cx, rec.cy = focal(cam)
     host = torch.empty(ctypes.sizeof(table), dtype=torch.uint8, pin_memory=True)
     host.numpy()[:] = np.frombuffer(table, dtype=np.uint8)
     return host.to(dev, non_blocking=True)

@@ -17,40 +17,16 @@ Differences a caller sees:
     0 with zero gradient; visual_refweight is a device map (the reference builds it on the CPU).
 """
 import ctypes
-import math
 import random
 
 import numpy as np
 import torch
 
 from . import _lib, edges
+from ._camconst import consts, focal
 
 
 _p = _lib.ptr
-
-
-def _focal(cam):
-    """(Fx, Fy, Cx, Cy) of scene/cameras.py:65-68."""
-    W, H = int(cam.image_width), int(cam.image_height)
-    fx = getattr(cam, "Fx", None)
-    fy = getattr(cam, "Fy", None)
-    if fx is None:
-        fx = W / (2.0 * math.tan(cam.FoVx * 0.5))
-    if fy is None:
-        fy = H / (2.0 * math.tan(cam.FoVy * 0.5))
-    return float(fx), float(fy), float(getattr(cam, "Cx", 0.5 * W)), float(getattr(cam, "Cy", 0.5 * H))
-
-
-def _cam_record(cam, device):
-    """world_view_transform (16), R (9), T (3) as one device float32 record; a device-side concat (host tensors are uploaded
-    asynchronously, nothing is read back)."""
-    parts = []
-    for t in (cam.world_view_transform, cam.R, cam.T):
-        t = torch.as_tensor(t)
-        if t.device != device:
-            t = t.to(device, non_blocking=True)
-        parts.append(t.reshape(-1).to(torch.float32))
-    return torch.cat(parts)
 
 
 def basecolor_weight(iteration, schedule):
@@ -252,7 +228,7 @@ def warp_consistency_loss(view_cam, view_pkg, nearest_cam, nearest_pkg, fg_mask,
     a = basecolor_weight(iteration, schedule)
     b = mtlrgh_weight(iteration, schedule)
     cfg = _lib.MrgsWarpConfig(int(H), int(W), int(sample_num), int(patch_size), n_given, flags, seed & 0xFFFFFFFF, seed >> 32,
-                              *_focal(view_cam), *_focal(nearest_cam), float(pixel_noise_th), float(geo_weight), float(a * ncc_weight),
+                              *focal(view_cam), *focal(nearest_cam), float(pixel_noise_th), float(geo_weight), float(a * ncc_weight),
                               float(b * metallic_weight), float(b * roughness_weight))
     fg = fg_mask.reshape(H, W) if fg_mask is not None else None
     if material and fg is None:
@@ -263,7 +239,7 @@ def warp_consistency_loss(view_cam, view_pkg, nearest_cam, nearest_pkg, fg_mask,
     if fg is not None and fg.device != dev:
         fg = fg.to(dev, non_blocking=True)
     vp, npk = view_pkg, nearest_pkg
-    cam_v, cam_n = _cam_record(view_cam, dev), _cam_record(nearest_cam, dev)
+    cam_v, cam_n = consts(view_cam, dev).record, consts(nearest_cam, dev).record
     terms, weight, counts, ws = _WarpLoss.apply(
         depth_v.reshape(H, W), depth_n.reshape(H, W), vp["diffuse_map"], vp["refl_strength_map"], vp["roughness_map"], npk["diffuse_map"],
         npk["refl_strength_map"], npk["roughness_map"], vp["rend_normal"], vp["rend_distance"], fg, keep,

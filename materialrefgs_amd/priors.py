@@ -20,6 +20,7 @@ from typing import NamedTuple, Optional
 import torch
 
 from . import _lib
+from ._camconst import consts
 
 _p = _lib.ptr
 _SLOTS = (0, 1, 2, 3, 4, 5, 6, 7, 8, 12)       # the entries of out_terms[16] (include/mrgs.h) that are terms; the rest are denominators
@@ -127,7 +128,6 @@ def view_prior_terms(viewpoint_cam=None, *, surf_normal=None, rend_normal=None, 
       normal prior: viewpoint_cam (its R), surf_normal and rend_normal [3,H,W], normal_prior [H*W,3], normal_mask [H*W,1] or None;
       mask entropy: rend_alpha [1,H,W], alpha_mask (H*W elements; the same tensor as normal_mask is read once for both);
       ref score:    refl_strength_map and roughness_map [1,H,W], ref_score_image [1,H,W] bool or uint8."""
-    from .renderer import _camera_rt_host
     use_n = surf_normal is not None or rend_normal is not None or normal_prior is not None
     use_e = rend_alpha is not None or alpha_mask is not None
     use_r = refl_strength_map is not None or roughness_map is not None or ref_score_image is not None
@@ -162,7 +162,7 @@ def view_prior_terms(viewpoint_cam=None, *, surf_normal=None, rend_normal=None, 
         prior = _prior_image(normal_prior, "normal_prior", 3 * N, dev)
         if normal_mask is not None:
             mask = _prior_image(normal_mask, "normal_mask", N, dev)
-        rt = _camera_rt_host(viewpoint_cam, dev)
+        rt = consts(viewpoint_cam, dev).rt_host
     if use_e:
         amask = mask if alpha_mask is normal_mask else _prior_image(alpha_mask, "alpha_mask", N, dev)
     if use_r:

@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._camconst import kinv
 
 ATTRIBUTE_NAMES = ("diffuse", "albedo", "normal", "metallic", "roughness")     # the `prefix_*` groups of the reference's reader (:59-75)
 _WIDTHS = {"diffuse": 3, "albedo": 3, "normal": 3, "metallic": 1, "roughness": 1}
@@ -243,8 +244,7 @@ class RayTracer:
         if self.blob is None:
             raise RuntimeError("materialrefgs_amd.raytracing needs a GPU (libmrgs.so has no CPU traversal)")
         H, W, K = HWK
-        Kinv = np.linalg.inv(np.asarray(K, dtype=np.float32)).astype(np.float32).reshape(-1)
-        kin = (ctypes.c_float * 9)(*[float(x) for x in Kinv])
+        kin = (ctypes.c_float * 9)(*kinv(K))
         nm, al = normal_map.detach().float(), render_alpha.detach().float()
         sd = surf_depth.detach().float().contiguous()
         Rc, Tc = R.detach().float().contiguous(), T.detach().float().contiguous()

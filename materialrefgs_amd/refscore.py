@@ -35,25 +35,17 @@ import numpy as np
 import torch
 
 from . import _lib, ballquery
-from ._cache import Bounded, derived
-from .multiview import _focal
+from ._camconst import consts, focal
 
 _p = _lib.ptr
-# host and device camera records, one entry per camera object and device, rebuilt when its pose tensors change (as renderer._camera_entry)
-_CAM_RECORDS = Bounded(4096)
 
 
-def _cam_record(cam, device):
-    """(28 host floats, device float32 [28]): world_view_transform (16), R (9), T (3), built once per camera object and pose.  Pose
-    tensors held on the device cost one host read then, none afterwards; the upload is asynchronous."""
-    srcs = tuple(torch.as_tensor(t) for t in (cam.world_view_transform, cam.R, cam.T))
-
-    def build():
-        host = torch.cat([t.detach().to("cpu", torch.float32).reshape(-1) for t in srcs])
-        if host.numel() != 28:
-            raise ValueError("reflection_score: a camera needs world_view_transform [4,4], R [3,3] and T [3]")
-        return cam, tuple(host.tolist()), host.to(device, non_blocking=True)       # (holds the camera: its id stays its own)
-    return derived(_CAM_RECORDS, (id(cam), device), srcs, build)[1:]
+def _cam_record(cam, device, field):
+    """`record_host` (28 host floats) or `record` (device float32 [28]) of the camera's constants: world_view_transform, R, T."""
+    rec = getattr(consts(cam, device), field)
+    if len(rec) != 28:
+        raise ValueError("reflection_score: a camera needs world_view_transform [4,4], R [3,3] and T [3]")
+    return rec
 
 
 def _photograph(cam):
@@ -118,10 +110,10 @@ def _score(view_cam, view_pkg, neighbours, image_v, pixel_noise_th, patch_size, 
     for i, (cam, _d, _i) in enumerate(neighbours):
         rec = table[i]
         rec.depth, rec.image = keep[4 + 2 * i].data_ptr(), keep[5 + 2 * i].data_ptr()
-        rec.cam[:] = _cam_record(cam, dev)[0]
-        rec.fx, rec.fy, rec.cx, rec.cy = _focal(cam)
-    cam_v = _cam_record(view_cam, dev)[1]
-    cfg = _lib.MrgsRefScoreConfig(H, W, int(patch_size), K, *_focal(view_cam), float(pixel_noise_th))
+        rec.cam[:] = _cam_record(cam, dev, "record_host")
+        rec.fx, rec.fy, rec.cx, rec.cy = focal(cam)
+    cam_v = _cam_record(view_cam, dev, "record")
+    cfg = _lib.MrgsRefScoreConfig(H, W, int(patch_size), K, *focal(view_cam), float(pixel_noise_th))
     with _lib.guard(dev):
         table_dev = None
         if K:

@@ -17,16 +17,16 @@ import math
 import os
 from types import SimpleNamespace
 
-import numpy as np
 import torch
 
 from . import _lib
-from ._cache import Bounded, constant, derived, zero_leaf
+from ._cache import constant, zero_leaf
+from ._camconst import consts, fov_focal, maps_frame
 from ._lib import MrgsMapsFrame, MrgsSurfelGrads, MrgsSurfelParams
 
 from .gs_utils import build_scaling_rotation, eval_sh, flip_align_view, linear_to_srgb, safe_normalize
 from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer, deferred_raster_count
-from .shading import (EnvLight, GradStackHandoff, _kinv_tuple, get_full_color_volume, get_full_color_volume_indirect,
+from .shading import (EnvLight, GradStackHandoff, get_full_color_volume, get_full_color_volume_indirect,
                       get_specular_color_surfel, shade_and_composite_surfel, volume_features, volume_raw_model)
 
 
@@ -197,32 +197,11 @@ def surfel_features(pc, camera_center, pass_xyz=False, viewmatrix=None, indirect
                                  pc._indirect_dc, pc._indirect_rest, camera_center, bool(pass_xyz), viewmatrix, bool(indirect_live), link)
 
 
-_MAPS_FRAME_CACHE = Bounded(4096)
-
-
 def _maps_frame(view, depth_ratio):
-    """Camera constants of depths_to_points (utils/point_utils.py:9-24) for the fused kernels.  Built once per camera on the
-    host (float64) from the camera's matrices and cached: the reference rebuilds them with ~10 small GPU kernels per view."""
-    wvt, fpt = view.world_view_transform, view.full_proj_transform
-    W, H = int(view.image_width), int(view.image_height)
-
-    def build():
-        import numpy as np
-        wv = wvt.detach().cpu().double().numpy()
-        fp = fpt.detach().cpu().double().numpy()
-        c2w = np.linalg.inv(wv.T)
-        ndc2pix = np.array([[W / 2, 0, 0, W / 2], [0, H / 2, 0, H / 2], [0, 0, 0, 1]], dtype=np.float64).T
-        intrins = ((c2w.T @ fp) @ ndc2pix)[:3, :3].T
-        M = c2w[:3, :3] @ np.linalg.inv(intrins)
-        return wv[:3, :3].reshape(-1).tolist(), M.reshape(-1).tolist(), c2w[:3, 3].tolist()
-    ent = derived(_MAPS_FRAME_CACHE, (wvt.data_ptr(), fpt.data_ptr(), W, H), (wvt, fpt), build)
+    """Camera constants of depths_to_points (utils/point_utils.py:9-24) for the fused kernels: `_camconst.maps_frame` as the struct."""
     fr = MrgsMapsFrame()
-    fr.H, fr.W = H, W
-    for i in range(9):
-        fr.view_rot[i] = ent[0][i]
-        fr.ray_matrix[i] = ent[1][i]
-    for i in range(3):
-        fr.ray_origin[i] = ent[2][i]
+    fr.H, fr.W = int(view.image_height), int(view.image_width)
+    fr.view_rot[:], fr.ray_matrix[:], fr.ray_origin[:] = maps_frame(view)
     fr.depth_ratio = float(depth_ratio)
     return fr
 
@@ -322,8 +301,7 @@ def pgsr_unbiased_depth(allmap, rend_distance, viewpoint_camera):
     reference does.  The product path evaluates this inside mrgs_surfel_maps_forward / _backward (MrgsMapsFrame::rend_distance); this
     function is the torch statement the kernels are tested against (tests/test_shading.py)."""
     H, W = int(viewpoint_camera.image_height), int(viewpoint_camera.image_width)
-    fx = W / (2.0 * math.tan(viewpoint_camera.FoVx * 0.5))
-    fy = H / (2.0 * math.tan(viewpoint_camera.FoVy * 0.5))
+    fx, fy = fov_focal(viewpoint_camera)
     dev, dt = allmap.device, allmap.dtype
     rx = (torch.arange(W, device=dev, dtype=dt) - 0.5 * (W - 1)) / fx
     ry = (torch.arange(H, device=dev, dtype=dt) - 0.5 * (H - 1)) / fy
@@ -341,9 +319,7 @@ def compute_2dgs_normal_and_regularizations(allmap, viewpoint_camera, pipe, retu
     if rend_distance is not None:
         # the unbiased depth is formed inside the kernels from the plane-distance map (round 5; pgsr_unbiased_depth is the torch statement
         # of the same expression, kept as the kernels' checker): no eight torch kernels and no [7,H,W] concatenation in front of them
-        H, W = int(viewpoint_camera.image_height), int(viewpoint_camera.image_width)
-        fr.pgsr_fx = W / (2.0 * math.tan(viewpoint_camera.FoVx * 0.5))
-        fr.pgsr_fy = H / (2.0 * math.tan(viewpoint_camera.FoVy * 0.5))
+        fr.pgsr_fx, fr.pgsr_fy = fov_focal(viewpoint_camera)
     rn, sd, sn, nm, ra, rd, *twin = _SurfelMaps.apply(allmap, fr, bool(return_depth_normal), bool(return_normal_map), bool(twin_alpha), rend_distance)
     out = {"render_alpha": ra, "render_normal": rn, "render_depth_median": None, "render_depth_expected": None,
            "render_dist": rd, "surf_depth": sd, "surf_normal": sn if return_depth_normal else None}
@@ -719,13 +695,9 @@ class _MirrorRays(torch.autograd.Function):
 def _mirror_rays(viewpoint_camera, normal_map, surf_depth):
     """Mirror rays of every pixel of a rendered view: from the surface point along the mirror direction of the view ray about
     `normal_map`, origin moved 1e-3 along it (one HIP launch; `mirror_rays_torch` states the same with torch ops)."""
-    import numpy as np
-    H, W, K = viewpoint_camera.HWK
-    dev = surf_depth.device
-    Kinv = tuple(np.linalg.inv(np.asarray(K, dtype=np.float32)).astype(np.float32).reshape(-1).tolist())
-    R = torch.as_tensor(viewpoint_camera.R, dtype=torch.float32, device=dev).contiguous()
-    T = torch.as_tensor(viewpoint_camera.T, dtype=torch.float32, device=dev).contiguous()
-    return _MirrorRays.apply(normal_map.reshape(H, W, 3).float(), surf_depth, Kinv, R, T)
+    H, W, _ = viewpoint_camera.HWK
+    c = consts(viewpoint_camera, surf_depth.device)
+    return _MirrorRays.apply(normal_map.reshape(H, W, 3).float(), surf_depth, c.Kinv, c.R, c.T)
 
 
 class _MirrorRaysBlended(torch.autograd.Function):
@@ -770,41 +742,10 @@ class _MirrorRaysBlended(torch.autograd.Function):
         return g_n.permute(2, 0, 1), g_al.reshape(ctx.shapes[0]), g_sd.reshape(ctx.shapes[1]), None, None, None
 
 
-_CAM_CONSTS = Bounded(4096)
-
-
-def _camera_entry(viewpoint_camera, dev):
-    K = viewpoint_camera.HWK[2]
-
-    def build():
-        R = torch.as_tensor(viewpoint_camera.R, dtype=torch.float32, device=dev).contiguous()
-        T = torch.as_tensor(viewpoint_camera.T, dtype=torch.float32, device=dev).contiguous()
-        return viewpoint_camera, _kinv_tuple(K), R, T, []   # holds the camera: its id stays its own; [] is filled by _camera_rt_host
-    return derived(_CAM_CONSTS, (id(viewpoint_camera), dev), (viewpoint_camera.R, viewpoint_camera.T, K), build)
-
-
-def _camera_consts(viewpoint_camera, dev):
-    """K^-1 (host tuple), Camera.R and Camera.T as device tensors, built once per camera object AND pose: an entry is only reused while
-    R, T and the intrinsics are what it was built from (a pose refinement or new intrinsics on the same object rebuild it)."""
-    return _camera_entry(viewpoint_camera, dev)[1:4]
-
-
-def _camera_rt_host(viewpoint_camera, dev):
-    """Camera.R transposed as nine host floats (row-major, float32 values), kept in the camera's `_camera_consts` entry: the world-to-
-    camera rotation of the normal prior (priors.py).  Filled at the first request; an R held on the device costs one host read then,
-    none afterwards, a numpy or CPU R none at all."""
-    slot = _camera_entry(viewpoint_camera, dev)[4]
-    if not slot:
-        R = viewpoint_camera.R
-        R = R.detach().to("cpu", torch.float32).numpy() if torch.is_tensor(R) else np.asarray(R, dtype=np.float32)
-        slot.append(tuple(float(x) for x in R.T.reshape(-1)))
-    return slot[0]
-
-
 def _mirror_rays_blended(viewpoint_camera, rend_normal, rend_alpha, surf_depth):
     """Mirror rays of every pixel from render_surfel's maps: rend_normal [3,H,W], rend_alpha [1,H,W], surf_depth [1,H,W]."""
-    Kinv, R, T = _camera_consts(viewpoint_camera, surf_depth.device)
-    return _MirrorRaysBlended.apply(rend_normal, rend_alpha, surf_depth, Kinv, R, T)
+    c = consts(viewpoint_camera, surf_depth.device)
+    return _MirrorRaysBlended.apply(rend_normal, rend_alpha, surf_depth, c.Kinv, c.R, c.T)
 
 
 class _TracedBlend(torch.autograd.Function):

@@ -20,6 +20,7 @@ from torch import nn
 
 from . import _lib
 from ._cache import Bounded, constant, derived, zero_leaf as _zero_leaf
+from ._camconst import consts
 from .gs_utils import build_rotation, eval_sh
 
 MID_CHANNELS = 16    # optix_utils.py:28-35: ray_o 3, ray_d 3, dpt 1, acc 1, norm 3, aux 2, rgb 3 per tracing depth
@@ -442,9 +443,8 @@ class HardwareRendering(nn.Module):
                 # reference's own code pins it (tests/test_reference_render.py).
                 _, _, K = camera.HWK
                 K = torch.as_tensor(K, dtype=torch.float32, device=means3D.device)
-                R = torch.as_tensor(camera.R, dtype=torch.float32, device=means3D.device)
-                T = torch.as_tensor(camera.T, dtype=torch.float32, device=means3D.device)
-                uvd = (K @ (R @ means3D.detach()[..., None] + T))[..., 0]
+                c = consts(camera, means3D.device)
+                uvd = (K @ (c.R @ means3D.detach()[..., None] + c.T))[..., 0]
                 uvd[..., :2] = uvd[..., :2] / uvd[..., 2:]
                 vis = (uvd[..., 2] >= 0.2) & (uvd[..., 0] >= 0.0) & (uvd[..., 0] <= camera.image_width) & (uvd[..., 1] >= 0.0) & \
                       (uvd[..., 1] <= camera.image_height)

@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._camconst import consts
 from .evaluate import _PngWriter, write_png
 
 (UNIT, ABSDIFF, NORMAL_VIEW, DEPTH, LEVEL, DEPTH2, MASK) = (_lib.MRGS_SHEET_UNIT, _lib.MRGS_SHEET_ABSDIFF, _lib.MRGS_SHEET_NORMAL_VIEW,
@@ -151,11 +152,10 @@ def visualize_d_mask(d_mask, H, W):
 
 
 # ---- save_training_vis ------------------------------------------------------------------------------------------------------------------------
-def view_rotation(viewpoint_cam):
-    """`viewpoint_cam.R.T.float()` (:1519) as a float32 [3,3] array on the host; R is a numpy array or a tensor."""
-    R = viewpoint_cam.R
-    R = R.detach().cpu().numpy() if torch.is_tensor(R) else np.asarray(R)
-    return np.ascontiguousarray(R.T.astype(np.float32))
+def view_rotation(viewpoint_cam, device=None):
+    """`viewpoint_cam.R.T.float()` (:1519) as a float32 [3,3] host array, from the camera's constants on `device` (default: where R is)."""
+    device = device or getattr(viewpoint_cam.R, "device", torch.device("cpu"))
+    return np.array(consts(viewpoint_cam, device).rt_host, dtype=np.float32).reshape(3, 3)
 
 
 def training_cells(viewpoint_cam, render_pkg, opt, iteration, initial_stage, d_mask=None, ref_weight=None, base_color_loss_map=None,
@@ -218,7 +218,7 @@ def save_training_vis(viewpoint_cam, gaussians, background, render_fn, pipe, opt
     cells = [cell for _name, cell in training_cells(viewpoint_cam, render_pkg, opt, iteration, initial_stage, d_mask, ref_weight,
                                                     base_color_loss_map, ref_score)]
     os.makedirs(visualize_path, exist_ok=True)
-    jobs = [(contact_sheet(cells, nrow=4, padding=2, height=height, rot=view_rotation(viewpoint_cam)),
+    jobs = [(contact_sheet(cells, nrow=4, padding=2, height=height, rot=view_rotation(viewpoint_cam, render_pkg["render"].device)),
              os.path.join(visualize_path, f"{iteration:06d}.png"))]
     if not initial_stage:
         if opt.volume_render_until_iter > opt.init_until_iter and iteration <= opt.volume_render_until_iter:

@@ -343,8 +343,8 @@ def test_no_host_read(gpu_device):
     masks, normals = {"view": dv["mask"]}, {"view": dv["prior"]}
     up = [torch.tensor(u, device=dev) for u in UP]
     priors.mask_entropy_loss(leaves["rend_alpha"].detach(), dv["mask"])       # (the library is loaded)
-    from materialrefgs_amd.renderer import _camera_rt_host
-    _camera_rt_host(cam, dev)                                                 # the camera's constants: uploaded once per camera and pose
+    from materialrefgs_amd._camconst import consts
+    consts(cam, dev).rt_host                                                  # the camera's constants: uploaded once per camera and pose
     torch.cuda.synchronize()
     torch.cuda.set_sync_debug_mode("error")
     try:

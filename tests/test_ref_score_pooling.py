@@ -45,7 +45,7 @@ def _maps():
 
 
 def _focal(cam):
-    from materialrefgs_amd.multiview import _focal as focal
+    from materialrefgs_amd._camconst import focal
     return focal(cam)
 
 
