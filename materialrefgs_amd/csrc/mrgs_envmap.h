@@ -3,12 +3,16 @@
 // shading), mrgs_prefilter.hip (filters, mips) and mrgs_bounce.hip (one-bounce light) uses lives here once.
 //
 // The reference samples with two nvdiffrast `dr.texture` launches.  nvdiffrast is not vendored (requirements.txt:57 pins a local path), so
-// its sampling rules are RESTATED here and in oracle/shading_oracle.py -- parity unpinned for the lookups: texel centres at
-// (i + 0.5) / res, bilinear taps, `clamp` boundary for the 2D LUT, seamless cube edges (a tap that falls off a face is taken from the face
-// across the edge; the non-existent corner tap gets zero weight and the other three are renormalised), mip level = mip_level_bias clamped
-// to [0, levels-1] with linear interpolation between the two nearest levels.  Face/orientation convention: cube_to_dir
-// (scene/light_utils.py:24-31).  The quotients of the fetch are v_rcp_f32, 1 ulp, not IEEE: the note at shade_rcp below says why and
-// which kernels keep the IEEE quotient.
+// its sampling rules are RESTATED here and in oracle/shading_oracle.py: texel centres at (i + 0.5) / res, bilinear taps, `clamp` boundary
+// for the 2D LUT, seamless cube edges (a tap that falls off a face is taken from the face across the edge; the non-existent corner tap
+// gets zero weight and the other three are renormalised), mip level = mip_level_bias clamped to [0, levels-1] with linear interpolation
+// between the two nearest levels.  Face/orientation convention: cube_to_dir (scene/light_utils.py:24-31).
+// tests/test_envmap_seams.py holds the restatement to the geometry of a cube and the kernels to the restatement.  PINNED BY GEOMETRY:
+// the face orientation, all 12 seams, all 8 vertices, the weight sums, the level shares, the tangency of the direction gradient and
+// that it is the slope of the forward inside a cell.  STILL A RESTATEMENT of nvdiffrast: the drop-and-renormalise rule of a vertex
+// cell and its gradient with the renormalisation held constant.
+// The quotients of the fetch are v_rcp_f32, 1 ulp, not IEEE: the note at shade_rcp below says why and which kernels keep the IEEE
+// quotient.
 #pragma once
 #include "mrgs_internal.h"
 #include "mrgs_wave.h"

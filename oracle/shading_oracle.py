@@ -4,13 +4,17 @@ Restates, with torch.autograd supplying the reference gradients:
   * EnvLight.get_mip / EnvLight.__call__            (scene/light.py:88-129)
   * sample_camera_rays, reflection, get_specular_color_surfel without visibility tracing
                                                      (utils/refl_utils.py:54-73,95-98,364-419)
-PARITY UNPINNED for the texture lookups: the reference performs them with nvdiffrast's `dr.texture`, which is not vendored
+The texture lookups: the reference performs them with nvdiffrast's `dr.texture`, which is not vendored
 (requirements.txt:57 pins a local path) and cannot be imported here, and the reference has no test for this path.  The
 sampling rules are therefore restated from nvdiffrast's documented behaviour (texel centres at (i+0.5)/res, bilinear,
 `clamp` boundary for the 2D LUT, seamless cube edges, trilinear between integer mip levels at LOD = mip_level_bias); the
-cube face/orientation convention IS pinned in-tree by cube_to_dir (scene/light_utils.py:24-31) and checked by the
-known-answer test "a lookup at cube_to_dir(texel centre) returns that texel" (tests/test_shading.py).  The kernels' statement of the
-same rules is csrc/mrgs_envmap.h, which the lookups and the shading (mrgs_shade.hip) and the one-bounce light (mrgs_bounce.hip) share.
+cube face/orientation convention is pinned in-tree by cube_to_dir (scene/light_utils.py:24-31).  tests/test_envmap_seams.py holds this
+restatement to the geometry of a cube, in float64 and with no second restatement in between.  PINNED BY GEOMETRY: the face
+orientation (texel centres on all six faces), all 12 seams and all 8 vertices (continuity), the weight sums, the level shares, the
+tangency of the direction gradient and that it is the slope of the forward inside a cell.  STILL A RESTATEMENT of nvdiffrast: the
+drop-and-renormalise rule of a vertex cell and its gradient, which holds the renormalisation constant.  The kernels' statement of the
+same rules is csrc/mrgs_envmap.h, which the lookups and the shading (mrgs_shade.hip) and the one-bounce light (mrgs_bounce.hip) share;
+csrc/mrgs_volume.hip restates the taps once more for fp64 coordinates.
 Everything else (ray set-up, mirror direction, Fresnel-style weight, compositing) is elementwise arithmetic restated literally.
 """
 import numpy as np
@@ -136,12 +140,18 @@ def lut_fetch(lut, uv):
     return (1 - wy) * ((1 - wx) * lut[y0, x0] + wx * lut[y0, x1]) + wy * ((1 - wx) * lut[y1, x0] + wx * lut[y1, x1])
 
 
-def sample_camera_rays(H, W, K, R, T):
-    """utils/refl_utils.py:54-73 (R is Camera.R, stored transposed; pixel centres at integer coordinates)."""
+def sample_camera_rays(H, W, K, R, T, dtype=torch.float32):
+    """utils/refl_utils.py:54-73 (R is Camera.R, stored transposed; pixel centres at integer coordinates).  The reference sets the rays
+    up in float32 whatever follows, and so does this by default.  dtype=torch.float64: the same expressions in float64 on the same
+    float32 K, R, T -- for a caller that wants the float64 reading of the WHOLE chain: `pixel_world - rays_o` cancels a camera distance,
+    so float32 rays sit a few ulp from the exact ones, which a fetch of a fine level magnifies by res / 2."""
+    np_dt = np.float64 if dtype == torch.float64 else np.float32
     R = R.T
-    i, j = np.meshgrid(np.arange(W, dtype=np.float32), np.arange(H, dtype=np.float32), indexing="xy")
+    if dtype == torch.float64:
+        R, T = R.double(), T.double()
+    i, j = np.meshgrid(np.arange(W, dtype=np_dt), np.arange(H, dtype=np_dt), indexing="xy")
     xy1 = np.stack([i, j, np.ones_like(i)], axis=2)
-    pixel_camera = torch.tensor(np.dot(xy1, np.linalg.inv(K.astype(np.float32)).T))
+    pixel_camera = torch.tensor(np.dot(xy1, np.linalg.inv(K.astype(np.float32).astype(np_dt)).T))
     rays_o = (-R.T @ T.unsqueeze(-1)).flatten()
     pixel_world = (pixel_camera - T[None, None]).reshape(-1, 3) @ R
     rays_d = pixel_world - rays_o[None]
@@ -150,11 +160,11 @@ def sample_camera_rays(H, W, K, R, T):
 
 
 def specular_color_surfel(mips, lut, albedo, H, W, K, R, T, normal_map, render_alpha, refl_strength, roughness,
-                          min_roughness=0.08, max_roughness=0.5):
+                          min_roughness=0.08, max_roughness=0.5, rays_dtype=torch.float32):
     """get_specular_color_surfel (utils/refl_utils.py:364-419) with pc.ray_tracer = None.
     albedo/normal_map [H,W,3], render_alpha/refl_strength/roughness [H,W,1] -> specular [3,H,W], direct_light [3,H,W],
-    specular_weight [H,W,3]."""
-    rays_cam, _ = sample_camera_rays(H, W, K, R.cpu(), T.cpu())
+    specular_weight [H,W,3].  rays_dtype: see sample_camera_rays."""
+    rays_cam, _ = sample_camera_rays(H, W, K, R.cpu(), T.cpu(), rays_dtype)
     w_o = -rays_cam.to(normal_map.device)
     NdotV = torch.sum(w_o * normal_map, dim=-1, keepdim=True)
     rays_refl = 2 * normal_map * NdotV - w_o
@@ -167,9 +177,9 @@ def specular_color_surfel(mips, lut, albedo, H, W, K, R, T, normal_map, render_a
     return specular.permute(2, 0, 1), direct_light.permute(2, 0, 1), specular_weight
 
 
-def mirror_dirs(H, W, K, R, T, normal_map):
+def mirror_dirs(H, W, K, R, T, normal_map, rays_dtype=torch.float32):
     """The normalised mirror directions [H*W,3] and NdotV [H*W] of specular_color_surfel (same arithmetic)."""
-    rays_cam, _ = sample_camera_rays(H, W, K, R.cpu(), T.cpu())
+    rays_cam, _ = sample_camera_rays(H, W, K, R.cpu(), T.cpu(), rays_dtype)
     w_o = -rays_cam.to(normal_map.device)
     NdotV = torch.sum(w_o * normal_map, dim=-1, keepdim=True)
     rays_refl = 2 * normal_map * NdotV - w_o
@@ -177,7 +187,7 @@ def mirror_dirs(H, W, K, R, T, normal_map):
     return rays_refl.reshape(-1, 3), NdotV.reshape(-1)
 
 
-def shade_taps(mip_res, H, W, K, R, T, normal_map, roughness, min_roughness=0.08, max_roughness=0.5):
+def shade_taps(mip_res, H, W, K, R, T, normal_map, roughness, min_roughness=0.08, max_roughness=0.5, rays_dtype=torch.float32):
     """Where every pixel of specular_color_surfel fetches (no gradients): the cubemap taps and the quantities at which its per-pixel
     gradient is discontinuous.  mip_res: resolutions of the levels, finest first.  Returns dict:
       keys [N,8] int64: level << 24 | texel of the two levels' four taps, -1 where the tap's weight (level share x bilinear) is 0 --
@@ -188,7 +198,7 @@ def shade_taps(mip_res, H, W, K, R, T, normal_map, roughness, min_roughness=0.08
       face_gap [N]:     (|major| - |second|) / |major| of the mirror direction (the face decision);
       ndv [N], lut_uv [N,2], level [N]."""
     with torch.no_grad():
-        dirs, ndv = mirror_dirs(H, W, K, R, T, normal_map)
+        dirs, ndv = mirror_dirs(H, W, K, R, T, normal_map, rays_dtype)
         rough = roughness.reshape(-1)
         n = len(mip_res)
         level = get_mip(rough, n, min_roughness, max_roughness)
