@@ -896,6 +896,30 @@ typedef struct MrgsAdamTensor {
 } MrgsAdamTensor;
 int mrgs_adam_step(const MrgsAdamTensor* tensors, int32_t n_tensors, double beta1, double beta2, double eps, void* stream);
 
+/* The same update for the rows a view touched only ("sparse Adam over visible gaussians").  Every tensor is [n_rows, row_floats]
+ * (numel == n_rows * row_floats, row_floats <= MRGS_ADAM_ROWS_MAX_WIDTH); masks[0 .. n_masks - 1], 1 <= n_masks <= MRGS_ADAM_ROWS_MAX_MASKS,
+ * are device uint8 [n_rows] (bool storage is the same bytes) and a row is VISIBLE when any of them is non-zero there.  `masks` itself
+ * is a HOST array.  Visible rows get exactly the update of mrgs_adam_step; param, exp_avg and exp_avg_sq of every other row keep their
+ * bits (and are neither read nor written where a whole 16-byte piece of the tensor is invisible).  `step` counts the calls, not the times
+ * a row was visible.  bias_correction == 0: step_size = lr and the second moment is used as it is (the plain rule of the 3DGS code base's
+ * sparse optimizer); otherwise both corrections are formed from `step` as in mrgs_adam_step.  The whole list is validated before the first
+ * launch: a refused call (MRGS_E_BAD_ARG; MRGS_E_UNSUPPORTED for a row wider than the limit or 2^43 elements and more) has moved nothing. */
+#define MRGS_ADAM_ROWS_MAX_MASKS 4
+#define MRGS_ADAM_ROWS_MAX_WIDTH 32768
+typedef struct MrgsAdamRowsTensor {
+    float* param;
+    const float* grad;
+    float* exp_avg;
+    float* exp_avg_sq;
+    int64_t numel;
+    int32_t row_floats;
+    float lr;
+    int32_t step;
+    int32_t reserved;      /* 0 */
+} MrgsAdamRowsTensor;
+int mrgs_adam_step_rows(const MrgsAdamRowsTensor* tensors, int32_t n_tensors, int64_t n_rows, const uint8_t* const* masks, int32_t n_masks,
+                        int32_t bias_correction, double beta1, double beta2, double eps, void* stream);
+
 /* ---- densify / prune compaction ----------------------------------------------------------------
  * Replaces the ~50 boolean-index calls of _prune_optimizer / prune_points (scene/gaussian_model.py:856-905) -- parameter tensors, their
  * two Adam moments, xyz_gradient_accum / denom / max_radii2D -- by one scan of the keep mask and one gather launch for all tensors.

@@ -156,6 +156,14 @@ class MrgsAdamTensor(ctypes.Structure):
                 ("lr", c_float), ("step", c_int32)]
 
 
+MRGS_ADAM_ROWS_MAX_MASKS = 4
+
+
+class MrgsAdamRowsTensor(ctypes.Structure):
+    _fields_ = [("param", c_void_p), ("grad", c_void_p), ("exp_avg", c_void_p), ("exp_avg_sq", c_void_p), ("numel", c_int64),
+                ("row_floats", c_int32), ("lr", c_float), ("step", c_int32), ("reserved", c_int32)]
+
+
 class MrgsCompactTensor(ctypes.Structure):
     _fields_ = [("src", c_void_p), ("dst", c_void_p), ("row_floats", c_int32)]
 
@@ -364,6 +372,8 @@ SYMBOLS = {
     "mrgs_bvh_visibility": (ctypes.c_int, [c_void_p, c_int64, c_int32, c_int32, ctypes.POINTER(c_float), c_void_p, c_void_p,
                                            ctypes.POINTER(MrgsStridedMap), ctypes.POINTER(MrgsStridedMap), c_void_p, c_void_p, c_void_p]),
     "mrgs_adam_step": (ctypes.c_int, [ctypes.POINTER(MrgsAdamTensor), c_int32, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_void_p]),
+    "mrgs_adam_step_rows": (ctypes.c_int, [ctypes.POINTER(MrgsAdamRowsTensor), c_int32, c_int64, ctypes.POINTER(c_void_p), c_int32, c_int32,
+                                           ctypes.c_double, ctypes.c_double, ctypes.c_double, c_void_p]),
     "mrgs_indirect_blend_forward": (ctypes.c_int, [c_int32, c_int32, c_void_p, c_void_p, ctypes.POINTER(MrgsStridedMap),
                                                    ctypes.POINTER(MrgsStridedMap), c_void_p, c_void_p, c_void_p, c_void_p]),
     "mrgs_indirect_blend_backward": (ctypes.c_int, [c_int32, c_int32, c_void_p, c_void_p, ctypes.POINTER(MrgsStridedMap),

@@ -45,9 +45,11 @@ def param_groups(model, training_args):
 
 
 def training_setup(model, training_args, optimizer_cls=None):
-    """training_setup (:417-453) without the learning-rate scheduler: statistics buffers + the Adam (lr = 0, eps = 1e-15)."""
+    """training_setup (:417-453) without the learning-rate scheduler: statistics buffers + the Adam (lr = 0, eps = 1e-15).
+    Without `optimizer_cls`, training_args.optimizer_type == "sparse_adam" selects optim.SparseAdam (an absent attribute: Adam)."""
     if optimizer_cls is None:
-        from .optim import Adam as optimizer_cls
+        from .optim import default_optimizer_cls
+        optimizer_cls = default_optimizer_cls(training_args)
     dev = model._xyz.device
     P = model._xyz.shape[0]
     model.percent_dense = getattr(training_args, "percent_dense", 0.01)

@@ -222,7 +222,7 @@ class EnvGaussianModel:
         self.max_radii2D = torch.zeros((n,), device=points.device)
 
     def training_setup(self, training_args, lr_downfactor_geo=5., anchored_lst=[]):
-        from .optim import Adam
+        from .optim import default_optimizer_cls
         self.percent_dense = 0.01                      # the reference fixes it here, whatever training_args.percent_dense says
         n, dev = self.get_xyz.shape[0], self._xyz.device
         self.xyz_gradient_accum = torch.zeros((n, 1), device=dev)
@@ -236,7 +236,7 @@ class EnvGaussianModel:
             {"params": [self._scaling], "lr": training_args.scaling_lr, "name": "scaling"},
             {"params": [self._rotation], "lr": training_args.rotation_lr, "name": "rotation"},
         ]
-        self.optimizer = Adam(groups, lr=0.0, eps=1e-15)
+        self.optimizer = default_optimizer_cls(training_args)(groups, lr=0.0, eps=1e-15)     # optimizer_type == "sparse_adam": SparseAdam
         self.xyz_scheduler_args = expon_lr_func(lr_init=training_args.position_lr_init * self.spatial_lr_scale,
                                                 lr_final=training_args.position_lr_final * self.spatial_lr_scale,
                                                 lr_delay_mult=training_args.position_lr_delay_mult, max_steps=training_args.position_lr_max_steps)
